@@ -13,11 +13,19 @@ over one batch of synthetic frames resident in HBM.  Default workload = BASELINE
 256 frames x (35k points, 6 cameras, 20 masks of 1600x900).  Every rank owns its own batch
 (weak scaling); after the K steps one RCCL gather ships the fixed-size box records to rank 0.
 Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline figures (`value`, `ms_per_step`).  `--full` adds
+everything else: the second mask mode, the spread of K-step regions and one long region, the
+unamortised rate, per-stage and roofline figures, the CPU baselines and the end-to-end leg.  `--dump-outputs DIR` writes
+rank 0's results of the last timed step to DIR/<name>.npy (the inputs are seeded: two builds compare output for output).
 """
 import argparse
+import contextlib
 import json
+import multiprocessing
 import os
 import platform
+import signal
 import sys
 import time
 
@@ -35,6 +43,70 @@ if ROOT not in sys.path:
 from cm3d_amd import dist as cdist, lifting, synthetic as syn  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0     # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured float4 copy)
+DUMP_BYTES = 64_000_000   # --dump-outputs: all files together
+GEN_CHUNK = 16            # frames per generation job
+
+
+def _make_frames(job):
+    cfg, first, n = job
+    return [syn.make_frame(cfg, first + i) for i in range(n)]
+
+
+def _gpu_open():
+    """True when this process holds the GPU driver (/dev/kfd) open: a profiler can start the runtime before Python runs."""
+    for fd in os.listdir("/proc/self/fd"):
+        try:
+            if os.readlink(f"/proc/self/fd/{fd}") == "/dev/kfd":
+                return True
+        except OSError:
+            pass
+    return False
+
+
+def make_batches_frames(cfg, firsts, n, workers, loud=False):
+    """The frames firsts[b] .. firsts[b] + n - 1 of `cfg` for every b, in `workers` forked processes (a C2 batch takes ~10 s on
+    one core).  make_frame is seeded by the frame index alone, so the frames do not depend on the split.  A process that has the
+    GPU open does not fork (a child would hold it too): it makes the frames itself.  loud: progress lines on stderr."""
+    jobs = [(cfg, f0 + i, min(GEN_CHUNK, n - i)) for f0 in firsts for i in range(0, n, GEN_CHUNK)]
+    chunks = []
+    # The workers take SIGTERM's default action: a handler they inherit (a profiler's) can block in a forked child, and the pool's
+    # terminate() would wait for that child forever.  On success the pool is closed and joined: the workers leave without a signal.
+    with (multiprocessing.get_context("fork").Pool(min(workers, len(jobs)), initializer=signal.signal, initargs=(signal.SIGTERM, signal.SIG_DFL))
+          if workers > 1 and len(jobs) > 1 and not _gpu_open() else contextlib.nullcontext()) as pool:
+        for c in (pool.imap(_make_frames, jobs) if pool else map(_make_frames, jobs)):
+            chunks.append(c)
+            if loud:
+                print(f"generating: frame {len(chunks) * GEN_CHUNK} / {len(jobs) * GEN_CHUNK}", file=sys.stderr, flush=True)
+        if pool:
+            pool.close()
+            pool.join()
+    per = len(jobs) // max(1, len(firsts))
+    return [[f for c in chunks[b * per:(b + 1) * per] for f in c] for b in range(len(firsts))]
+
+
+def dump_outputs(arrays, out_dir, budget=DUMP_BYTES):
+    """Writes `arrays` (name -> numpy array) as out_dir/<name>.npy: float32 arrays as they are, every other one as float64 (integers
+    below 2**53 exactly).  Every file holds finite values only: where an array has NaN / +inf / -inf (lane_dist's +inf of a mask
+    without a lane, a box of degenerate geometry) the value is written as 0 and <name>_nonfinite.npy beside it says which
+    (0 finite, 1 NaN, 2 +inf, 3 -inf).  The budget is shared out smallest array first; an array larger than its share keeps a
+    fixed, seeded sample of its rows, in their order (the same rows in its _nonfinite file)."""
+    groups = {}
+    for k, v in arrays.items():
+        a = np.asarray(v, np.float32 if np.asarray(v).dtype == np.float32 else np.float64)
+        code = np.select([np.isnan(a), np.isposinf(a), np.isneginf(a)], [1.0, 2.0, 3.0], 0.0)
+        groups[k] = {k: np.where(code == 0, a, 0).astype(a.dtype), k + "_nonfinite": code} if code.any() else {k: a}
+    os.makedirs(out_dir, exist_ok=True)
+    left = budget - 256 * sum(len(g) for g in groups.values())             # (the .npy headers)
+    nbytes = {k: sum(a.nbytes for a in g.values()) for k, g in groups.items()}
+    for i, k in enumerate(sorted(groups, key=lambda k: (nbytes[k], k))):
+        g, share = groups[k], left // (len(groups) - i)
+        if nbytes[k] > share:
+            n = g[k].shape[0]
+            keep = np.sort(np.random.default_rng(0).choice(n, share // (nbytes[k] // n), replace=False))
+            g = {name: a[keep] for name, a in g.items()}
+        for name, a in g.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            left -= a.nbytes
 
 
 def packed_rect_bytes(bbox, Wp):
@@ -336,11 +408,17 @@ def main(argv=None):
     ap.add_argument("--config", default="c2", help="synthetic config (c1,c2,c4,c5,tiny)")
     ap.add_argument("--masks", default="rle", choices=["rle", "dense"],
                     help="mask input resident in HBM: COCO-RLE run lengths (the on-disk contract) or dense uint8")
-    ap.add_argument("--cpu-sample", type=int, default=48, help="frames timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: second mask mode, spread and long regions, unamortised rate, "
+                         "per-stage and roofline figures, CPU baselines, end-to-end leg")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the results of rank 0's last timed step (its own batch) to DIR/<name>.npy (float32 / float64, finite, "
+                         "at most 64 MB in all)")
+    ap.add_argument("--cpu-sample", type=int, default=48, help="--full: frames timed on the CPU oracle (0 = skip)")
     ap.add_argument("--lane-points", type=int, default=50000)
-    ap.add_argument("--no-secondary", action="store_true", help="skip the second mask mode")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the second mask mode")
     ap.add_argument("--cpu-workers", type=int, default=-1,
-                    help="processes of the all-cores CPU baseline (-1 = every core this job may use; 0 = skip)")
+                    help="--full: processes of the all-cores CPU baseline (-1 = every core this job may use; 0 = skip)")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="override a field of the synthetic config (e.g. --set n_masks=80); for experiments")
     ap.add_argument("--in-flight", type=int, default=4,
@@ -356,12 +434,14 @@ def main(argv=None):
                     help="time the SAM3D fusion matching (SURVEY 8 f4) on this many samples instead of the lifting path")
     ap.add_argument("--rehearse-launch", action="store_true", help="launch, rendezvous and the record exchange only (no GPU needed)")
     ap.add_argument("--e2e-frames", type=int, default=int(os.environ.get("CM3D_BENCH_E2E_FRAMES", "2048")), metavar="FRAMES",
-                    help="frames of the end-to-end leg of the default line (files -> labels through the entry point; 0 = skip)")
+                    help="--full: frames of the end-to-end leg (files -> labels through the entry point; 0 = skip)")
     ap.add_argument("--end-to-end", type=int, default=0, metavar="FRAMES",
                     help="time the entry point instead: files of a synthetic dataset of this many frames -> pseudolabels json")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus >= 1")
+    if args.steps < 1:
+        ap.error("--steps >= 1")
     if args.gpus > 1 and "RANK" not in os.environ:
         return self_launch(args, argv)
     env_world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -377,12 +457,8 @@ def main(argv=None):
     if args.end_to_end > 0:
         return end_to_end_bench(args)
 
-    rank, world, local_rank = cdist.init_from_env()
-    if os.environ.get("CM3D_SINGLE_DEVICE"):      # rehearsal of the N>1 path on a one-GPU box (with CM3D_DIST_BACKEND=gloo)
-        local_rank = 0
-    dev = torch.device(f"cuda:{local_rank}")
-    torch.cuda.set_device(dev)
-
+    # The synthetic batches are made before anything initialises the GPU (make_batches_frames forks); init_from_env reads the same rank.
+    rank = int(os.environ.get("RANK", "0"))
     over = {}
     for kv in args.set:
         k, v = kv.split("=", 1)
@@ -395,32 +471,39 @@ def main(argv=None):
     lanes = [syn.make_lane_table([600.0, 1600.0], args.lane_points, seed=7 + rank, extent=260.0)]
     frame_lane = [0] * args.frames
     # `depth` independent batches stay in flight (LiftPipeline: one engine + stream each); step k runs on batch k % depth
-    batches = []
-    cache_dir = os.environ.get("CM3D_BENCH_CACHE")     # experiments: packed batches kept between runs of one GPU call (generation takes
-    for slot in range(depth):                          # longer than the measurement); only without the CPU legs, which need the frames
-        import pickle
-        # (rank 0 needs the frames themselves for the CPU legs; every other rank only the packed batch)
-        cache = cache_dir and (args.cpu_sample == 0 or rank != 0) and os.path.join(
+    import pickle
+    keep_frames = args.full and env_world == 1 and args.cpu_sample > 0      # the CPU legs run the oracle over batch 0's frames
+    batches = [None] * depth
+    todo = []
+    cache_dir = os.environ.get("CM3D_BENCH_CACHE")     # experiments: packed batches kept between runs of one GPU call; not when the
+    for slot in range(depth):                          # frames themselves are needed
+        cache = cache_dir and not keep_frames and os.path.join(
             cache_dir, f"bench_{args.config}_{args.frames}_{rank * depth + slot}_{args.lane_points}_{'_'.join(sorted(args.set))}.pkl")
         if cache and os.path.exists(cache):
-            batches.append((None, pickle.load(open(cache, "rb"))))
-            continue
-        if args.reuse_batch and batches:
-            batches.append(batches[0])
-            continue
-        fr = []
-        for i in range(args.frames):
-            fr.append(syn.make_frame(cfg, (rank * depth + slot) * args.frames + i))
-            if rank == 0 and cfg.n_points * cfg.n_sweeps >= 300000 and (i + 1) % 32 == 0:
-                print(f"generating: batch {slot}, frame {i + 1} / {args.frames}", file=sys.stderr, flush=True)     # a long run must not look hung
-        batches.append((fr, lifting.pack_frames(fr, lanes, frame_lane)))
+            batches[slot] = (None, pickle.load(open(cache, "rb")))
+        elif not (args.reuse_batch and slot > 0):
+            todo.append((slot, cache))
+    # (a job is granted 16 cores of a GPU node: more processes than that only queue)
+    workers = max(1, min(16, visible_cores() // env_world))
+    made = make_batches_frames(cfg, [(rank * depth + slot) * args.frames for slot, _ in todo], args.frames, workers,
+                               loud=rank == 0 and cfg.n_points * cfg.n_sweeps >= 300000)     # a long run must not look hung
+    for (slot, cache), fr in zip(todo, made):
+        batches[slot] = (fr if keep_frames else None, lifting.pack_frames(fr, lanes, frame_lane))
         if cache:
             os.makedirs(cache_dir, exist_ok=True)
-            pickle.dump(batches[-1][1], open(cache, "wb"), protocol=4)
+            pickle.dump(batches[slot][1], open(cache, "wb"), protocol=4)
+    del made
+    batches = [b if b is not None else batches[0] for b in batches]        # --reuse-batch: resident copies of batch 0
     frames, hb = batches[0]
     t_gen = time.perf_counter() - t_gen
 
-    modes = [args.masks] + ([] if args.no_secondary else [m for m in ("rle", "dense") if m != args.masks])
+    rank, world, local_rank = cdist.init_from_env()
+    if os.environ.get("CM3D_SINGLE_DEVICE"):      # rehearsal of the N>1 path on a one-GPU box (with CM3D_DIST_BACKEND=gloo)
+        local_rank = 0
+    dev = torch.device(f"cuda:{local_rank}")
+    torch.cuda.set_device(dev)
+
+    modes = [args.masks] + ([] if args.no_secondary or not args.full else [m for m in ("rle", "dense") if m != args.masks])
     pipe = lifting.LiftPipeline(dev, depth=depth, keep_cloud=args.keep_cloud)
     for slot in range(depth):
         with torch.cuda.stream(pipe.streams[slot]):
@@ -453,7 +536,7 @@ def main(argv=None):
         if world > 1 and mode == modes[0]:
             cdist.gather_records(eng.b.box, dst=0)      # untimed: sets up the RCCL channels the final gather uses (the records' buffer exists since upload)
         ev_every = 1 if args.steps <= 16 else 8        # an event pair costs ~5 us of stream time: sample every 8th step
-        for _ in range(0, args.steps, ev_every):        # created (first record) outside the timed region
+        for _ in range(0, args.steps if args.full else 0, ev_every):        # created (first record) outside the timed region
             pe = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             pe[0].record()
             pe[1].record()
@@ -475,7 +558,7 @@ def main(argv=None):
         t0 = time.perf_counter()
         for step in range(args.steps):
             pe = None
-            if step % ev_every == 0:    # HIP events around the roofline kernel only, recorded by the library on its launch stream
+            if args.full and step % ev_every == 0:    # HIP events around the roofline kernel only, recorded by the library on its launch stream
                 pe = ev["project"][step // ev_every]
             if graphs is not None and pe is None:
                 with torch.cuda.stream(pipe.streams[step % depth]):
@@ -503,6 +586,12 @@ def main(argv=None):
             torch.distributed.all_gather(every, mine)
             per_rank_dt = [float(t.item()) for t in every]
             dt = max(per_rank_dt)                        # the job's time is its slowest rank's
+        if args.dump_outputs and mode == modes[0] and rank == 0:
+            _, res = pipe.collect((args.steps - 1) % depth, full=True)        # the batch of the last timed step
+            dump_outputs(res, args.dump_outputs)
+        if not args.full:
+            results[mode] = dict(dt=dt, per_rank_dt=per_rank_dt)
+            continue
         # how far a K-step region can be off: the same K passes five more times, and one region of >= 0.5 s
         spread, long_rate = None, None
         if mode == modes[0]:
@@ -605,6 +694,23 @@ def main(argv=None):
     frames_total = args.frames * world * args.steps
     value = frames_total / r["dt"]
     cloud_stored = eng.b.points is not None
+    out = {
+        "metric": "pseudo-label frames/sec on nuScenes-shaped sweeps", "value": round(value, 1), "unit": "frames/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(r["dt"] / args.steps * 1e3, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.config}: {args.frames} frames/GPU x ({cfg.n_points}x{cfg.n_sweeps} pts, {cfg.n_cams} cams, "
+                               f"{cfg.n_masks} masks {cfg.width}x{cfg.height}), masks resident as {main_mode}",
+                   "frames_per_gpu": args.frames, "points_per_frame": cfg.n_points * cfg.n_sweeps, "masks_per_frame": cfg.n_masks,
+                   "mask_size": [cfg.width, cfg.height], "lane_points": args.lane_points, "mask_input": main_mode,
+                   "batches_in_flight": depth, "distinct_batches": 1 if args.reuse_batch else depth, "cloud_materialised": cloud_stored,
+                   "parallelism": f"frame-sharded x{world}, {depth} independent batches in flight per GPU, one RCCL gather of box records"},
+        "ranks_in_group": torch.distributed.get_world_size() if world > 1 else 1,
+        "per_rank_ms_per_step": [round(t / args.steps * 1e3, 4) for t in r["per_rank_dt"]],
+        "gen_seconds": round(t_gen, 1),
+        "cpu_baseline": None,
+    }
+    if not args.full:
+        return emit(out, world)
     by = compulsory_bytes(hb, eng.b.planes, r["sum_hits"], main_mode, r["fused"], cloud_stored, r["rect_bytes"], r["hit_rows"])
 
     def rate(nbytes, ms):
@@ -731,16 +837,7 @@ def main(argv=None):
         kernels["sweeps"] = roof("k_sweep_xform", r["stage_ms"]["sweeps"], "k_sweep_xform", "HBM streaming, one pass; stage time incl. the launch boundary")
         kernels["sweeps"]["traffic"] = per_kernel.get("k_sweep_xform")
     pass_rate = by["pass_total"] * (value / world / args.frames) / 1e9       # bytes of one pass x passes per second per GPU
-    out = {
-        "metric": "pseudo-label frames/sec on nuScenes-shaped sweeps", "value": round(value, 1), "unit": "frames/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(r["dt"] / args.steps * 1e3, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{args.config}: {args.frames} frames/GPU x ({cfg.n_points}x{cfg.n_sweeps} pts, {cfg.n_cams} cams, "
-                               f"{cfg.n_masks} masks {cfg.width}x{cfg.height}), masks resident as {main_mode}",
-                   "frames_per_gpu": args.frames, "points_per_frame": cfg.n_points * cfg.n_sweeps, "masks_per_frame": cfg.n_masks,
-                   "mask_size": [cfg.width, cfg.height], "lane_points": args.lane_points, "mask_input": main_mode,
-                   "batches_in_flight": depth, "distinct_batches": 1 if args.reuse_batch else depth, "cloud_materialised": cloud_stored,
-                   "parallelism": f"frame-sharded x{world}, {depth} independent batches in flight per GPU, one RCCL gather of box records"},
+    out.update({
         # the timed K steps are short (a few ms at the driver's --steps): the same region five more times, and one of >= 0.5 s
         "value_spread": r["spread"], "value_long": None if r["long_rate"] is None else r["long_rate"]["value"],
         # what the HOST needs to hand one pass to its stream (Python + ~12 launches), measured in the long region: the pass is GPU-bound while
@@ -750,8 +847,6 @@ def main(argv=None):
         # the same K passes with the lane index rebuilt in every pass and the medoid stage without the previous pass's hint: what a
         # job pays whose every batch brings new lane tables (the timed loop replays resident batches: index built once, hint warm)
         "value_unamortised": r["unamortised"],
-        "ranks_in_group": torch.distributed.get_world_size() if world > 1 else 1,
-        "per_rank_ms_per_step": [round(t / args.steps * 1e3, 4) for t in r["per_rank_dt"]],
         "roofline": roofline,
         "roofline_group": roofline_group,
         "kernels": kernels,
@@ -764,8 +859,7 @@ def main(argv=None):
                           note="SURVEY 8(d)'s per-frame figures, which price a full read of every bit-packed mask; this design never "
                                "moves those bytes, so they are reference numbers only and enter no fraction"),
         "boxes_per_step": r["n_boxes"], "in_mask_points_per_step": r["sum_hits"], "max_points_in_a_mask": r["max_hits"],
-        "gen_seconds": round(t_gen, 1),
-    }
+    })
     for mode in modes[1:]:
         o = results[mode]
         out[f"value_{mode}_masks"] = round(frames_total / o["dt"], 1)
@@ -783,8 +877,6 @@ def main(argv=None):
                 out["cpu_baseline_all_cores"]["sample"] += f"; host has {os.cpu_count()} cores, {cores} usable by this job (affinity / cgroup quota)"
             except Exception as exc:        # a reported extra: never let it break the bench line
                 out["cpu_baseline_all_cores"] = {"error": repr(exc)}
-    else:
-        out["cpu_baseline"] = None
     # what a user of the drop-in script gets: files on disk -> labels, timed here so that the driver's run carries it
     if world == 1 and args.e2e_frames > 0 and args.cpu_sample > 0:
         try:
@@ -796,6 +888,10 @@ def main(argv=None):
             out["end_to_end"] = end_to_end_bench(e_args, quick=True)
         except Exception as exc:            # a reported extra: never let it break the bench line
             out["end_to_end"] = {"error": repr(exc)}
+    return emit(out, world)
+
+
+def emit(out, world):
     print(json.dumps(out))
     if world > 1:
         torch.distributed.destroy_process_group()

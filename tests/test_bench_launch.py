@@ -66,3 +66,49 @@ def test_byte_accounting_counts_only_bytes_that_move():
     full_masks = 2 * 50 * 4 * 900
     assert by["pass_total"] < full_masks + by["k_project_hits"] + 200000     # nothing near a full read of the packed masks
     assert bench.visible_cores() >= 1
+
+
+def test_dumped_outputs_fit_the_budget_and_batches_do_not_depend_on_the_split(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+    from cm3d_amd import synthetic as syn
+    rng = np.random.default_rng(1)
+    arrs = {"xyz": rng.normal(size=(50000, 3)).astype(np.float32), "idx": np.arange(60000, dtype=np.int32),
+            "flags": np.array([1, 3, 0], np.int32), "none": np.zeros((0, 10))}
+    for d in ("a", "b"):
+        bench.dump_outputs(arrs, str(tmp_path / d), budget=400_000)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 400_000
+    for name in arrs:
+        a, b = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert a.dtype == (np.float32 if name == "xyz" else np.float64) and np.array_equal(a, b)
+    assert np.array_equal(np.load(tmp_path / "a" / "flags.npy"), [1, 3, 0])
+    # NaN / inf: written as 0, with <name>_nonfinite.npy saying which -- finite files, nothing lost, the same rows when sampled
+    odd = np.where(np.arange(60000) % 7 == 0, np.inf, np.arange(60000.0))
+    odd[3], odd[5] = np.nan, -np.inf
+    bench.dump_outputs({"ok": np.zeros(3), "odd": odd}, str(tmp_path / "c"), budget=200_000)
+    assert sorted(f.name for f in (tmp_path / "c").iterdir()) == ["odd.npy", "odd_nonfinite.npy", "ok.npy"]
+    v, code = np.load(tmp_path / "c" / "odd.npy"), np.load(tmp_path / "c" / "odd_nonfinite.npy")
+    assert np.isfinite(v).all() and 0 < v.size < 60000 and v.shape == code.shape and sum(f.stat().st_size for f in (tmp_path / "c").iterdir()) <= 200_000
+    fin = v[code == 0]                          # odd[i] == i where finite: a sampled row keeps its value, and the rows stay in order
+    assert (code == 2).any() and np.all(np.diff(fin) > 0) and np.all(fin % 7 != 0) and np.all(v[code != 0] == 0)
+    bench.dump_outputs({"odd": odd}, str(tmp_path / "d"))
+    assert np.array_equal(np.select([np.load(tmp_path / "d" / "odd_nonfinite.npy") == k for k in (1, 2, 3)], [np.nan, np.inf, -np.inf],
+                                    np.load(tmp_path / "d" / "odd.npy")), odd, equal_nan=True)
+    idx = np.load(tmp_path / "a" / "idx.npy")
+    assert 0 < idx.size < 60000 and np.all(np.diff(idx) > 0)          # a sample of the rows, in their order
+    cfg = syn.config("tiny")
+    split = bench.make_batches_frames(cfg, [0, 20], 20, 3)
+    for b, f0 in enumerate((0, 20)):
+        one = [syn.make_frame(cfg, f0 + i) for i in range(20)]
+        assert [f.token for f in split[b]] == [f.token for f in one]
+        assert all(np.array_equal(x.sweeps_raw[0], y.sweeps_raw[0]) and x.rles == y.rles for x, y in zip(split[b], one))
+
+
+def test_generation_pool_ends_under_a_blocking_sigterm_handler():
+    """A profiler can install a SIGTERM handler that blocks in a forked child; the generation pool must still end (its workers take
+    the default action and, on success, leave without a signal)."""
+    code = ("import signal, sys, time; sys.path.insert(0, '.'); import bench; from cm3d_amd import synthetic as syn; "
+            "signal.signal(signal.SIGTERM, lambda *a: time.sleep(1e9)); "
+            "print(len(bench.make_batches_frames(syn.config('tiny'), [0, 16], 16, 2)[1]))")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "16", r.stderr[-2000:]

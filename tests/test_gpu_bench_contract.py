@@ -4,6 +4,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ def _run(*args):
 
 
 def test_lifting_bench_line():
-    d = _run("--config", "tiny", "--frames", "8", "--steps", "6", "--warmup", "2", "--cpu-sample", "2", "--cpu-workers", "2",
+    d = _run("--full", "--config", "tiny", "--frames", "8", "--steps", "6", "--warmup", "2", "--cpu-sample", "2", "--cpu-workers", "2",
              "--lane-points", "2000", "--e2e-frames", "64")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
@@ -61,6 +62,37 @@ def test_lifting_bench_line():
     one = _run("--config", "tiny", "--frames", "8", "--steps", "3", "--warmup", "1", "--cpu-sample", "0", "--no-secondary", "--in-flight", "1",
                "--lane-points", "2000")
     assert one["config"]["batches_in_flight"] == 1 and one["cpu_baseline"] is None
+
+
+def test_plain_line_and_dumped_outputs(tmp_path, oracle):
+    """Without --full the line holds the headline only; --dump-outputs writes the results of the last timed step: float32 / float64
+    arrays, the same in two runs of one command line, and the oracle's results over that step's frames."""
+    from cm3d_amd import lifting, synthetic as syn
+    from tests.helpers import oracle_batch
+    cmd = ("--config", "tiny", "--frames", "8", "--steps", "6", "--warmup", "2", "--lane-points", "2000")
+    runs = [_run(*cmd, "--dump-outputs", str(tmp_path / k)) for k in "ab"]
+    for d in runs:
+        assert d["steps"] == 6 and d["warmup"] == 2 and d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["value"] > 0 and abs(d["value"] - 8 / (d["ms_per_step"] * 1e-3)) / d["value"] < 0.01
+        assert d["cpu_baseline"] is None and not {"roofline", "kernels", "value_spread", "end_to_end"} & set(d)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and {"box.npy", "flags.npy", "hit_idx.npy", "hit_off.npy", "medoid_pos.npy"} <= set(names)
+    got = {}
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all() and np.array_equal(a, b), n
+        got[n[:-4]] = a
+    slot = (6 - 1) % runs[0]["config"]["batches_in_flight"]           # the batch of step 6: frames slot*8 .. slot*8+7 (bench.py, rank 0)
+    assert slot != 0                                                  # (not the slot of the first upload: a dump of slot 0 would not pass)
+    frames = [syn.make_frame(syn.config("tiny"), slot * 8 + i) for i in range(8)]
+    lanes = [syn.make_lane_table([600.0, 1600.0], 2000, seed=7, extent=260.0)]
+    exp = oracle_batch(oracle, frames, lanes, [0] * 8, lifting.pack_frames(frames, lanes, [0] * 8))
+    for k in ("hit_off", "hit_idx", "medoid_pos", "flags", "lane_idx"):
+        assert np.array_equal(got[k], exp[k]), k
+    assert np.allclose(got["box"], exp["box"], rtol=0, atol=1e-4)
+    valid = (exp["flags"] & 1) == 1             # lane_dist: the reference's distance where there is a box; +inf (code 2) where there is no lane
+    assert np.array_equal(got["lane_dist"][valid], exp["lane_dist"][valid])
+    assert (got["lane_idx"] < 0).any() and np.array_equal(got["lane_dist_nonfinite"] == 2, got["lane_idx"] < 0)
 
 
 def test_two_ranks_from_a_bare_command_line():

@@ -6,7 +6,7 @@ LIBS=()
 while [ $# -gt 0 ] && [[ "$1" == *.so ]]; do LIBS+=("$1"); shift; done
 for rep in 1 2; do
   for lib in "${LIBS[@]}"; do
-    CM3D_LIB=$lib python3 bench.py --cpu-sample 0 --no-secondary --steps 300 "$@" > /tmp/ab.json 2>/dev/null || exit 1
+    CM3D_LIB=$lib python3 bench.py --full --cpu-sample 0 --no-secondary --steps 300 "$@" > /tmp/ab.json 2>/dev/null || exit 1
     python3 - "$lib" <<'PY'
 import json, sys
 d = json.loads(open('/tmp/ab.json').read().strip().splitlines()[-1])

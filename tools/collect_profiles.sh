@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export CM3D_BENCH_CACHE=/tmp/cm3d_bench_cache      # the same synthetic batches for all passes (generated once)
-B="python3 bench.py --cpu-sample 0 --no-secondary"
+B="python3 bench.py --full --cpu-sample 0 --no-secondary"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt -o k --output-format csv -- $B --steps 20 --warmup 3 > $OUT/bench_profiled.json 2> $OUT/kt.err || exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt1 -o k --output-format csv -- $B --steps 20 --warmup 3 --in-flight 1 > $OUT/bench_profiled_one_batch.json 2> $OUT/kt1.err || exit 1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/fetch -o p --output-format csv -- $B --steps 3 --warmup 1 > $OUT/fetch.json 2> $OUT/fetch.err || exit 1

@@ -12,18 +12,18 @@ part=${1:-a}
 if [ "$part" == "a" ]; then
   tools/collect_profiles.sh r03 || exit 1
   echo "profiles collected"
-  python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
+  python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
   echo "default bench done"
-  python3 bench.py --steps 20 --warmup 5 --cpu-sample 0 --no-secondary > $OUT/bench_driver_flags.json 2>> $OUT/bench_default.err || exit 1
-  python3 bench.py --cpu-sample 0 --no-secondary --in-flight 1 > $OUT/bench_one_batch.json 2>> $OUT/bench_default.err || exit 1
+  python3 bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --no-secondary > $OUT/bench_driver_flags.json 2>> $OUT/bench_default.err || exit 1
+  python3 bench.py --full --cpu-sample 0 --no-secondary --in-flight 1 > $OUT/bench_one_batch.json 2>> $OUT/bench_default.err || exit 1
   python3 bench.py --end-to-end 4096 > $OUT/end_to_end_4096.json 2> $OUT/e2e.err || exit 1
   echo "part a done"
 else
   for c in c1 c4; do
-    timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/kt_$c -o k --output-format csv -- python3 bench.py --config $c --frames 256 --reuse-batch --cpu-sample 0 --no-secondary --steps 30 --warmup 3 > $OUT/bench_${c}_256frames_profiled.json 2> $OUT/kt_$c.err || exit 1
-    python3 bench.py --config $c --frames 256 --reuse-batch --cpu-sample 0 --no-secondary --steps 100 > $OUT/bench_${c}_256frames.json 2>> $OUT/kt_$c.err || exit 1
+    timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/kt_$c -o k --output-format csv -- python3 bench.py --full --config $c --frames 256 --reuse-batch --cpu-sample 0 --no-secondary --steps 30 --warmup 3 > $OUT/bench_${c}_256frames_profiled.json 2> $OUT/kt_$c.err || exit 1
+    python3 bench.py --full --config $c --frames 256 --reuse-batch --cpu-sample 0 --no-secondary --steps 100 > $OUT/bench_${c}_256frames.json 2>> $OUT/kt_$c.err || exit 1
     echo "$c done"
   done
-  python3 bench.py --config c5 --frames 256 --reuse-batch --cpu-sample 0 --no-secondary --steps 20 --warmup 3 > $OUT/bench_c5_256frames.json 2> $OUT/c5.err || exit 1
+  python3 bench.py --full --config c5 --frames 256 --reuse-batch --cpu-sample 0 --no-secondary --steps 20 --warmup 3 > $OUT/bench_c5_256frames.json 2> $OUT/c5.err || exit 1
   echo "part b done"
 fi

@@ -6,12 +6,13 @@ REPS=$1; shift
 LIBS=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do LIBS+=("$1"); shift; done
 [ "$1" == "--" ] && shift
+J=$(mktemp)
 for r in $(seq $REPS); do
   for l in "${LIBS[@]}"; do
-    CM3D_LIB=$l timeout -k 10 300 python3 bench.py --cpu-sample 0 --no-secondary --in-flight 1 --steps 200 "$@" > gpurun_out/sweep_lib.json 2> gpurun_out/sweep_err.log || { echo "$l failed"; tail -3 gpurun_out/sweep_err.log; continue; }
+    CM3D_LIB=$l timeout -k 10 300 python3 bench.py --full --cpu-sample 0 --no-secondary --in-flight 1 --steps 200 "$@" > $J 2> $J.err || { echo "$l failed"; tail -3 $J.err; continue; }
     python3 -c "
 import json
-d=json.load(open('gpurun_out/sweep_lib.json'))
+d=json.load(open('$J'))
 s=d['kernels']['stage_ms_one_batch_alone']
 print('$l', round(d['value']), 'frames/s  project alone', d['roofline']['avg_launch_ms_alone'], ' in region', d['roofline']['avg_launch_ms'], ' control: masks', s['masks'], 'medoid', s['medoid'])
 "

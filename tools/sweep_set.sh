@@ -3,7 +3,7 @@
 i=0
 for envs in "$@"; do
   i=$((i+1))
-  env $envs timeout -k 10 200 python bench.py --steps 20 --warmup 3 --cpu-sample 0 --no-secondary 2>/dev/null > /tmp/sweepset_$i.json
+  env $envs timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --cpu-sample 0 --no-secondary 2>/dev/null > /tmp/sweepset_$i.json
   python - "$envs" "$i" <<'PY'
 import json, sys
 d = json.load(open(f"/tmp/sweepset_{sys.argv[2]}.json"))
