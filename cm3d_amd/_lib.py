@@ -9,7 +9,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CM3D_LIB") or os.path.join(_HERE, "libcm3d_hip.so")      # CM3D_LIB: experiments only
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 CAM_STRIDE = 64
 SWEEP_XF_STRIDE = 24
 MAX_CAMS = 8
@@ -21,6 +21,7 @@ BBOX_STRIDE = 8          # int32 per mask in `bbox`: eroded bounds [0..3], store
 MAX_MATCH_BOXES = 1024
 MAX_FUSED_SWEEPS = 16
 MATCH_BOX_STRIDE = 6
+OBB_ROT_STRIDE = 9       # doubles per mask of cm3d_obb's rot_opt (row-major 3x3, ABI v5)
 RAW_QUADS = 3            # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -62,6 +63,9 @@ SIGNATURES = {
     "cm3d_centroid_transform": (_i32, [_p, _p, _p, _i32, _p, _p, _p]),
     "cm3d_bev_match_workspace_bytes": (_i64, [_i64]),
     "cm3d_bev_match": (_i32, [_p, _p, _i32, _p, _p, _i32, _p, _i32, _i64, C.c_double, _p, _p, _p, _p, _p, _i64, _p]),
+    "cm3d_obb_workspace_bytes": (_i64, [_i32, _i32]),
+    "cm3d_obb": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i64, _p]),
+    "cm3d_selftest_obb_yaw": (_i32, [_p, _i32, _p, _p]),
 }
 
 

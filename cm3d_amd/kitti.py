@@ -119,6 +119,42 @@ def obb_yaw(pts3d):
     return float(Rotation.from_matrix(Rm).as_euler("zyx")[0])
 
 
+def canonical_signs(v):
+    """Columns of `v` (unit eigenvectors) negated where needed so that each column's component of largest magnitude is positive (the
+    first such component on an exact tie): the sign rule of the device fit (cm3d_obb, include/cm3d_hip.h).  LAPACK's signs are an
+    implementation detail; this makes the result a function of the eigenspaces alone."""
+    v = np.array(v, np.float64)
+    k = np.argmax(np.abs(v), axis=0)
+    s = np.where(v[k, np.arange(v.shape[1])] < 0, -1.0, 1.0)
+    return v * s
+
+
+def obb_canonical(pts3d):
+    """obb_yaw with the canonical eigenvector signs (canonical_signs) applied right after the eigen-solve, before the first det fix:
+    the host restatement of what cm3d_obb computes.  Returns (yaw, Rm (3, 3), vertex_idx = ConvexHull(p).vertices); raises where
+    obb_yaw raises (no hull).  Its yaw is one of the values obb_yaw gives under some choice of eigenvector signs."""
+    from scipy.spatial import ConvexHull
+    from scipy.spatial.transform import Rotation
+    p = np.asarray(pts3d, np.float64)
+    vidx = ConvexHull(p).vertices
+    hull = p[vidx]
+    mean = hull.mean(0)
+    cov = (hull - mean).T @ (hull - mean) / hull.shape[0]
+    w, v = np.linalg.eigh(cov)
+    Rm = canonical_signs(v / np.linalg.norm(v, axis=0))[:, ::-1].copy()
+    if np.linalg.det(Rm) < 0:
+        Rm[:, 2] = -Rm[:, 2]
+    size = p.max(0) - p.min(0)
+    axis = [a for _, a in sorted(zip(size, "xyz"), key=lambda t: t[0])]
+    Rm = np.stack([Rm[:, axis.index("z")], Rm[:, axis.index("y")], Rm[:, axis.index("x")]], axis=1)
+    if np.linalg.det(Rm) < 0:
+        Rm[:, 0] = -Rm[:, 0]
+    return float(Rotation.from_matrix(Rm).as_euler("zyx")[0]), Rm, vidx
+
+
+OBB_FITTED, OBB_SKIPPED, OBB_NO_HULL, OBB_OVERFLOW = 0, 1, 2, 4      # cm3d_obb's status values (include/cm3d_hip.h)
+
+
 # src/kitti/2d_to_3d.py:105-116: what get_detection_name (:183-197) finally returns -- the KITTI class written to the label file
 KITTI_CLASS_MAPS = {"car": "Car", "pedestrian": "Pedestrian", "truck": "Truck", "bus": "Tram", "traffic_cone": "Misc",
                     "construction_vehicle": "Misc", "bicycle": "Cyclist", "motorcycle": "Cyclist", "trailer": "Misc", "barrier": "Misc"}
@@ -132,19 +168,34 @@ def label_line(object_type, wlh, xyz, yaw, conf=None, truncation=-1, occlusion=-
     return s + (f" {conf}\n" if conf is not None else "\n")
 
 
-def labels_of_frame(hb, res, f, classes, shape_priors):
-    """Label lines (pred with score, pseudo without) of frame f from the device results (:1479-1536)."""
+def labels_of_frame(hb, res, f, classes, shape_priors, obb="host"):
+    """Label lines (pred with score, pseudo without) of frame f from the device results (:1479-1536).
+    obb="host": the yaw is fitted here from the in-mask points (res["hit_xyz"], obb_yaw); obb="device": it is the device's
+    (res["obb_yaw"] / res["obb_status"] of a LiftEngine built with obb=True; no hit_xyz needed), status 2 (no hull) giving the
+    identity box's 0.0 like the host fallback; a mask the device could not fit (status 4) is fitted here from res["hit_xyz"], which
+    the caller then downloads (pipeline_kitti does)."""
+    if obb not in ("host", "device"):
+        raise ValueError(obb)
     from .lifting import get_detection_name
     pred, pseudo = [], []
     for m in range(hb.mask_off[f], hb.mask_off[f + 1]):
         o, e = res["hit_off"][m], res["hit_off"][m + 1]
         if e - o <= 3:                                   # :1479-1480
             continue
-        pts = res["hit_xyz"][o:e, :3]                    # the in-mask points (:1479), laid out like hit_idx
-        try:
-            yaw = obb_yaw(pts)
-        except Exception:                                # :1481-1484: bare except -> identity box
+        st = int(res["obb_status"][m]) if obb == "device" else None
+        if st == OBB_NO_HULL:                            # Qhull raised on the host: identity box (:1481-1484)
             yaw = 0.0
+        elif st == OBB_FITTED:
+            yaw = float(res["obb_yaw"][m])
+        elif st is not None and "hit_xyz" not in res:
+            raise RuntimeError(f"mask {m}: the device box fit gave status {st}; download the in-mask points (download(full=True)) "
+                               "to fit it on the host, or run with --obb host")
+        else:                                            # host mode, or a mask the device could not fit (status 4): the host fit
+            pts = res["hit_xyz"][o:e, :3]                # the in-mask points (:1479), laid out like hit_idx
+            try:
+                yaw = obb_yaw(pts)
+            except Exception:                            # :1481-1484: bare except -> identity box
+                yaw = 0.0
         label = hb.labels[f][m - hb.mask_off[f]]
         name = KITTI_CLASS_MAPS[get_detection_name(label)]       # :1523, :183-197: the label file carries the KITTI class
         # :1530 looks the prior up by the RAW label; for the three spellings get_detection_name renames (trafficcone,

@@ -352,10 +352,12 @@ class LiftEngine:
     All launches go to torch's current HIP stream and never synchronise."""
 
     def __init__(self, device="cuda:0", classes: Optional[ClassTable] = None, min_dist=MIN_DIST,
-                 hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None):
+                 hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
-        off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it."""
+        off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
+        obb: also fit KITTI's oriented box of every mask on the device (stage_obb, cm3d_obb: src/kitti/2d_to_3d.py:855-876, :1524);
+        download() then returns `obb_yaw` and `obb_status`.  Off: no OBB buffer, no OBB launch."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -366,6 +368,7 @@ class LiftEngine:
         self.hits_per_point = hits_per_point
         self.keep_colsum = keep_colsum
         self.keep_cloud = (os.environ.get("CM3D_KEEP_CLOUD", "0") == "1") if keep_cloud is None else bool(keep_cloud)
+        self.obb = bool(obb)
         _verify_matrix_pipe(self.lib, self.dev)
         self.b = None
         self._lane = None                                    # the lane tables on the device and their spatial index (upload)
@@ -448,6 +451,10 @@ class LiftEngine:
         # the RLE run ends stay alive across the whole pass, so they get their own buffer
         b.rle_ws_bytes = int(L.cm3d_rle_workspace_bytes(max(1, hb.rle_counts.size)))
         b.rle_ws = torch.empty(b.rle_ws_bytes, dtype=torch.uint8, device=d)
+        if self.obb:                  # the OBB fit keeps its own workspace: nothing it leaves there is read by another stage, nor the reverse
+            b.obb_yaw = e(M, dtype=torch.float64); b.obb_status = e(M)
+            b.obb_ws_bytes = int(L.cm3d_obb_workspace_bytes(M, b.idx_cap))
+            b.obb_ws = torch.empty(b.obb_ws_bytes, dtype=torch.uint8, device=d)
         b.n_tables, b.n_lane = len(hb.lane_off) - 1, int(hb.lane.shape[0])
         b.grid_bytes = int(L.cm3d_lane_grid_bytes(b.n_tables, b.n_lane))
         # The spatial index of the lane tables depends on the tables alone (the reference discretises a scene's lanes once,
@@ -638,6 +645,12 @@ class LiftEngine:
                                     _ptr(self.nms_thr), len(self.classes.names), _ptr(b.ego_xyz), _ptr(b.pose_inv), _ptr(b.box),
                                     _ptr(b.flags), st), "cm3d_box_nms")
 
+    def stage_obb(self, st):
+        """a18 (KITTI): yaw of the oriented box of every mask's in-mask points (cm3d_obb), on hit_xyz / hit_off of the compaction."""
+        b = self.b
+        check(self.lib.cm3d_obb(_ptr(b.hit_xyz), _ptr(b.hit_off), b.M, b.idx_cap, _ptr(b.obb_yaw), _ptr(b.obb_status), 0, 0,
+                                _ptr(b.obb_ws), b.obb_ws_bytes, st), "cm3d_obb")
+
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
     def run(self, masks="dense", project_events=None, stage_events=None):
@@ -673,6 +686,8 @@ class LiftEngine:
         mark()
         self.stage_boxes(st)
         mark()
+        if self.obb:
+            self.stage_obb(st)
         self._lane["passes_since_build"] = self._lane.get("passes_since_build", 0) + 1
 
     def capture_graph(self, masks="rle"):
@@ -740,9 +755,12 @@ class LiftEngine:
         b = self.b
         s = self.check_status()
         if not full:
-            return dict(hit_off=b.hit_off.cpu().numpy(), medoid_pos=b.medoid_pos.cpu().numpy(), centroid=b.centroid.cpu().numpy(),
-                        lane_idx=b.lane_idx.cpu().numpy(), lane_dist=b.lane_dist.cpu().numpy(),
-                        centroid_global=b.centroid_g.cpu().numpy(), box=b.box.cpu().numpy(), flags=b.flags.cpu().numpy())
+            out = dict(hit_off=b.hit_off.cpu().numpy(), medoid_pos=b.medoid_pos.cpu().numpy(), centroid=b.centroid.cpu().numpy(),
+                       lane_idx=b.lane_idx.cpu().numpy(), lane_dist=b.lane_dist.cpu().numpy(),
+                       centroid_global=b.centroid_g.cpu().numpy(), box=b.box.cpu().numpy(), flags=b.flags.cpu().numpy())
+            if self.obb:
+                out.update(obb_yaw=b.obb_yaw.cpu().numpy(), obb_status=b.obb_status.cpu().numpy())
+            return out
         n_rows, n_idx = int(s[1]), int(s[2])
         pt_off_rows = b.pt_off.cpu().numpy()
         keep = ~self.removed_rows()[:n_rows]
@@ -762,6 +780,8 @@ class LiftEngine:
             out["points"] = b.points[:n_rows].cpu().numpy()[keep]
         if b.colsum is not None:
             out["colsum"] = b.colsum[:n_idx].cpu().numpy()
+        if self.obb:
+            out.update(obb_yaw=b.obb_yaw.cpu().numpy(), obb_status=b.obb_status.cpu().numpy())
         return out
 
 

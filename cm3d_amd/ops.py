@@ -8,6 +8,7 @@ src/nuscenes/2d_to_3d.py so that parity tests read like calls into the reference
     circle_nms(dets, det_labels, threshs_by_label)       :309-332
     points_in_masks(points, cams, masks, cam_nums)       :553-620 for all masks of a frame
     erode(mask) / decode(rles)                           :526-527 / :425
+    obb_yaws(point_lists)                                src/kitti/2d_to_3d.py:855-876 + :1524 for several lists
 
 They are conveniences for tests and small jobs; the batched path is lifting.LiftEngine.
 """
@@ -192,6 +193,44 @@ def get_medoids(point_lists, via_rows=False, want_colsum=False):
         cs = colsum.cpu().numpy()
         return out, [cs[hit_off[k]:hit_off[k + 1]] for k in range(n)]
     return out
+
+
+# ----------------------------------------------------------------------------- a18 (KITTI)
+def obb_yaws(point_lists, vertices=False):
+    """Yaw of the oriented box of each list in ONE call of cm3d_obb (one "mask" per list; src/kitti/2d_to_3d.py:855-876, :1524 with
+    the canonical eigenvector signs of include/cm3d_hip.h -- host restatement kitti.obb_canonical).  point_lists: arrays (M_k, 3) of
+    float32 coordinates.  Returns (yaw (n,) float64, status (n,) int32, R (n, 3, 3) float64); status 0 fitted, 1 <= 3 points (yaw
+    NaN), 2 no hull (yaw 0, R identity), 4 not fitted (more than 512 facets seen in one step).  vertices=True adds the list of hull-vertex positions of each list."""
+    L = _lib.lib()
+    Ms = [int(np.asarray(p).shape[0]) for p in point_lists]
+    n, tot = len(Ms), int(sum(Ms))
+    P4 = np.zeros((max(tot, 1), 4), np.float32)
+    if tot:
+        P4[:tot, :3] = np.concatenate([np.asarray(p, np.float32).reshape(-1, 3) for p in point_lists], 0)
+    hit_off = np.concatenate([[0], np.cumsum(Ms)]).astype(np.int32)
+    idx_cap = max(tot, 1)
+    pts, d_off = _t(P4), _t(hit_off)
+    yaw, st = _e(n, dtype=torch.float64), _e(n)
+    rot = _e(n, _lib.OBB_ROT_STRIDE, dtype=torch.float64)
+    vm = _e(idx_cap, dtype=torch.uint8) if vertices else None
+    ws = _ws(L.cm3d_obb_workspace_bytes(n, idx_cap))
+    check(L.cm3d_obb(pts.data_ptr(), d_off.data_ptr(), n, idx_cap, yaw.data_ptr(), st.data_ptr(), rot.data_ptr(),
+                     vm.data_ptr() if vertices else 0, ws.data_ptr(), ws.numel(), _st()), "cm3d_obb")
+    out = (yaw.cpu().numpy(), st.cpu().numpy(), rot.cpu().numpy().reshape(n, 3, 3))
+    if vertices:
+        marks = vm.cpu().numpy()
+        out = out + ([np.flatnonzero(marks[hit_off[k]:hit_off[k + 1]]) for k in range(n)],)
+    return out
+
+
+def obb_selftest_yaw(R):
+    """The yaw step of cm3d_obb alone (cm3d_selftest_obb_yaw): as_euler('zyx')[0] of each 3x3 matrix of R (n, 3, 3)."""
+    L = _lib.lib()
+    R = np.ascontiguousarray(np.asarray(R, np.float64).reshape(-1, 9))
+    n = R.shape[0]
+    d_R, yaw = _t(R), _e(n, dtype=torch.float64)
+    check(L.cm3d_selftest_obb_yaw(d_R.data_ptr(), n, yaw.data_ptr(), _st()), "cm3d_selftest_obb_yaw")
+    return yaw.cpu().numpy()
 
 
 # ----------------------------------------------------------------------------- a10

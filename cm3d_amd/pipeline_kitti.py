@@ -25,6 +25,10 @@ def main(argv=None):
     ap.add_argument("--priors", default="cfg/shape_priors_chatgpt.json")
     ap.add_argument("--ratio", type=float, default=kt.RATIO)
     ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--obb", choices=("host", "device"), default="host",
+                    help="where the yaw of the oriented box is fitted (:855-876, :1524): host = scipy/numpy per mask on the downloaded "
+                         "in-mask points (the restatement the default output is pinned to); device = cm3d_obb in the pass, only the "
+                         "per-mask results come back (eigenvector signs canonical, see include/cm3d_hip.h)")
     args = ap.parse_args(argv)
     t0 = time.time()
     pri = json.load(open(args.priors)) if os.path.exists(args.priors) else dict(lifting.SHAPE_PRIORS_CHATGPT)
@@ -34,7 +38,8 @@ def main(argv=None):
     os.makedirs(pred_dir, exist_ok=True)
     os.makedirs(pseudo_dir, exist_ok=True)
     nums = sorted(int(os.path.basename(p).split("_")[0]) for p in glob.glob(os.path.join(args.mask_dir, "*_masks.pkl")))
-    eng = lifting.LiftEngine("cuda:0", classes=classes)
+    device_obb = args.obb == "device"
+    eng = lifting.LiftEngine("cuda:0", classes=classes, obb=device_obb)
     lane = [[0.0, 0.0, 0.0]]                   # stage 1 of KITTI uses no lanes; the engine still wants a table
     n_lines = 0
     for b0 in range(0, len(nums), args.batch):
@@ -59,9 +64,11 @@ def main(argv=None):
             eng.upload(hb)
             eng.run(masks="rle")
             torch.cuda.synchronize()
-            res = eng.download()
+            res = eng.download(full=not device_obb)          # device fit: no in-mask points to copy back
+            if device_obb and (res["obb_status"] == kt.OBB_OVERFLOW).any():
+                res = eng.download(full=True)                 # ... unless the device could not fit a mask: the host fits that one
             for i, f in enumerate(fs):
-                pred, pseudo = kt.labels_of_frame(hb, res, i, classes, pri)
+                pred, pseudo = kt.labels_of_frame(hb, res, i, classes, pri, obb=args.obb)
                 with open(os.path.join(pred_dir, f"{f.token}.txt"), "a") as fh:
                     fh.writelines(pred)
                 with open(os.path.join(pseudo_dir, f"{f.token}.txt"), "a") as fh:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define CM3D_ABI_VERSION 4
+#define CM3D_ABI_VERSION 5
 
 #define CM3D_OK 0
 #define CM3D_ERR_ARG (-1)      /* null pointer / non-positive size / unsupported shape */
@@ -47,6 +47,7 @@ extern "C" {
 #define CM3D_MEDOID_TILE 64      /* columns per medoid tile (one wave)                 */
 #define CM3D_MAX_MATCH_BOXES 1024 /* boxes per sample and side, see cm3d_bev_match    */
 #define CM3D_MATCH_BOX_STRIDE 6  /* doubles per box of cm3d_bev_match                  */
+#define CM3D_OBB_ROT_STRIDE 9    /* doubles per mask in cm3d_obb's rot_opt (row-major 3x3, ABI v5) */
 
 /* status word written by kernels (int32[4] in device memory, zero it per batch):
  *  [0] bit0: point capacity overflow (cm3d_sweep_prep), bit1: hit-index capacity
@@ -354,6 +355,44 @@ int cm3d_bev_match(const double *pred, const int32_t *pred_off, int32_t n_pred, 
                    const int32_t *gt_off, int32_t n_gt, const int64_t *pair_off, int32_t n_frames,
                    int64_t total_pairs, double iou_thr, int32_t *pred_match, int32_t *gt_match, double *match_iou,
                    int32_t *status, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
+
+/* ---- a18 (KITTI, ABI v5): yaw of the oriented bounding box of every mask ------------
+ * Replaces the per-mask Open3D box of src/kitti/2d_to_3d.py:855-876 (get_oriented_bounding_box: PCA of the convex-hull
+ * vertices) and the yaw taken from it at :1524 (Rotation.from_matrix(R).as_euler("zyx")[0]), host restatement
+ * cm3d_amd.kitti.obb_yaw.  One launch for all masks, one workgroup of one wave per mask, float64 throughout on coordinates shifted
+ * to the list's AABB centre:
+ *   1. hull vertices = the extreme points of the list (Qhull's ConvexHull(p).vertices: a point on a face or an edge that is no
+ *      corner is no vertex, a vertex listed several times counts once; outside tolerance 16 DBL_EPSILON x half the list's extent);
+ *      a flat, collinear or single-point list has no hull (Qhull raises; the reference falls back to the identity box, :1481-1484);
+ *   2. mean and population covariance of the vertices (a fixed summation order: the same bits on every run);
+ *   3. 3x3 eigen-solve (cyclic Jacobi), columns by descending eigenvalue.  The signs of the eigenvectors are an implementation
+ *      detail of LAPACK / Open3D; here each unit eigenvector is negated if needed so that its component of largest magnitude is
+ *      positive (the first one on an exact tie) -- cm3d_amd.kitti.obb_canonical restates this rule on the host.  det < 0: column 2
+ *      negated;
+ *   4./5. extents = max - min of all points; columns re-ordered as [rank z, rank y, rank x] of the stable ascending sort of the
+ *      extents; det < 0: column 0 negated;
+ *   6. yaw = scipy's as_euler('zyx')[0] of that matrix (quaternion method, gimbal-lock branch included).
+ *  hit_xyz   float[idx_cap][4]  the compaction's in-mask points (cm3d_compact_hits), mask m at [hit_off[m], hit_off[m+1])
+ *  hit_off   int32[n_masks+1]
+ *  yaw       double[n_masks] OUT   obb_status int32[n_masks] OUT:
+ *              0 fitted; 1 three points or fewer, skipped (:1479-1480), yaw NaN; 2 no hull (flat / collinear / one distinct
+ *              point), yaw 0.0 and rot = identity; 4 the construction could not go on (more than 512 facets seen from one
+ *              point, or a numerically degenerate new facet), yaw NaN -- nothing is written out of range.  The workspace holds every
+ *              hull a list can have: no list fails for lack of room
+ *  rot_opt   double[n_masks][9] OUT, optional (NULL): the final row-major matrix (NaN for status 1 and 4)
+ *  vertex_opt uint8[idx_cap] OUT, optional (NULL): laid out like hit_xyz, 1 at the list positions of the hull vertices (the first
+ *              position of a repeated vertex that the construction reached), else 0
+ *  workspace: cm3d_obb_workspace_bytes(n_masks, idx_cap) = 8 idx_cap + 48 (3 idx_cap + 64 n_masks) bytes, 8-byte aligned: 8 bytes per
+ *             list position (live points) and, for the hulls too large for LDS, a region of 3 n + 64 facets per list of n points at
+ *             facet 3 hit_off[m] + 64 m (room for any hull of the list; placed by the offsets, so results never depend on the order
+ *             in which masks run).  hit_off must be non-decreasing, as cm3d_compact_hits writes it */
+int64_t cm3d_obb_workspace_bytes(int32_t n_masks, int32_t idx_cap);
+int cm3d_obb(const float *hit_xyz, const int32_t *hit_off, int32_t n_masks, int32_t idx_cap, double *yaw, int32_t *obb_status,
+             double *rot_opt, uint8_t *vertex_opt, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
+
+/* Diagnostic for the tests: the yaw step of cm3d_obb alone -- as_euler('zyx')[0] of n row-major 3x3 rotation matrices R
+ * (double[n][9]) into yaw (double[n]). */
+int cm3d_selftest_obb_yaw(const double *R, int32_t n, double *yaw, cm3d_stream_t stream);
 
 #ifdef __cplusplus
 }
