@@ -22,6 +22,9 @@ MAX_MATCH_BOXES = 1024
 MAX_FUSED_SWEEPS = 16
 MATCH_BOX_STRIDE = 6
 OBB_ROT_STRIDE = 9       # doubles per mask of cm3d_obb's rot_opt (row-major 3x3, ABI v5)
+WM_BOX_STRIDE = 8        # doubles per box of cm3d_waymo_metrics
+WM_BREAKDOWNS = 16
+WM_CUTOFFS = 101
 RAW_QUADS = 3            # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -66,6 +69,8 @@ SIGNATURES = {
     "cm3d_obb_workspace_bytes": (_i64, [_i32, _i32]),
     "cm3d_obb": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i64, _p]),
     "cm3d_selftest_obb_yaw": (_i32, [_p, _i32, _p, _p]),
+    "cm3d_waymo_metrics_workspace_bytes": (_i64, [_i64]),
+    "cm3d_waymo_metrics": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _i64, _p]),
 }
 
 

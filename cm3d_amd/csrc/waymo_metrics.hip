@@ -1,0 +1,340 @@
+// Waymo 3D detection metrics (the counting part of waymo-open-dataset's compute_detection_metrics_main; host side and
+// the rules: cm3d_amd/waymo_eval.py).
+//
+// Input: "groups" = (frame, type, shard) with their predictions (descending score) and ground truth.  Per group and per
+// score cutoff c (101 of them, float32(c * 0.01)) the predictions with score >= cutoff are matched one to one with the
+// group's ground truth: maximum-weight assignment on weight = int(3D IoU x 1e6), pairs below the type's IoU threshold
+// never match.  Counted per (breakdown, cutoff): TP, FP, FN at LEVEL_1, FN at LEVEL_2 and the heading-accuracy sum of
+// the matches (int64, 2^-32 units), all with integer atomics: the result does not depend on the order in which waves run.
+//
+// Two launches:
+//   k_wm_weights   one thread per (prediction, ground truth) pair of a group: float64 polygon clipping x z overlap
+//   k_wm_match<C>  one wave per group of at most 64 C columns (C = 1, 2, 4, 16): the Hungarian method with potentials,
+//                  columns in registers (lane (j - 1) % 64, slot (j - 1) / 64) as in fusion.hip's k_bev_assign_small.  Rows
+//                  are predictions in score order, columns the ground truth padded with empty columns to max(P, G).
+//                  The method adds one row per phase and the assignment after phase k is optimal for the first k rows,
+//                  so ONE solve gives the matching of every cutoff: the counts are taken after the phases that end a
+//                  cutoff's prediction subset (at most P + 1 distinct subsets).  per_cutoff != 0 solves every cutoff
+//                  afresh instead (a check of that deduplication).
+#include "bev_iou.h"
+
+#define WM_KMAX 1000000
+#define WM_BREAKDOWNS 16
+#define WM_CUTOFFS 101
+#define WM_LDS 4096                 // weights of a group up to this many pairs sit in LDS, larger ones are read from L2
+
+static __device__ __forceinline__ float wm_cutoff(int c) { return (float)(c * 0.01); }
+
+static __device__ __forceinline__ double wm_thr(int bd) { return bd < 4 ? 0.7 : 0.5; }     // vehicle 0.7, the other types 0.5
+
+// Box record (CM3D_WM_BOX_STRIDE doubles): cx, cy, length, width, cos(heading), sin(heading), cz, height.
+static __device__ double wm_iou3d(const double *__restrict__ a, const double *__restrict__ b)
+{
+    const double va = a[2] * a[3] * a[7], vb = b[2] * b[3] * b[7];
+    if (!(a[2] * a[3] > 0.0) || !(b[2] * b[3] > 0.0) || !(a[7] > 0.0) || !(b[7] > 0.0)) return 0.0;
+    double inter = bev_inter_area(a, b);
+    const double zlo = fmax(a[6] - 0.5 * a[7], b[6] - 0.5 * b[7]);
+    const double zhi = fmin(a[6] + 0.5 * a[7], b[6] + 0.5 * b[7]);
+    inter = inter * fmax(zhi - zlo, 0.0);
+    const double uni = (va + vb) - inter;
+    if (!(uni > 0.0)) return 0.0;
+    const double iou = inter / uni;
+    return iou > 1.0 ? 1.0 : iou;
+}
+
+// heading accuracy of a match in 2^-32 units: 1 - |d| / pi, d = float32 heading difference wrapped to [-pi, pi]
+static __device__ long long wm_heading_fx(float pd, float gt)
+{
+    const double pi = 3.141592653589793, two_pi = 6.283185307179586;
+    const float d32 = gt - pd;
+    double t = fmod((double)d32 + pi, two_pi);
+    if (t < 0.0) t += two_pi;
+    double d = (double)(float)fabs(t - pi);
+    if (d > pi) d = (double)(float)(two_pi - d);
+    double acc = 1.0 - d / pi;
+    acc = acc < 0.0 ? 0.0 : (acc > 1.0 ? 1.0 : acc);
+    return llrint((double)(float)acc * 4294967296.0);
+}
+
+__global__ __launch_bounds__(256) void k_wm_zero(long long *__restrict__ counts, long long *__restrict__ heading)
+{
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t < WM_BREAKDOWNS * WM_CUTOFFS * 4) counts[t] = 0;
+    if (t < WM_BREAKDOWNS * WM_CUTOFFS) heading[t] = 0;
+}
+
+// first group of every 256-pair block of k_wm_weights
+__global__ __launch_bounds__(256) void k_wm_block_groups(const int64_t *__restrict__ pair_off, int n_groups, int64_t n_blocks,
+                                                         int32_t *__restrict__ blk_group)
+{
+    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= n_blocks) return;
+    const int64_t t = b * 256;
+    int lo = 0, hi = n_groups;              // last g with pair_off[g] <= t
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (pair_off[mid] <= t) lo = mid; else hi = mid;
+    }
+    blk_group[b] = lo;
+}
+
+__global__ __launch_bounds__(256) void k_wm_weights(const double *__restrict__ pred, const int32_t *__restrict__ pred_off,
+                                                    const double *__restrict__ gt, const int32_t *__restrict__ gt_off,
+                                                    const int32_t *__restrict__ group_bd, const int64_t *__restrict__ pair_off,
+                                                    const int32_t *__restrict__ blk_group, int n_groups, int64_t total_pairs,
+                                                    int32_t *__restrict__ weight)
+{
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= total_pairs) return;
+    int g = blk_group[blockIdx.x];
+    while (g + 1 < n_groups && pair_off[g + 1] <= t) ++g;
+    const int G = gt_off[g + 1] - gt_off[g];
+    const int64_t r = t - pair_off[g];
+    const int p = (int)(r / G), j = (int)(r - (int64_t)p * G);
+    const double iou = wm_iou3d(pred + (int64_t)(pred_off[g] + p) * CM3D_WM_BOX_STRIDE, gt + (int64_t)(gt_off[g] + j) * CM3D_WM_BOX_STRIDE);
+    weight[t] = iou >= wm_thr(group_bd[g]) ? (int)(iou * (double)WM_KMAX) : 0;
+}
+
+static __device__ __forceinline__ long long wm_wave_min(long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long w = __shfl_xor(v, o, 64);
+        v = w < v ? w : v;
+    }
+    return v;
+}
+
+static __device__ __forceinline__ long long wm_wave_sum(long long v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <int CPL, typename T>
+static __device__ __forceinline__ T wm_get(const T (&a)[CPL], int idx)        // a[] of element idx (uniform idx)
+{
+    T r = a[0];
+    r = __shfl(r, idx & 63, 64);
+#pragma unroll
+    for (int k = 1; k < CPL; ++k) {
+        const T t = __shfl(a[k], idx & 63, 64);
+        r = (idx >> 6) == k ? t : r;
+    }
+    return r;
+}
+
+template <int CPL>
+struct WmSolver {                                // potentials stay within n x WM_KMAX <= 1024 x 10^6 < 2^31
+    int u[CPL], v[CPL];
+    int p[CPL], way[CPL];
+};
+
+template <int CPL>
+__global__ __launch_bounds__(64) void k_wm_match(const float *__restrict__ pred_head, const float *__restrict__ pred_score,
+                                                 const int32_t *__restrict__ pred_off, const float *__restrict__ gt_head,
+                                                 const int32_t *__restrict__ gt_level, const int32_t *__restrict__ gt_off,
+                                                 const int32_t *__restrict__ group_bd, const int64_t *__restrict__ pair_off,
+                                                 const int32_t *__restrict__ weight, int per_cutoff,
+                                                 unsigned long long *__restrict__ counts, unsigned long long *__restrict__ heading,
+                                                 int32_t *__restrict__ status)
+{
+    __shared__ int s_w[WM_LDS];
+    const int g = blockIdx.x, lane = threadIdx.x;
+    const int p0 = pred_off[g], g0 = gt_off[g];
+    const int P = pred_off[g + 1] - p0, G = gt_off[g + 1] - g0;
+    const int bd = group_bd[g];
+    const int big = P > G ? P : G;
+    if (CPL == 1) {                              // capacity and type checks, once per group
+        if (bd < 0 || bd >= WM_BREAKDOWNS) { if (lane == 0) atomicOr(status, 2); return; }
+        if (big > CM3D_MAX_MATCH_BOXES) { if (lane == 0) atomicOr(status, 1); return; }
+    }
+    if (bd < 0 || bd >= WM_BREAKDOWNS || big > 64 * CPL) return;
+    if (CPL > 1 && big <= 64 * (CPL == 2 ? 1 : CPL == 4 ? 2 : 4)) return;        // another instance's group
+    if (CPL == 1 && big == 0) return;
+    const int32_t *__restrict__ Wm = weight + pair_off[g];
+    const bool in_lds = P * G <= WM_LDS;
+    if (in_lds) {
+        for (int q = lane; q < P * G; q += 64) s_w[q] = Wm[q];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    auto wgt = [&](int i, int j) -> int {        // row i (prediction), column j (ground truth or empty), 1-based
+        if (j > G) return 0;
+        return in_lds ? s_w[(i - 1) * G + (j - 1)] : Wm[(int64_t)(i - 1) * G + (j - 1)];
+    };
+    // prediction subset size of this lane's cutoffs (lane, lane + 64): predictions with score >= cutoff
+    int kc[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int c = lane + 64 * s;
+        const float cut = wm_cutoff(c < WM_CUTOFFS ? c : 0);
+        int lo = 0, hi = P;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (pred_score[p0 + mid] >= cut) lo = mid + 1; else hi = mid;
+        }
+        kc[s] = c < WM_CUTOFFS ? lo : -1;
+    }
+    int n_l1 = 0;
+    for (int j = lane; j < G; j += 64) n_l1 += gt_level[g0 + j] == 1;
+    n_l1 = (int)wm_wave_sum(n_l1);
+    long long r_tp[2] = {0, 0}, r_fn1[2] = {n_l1, n_l1}, r_fn2[2] = {G, G}, r_h[2] = {0, 0};      // the empty subset's counts
+
+    WmSolver<CPL> S;
+    // counts of the current assignment, taken by the lanes whose cutoff subset has `rows` predictions
+    // TP, FN at LEVEL_1 and the heading sum of the current assignment (pairs of zero weight are no match)
+    auto count = [&](long long &tp, long long &fn1, long long &h) {
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) {
+            const int col = k * 64 + lane + 1;
+            if (col <= G) {
+                const int i = S.p[k];
+                const bool matched = i != 0 && wgt(i, col) > 0;
+                tp += matched;
+                if (!matched && gt_level[g0 + col - 1] == 1) ++fn1;
+                if (matched) h += wm_heading_fx(pred_head[p0 + i - 1], gt_head[g0 + col - 1]);
+            }
+        }
+        tp = wm_wave_sum(tp);
+        fn1 = wm_wave_sum(fn1);
+        h = wm_wave_sum(h);
+    };
+    auto record = [&](int rows) {
+        long long tp = 0, fn1 = 0, h = 0;
+        count(tp, fn1, h);
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+            if (kc[s] == rows) { r_tp[s] = tp; r_fn1[s] = fn1; r_fn2[s] = G - tp; r_h[s] = h; }
+    };
+    // Hungarian method over rows 1..n, columns 1..m; after row i: record(i) when some lane's cutoff ends there
+    auto solve = [&](int n, int m, bool every_boundary) {
+#pragma unroll
+        for (int k = 0; k < CPL; ++k) { S.u[k] = 0; S.v[k] = 0; S.p[k] = 0; S.way[k] = 0; }
+        for (int i = 1; i <= n; ++i) {
+            long long minv[CPL];
+            bool used[CPL], row_in_tree[CPL];
+#pragma unroll
+            for (int k = 0; k < CPL; ++k) { minv[k] = 1ll << 50; used[k] = false; row_in_tree[k] = false; }
+            int j0 = 0;
+            while (true) {
+                const int i0 = j0 == 0 ? i : wm_get<CPL, int>(S.p, j0 - 1);
+                const long long ui0 = wm_get<CPL, int>(S.u, i0 - 1);
+                long long key = (1ll << 62);
+#pragma unroll
+                for (int k = 0; k < CPL; ++k) {
+                    const int col = k * 64 + lane + 1;
+                    if (col == j0) used[k] = true;
+                    if (col == i0) row_in_tree[k] = true;
+                    if (col <= m && !used[k]) {
+                        const long long cur = (long long)(WM_KMAX - wgt(i0, col)) - ui0 - S.v[k];
+                        if (cur < minv[k]) { minv[k] = cur; S.way[k] = j0; }
+                        const long long kk = minv[k] * 4096 + (S.p[k] != 0 ? 2048 : 0) + col;     // an unassigned column first
+                        key = kk < key ? kk : key;
+                    }
+                }
+                key = wm_wave_min(key);
+                const long long delta = key >> 12;
+                const int j1 = __builtin_amdgcn_readfirstlane((int)(key & 2047));
+#pragma unroll
+                for (int k = 0; k < CPL; ++k) {
+                    if (row_in_tree[k]) S.u[k] += (int)delta;
+                    if (used[k]) S.v[k] -= (int)delta; else minv[k] -= delta;
+                }
+                j0 = j1;
+                if (wm_get<CPL, int>(S.p, j0 - 1) == 0) break;
+            }
+            do {                                 // augment along the predecessor chain
+                const int j1 = wm_get<CPL, int>(S.way, j0 - 1);
+                const int pr = j1 == 0 ? i : wm_get<CPL, int>(S.p, (j1 == 0 ? 1 : j1) - 1);
+#pragma unroll
+                for (int k = 0; k < CPL; ++k)
+                    if (k * 64 + lane + 1 == j0) S.p[k] = pr;
+                j0 = j1;
+            } while (j0);
+            if (every_boundary) {
+                const bool here = kc[0] == i || kc[1] == i;
+                if (__builtin_amdgcn_ballot_w64(here) != 0ull) record(i);
+            }
+        }
+    };
+    if (!per_cutoff) {
+        if (P > 0 && G > 0) solve(P, big, true);
+    } else {
+        // every cutoff on its own: a fresh solve over its subset, columns padded to max(k, G)
+        for (int c = 0; c < WM_CUTOFFS; ++c) {
+            const int k = __shfl(c < 64 ? kc[0] : kc[1], c & 63, 64);
+            if (k > 0 && G > 0) {
+                solve(k, k > G ? k : G, false);
+                long long tp = 0, fn1 = 0, h = 0;
+                count(tp, fn1, h);
+                if (lane == (c & 63) && c < 64) { r_tp[0] = tp; r_fn1[0] = fn1; r_fn2[0] = G - tp; r_h[0] = h; }
+                if (lane == (c & 63) && c >= 64) { r_tp[1] = tp; r_fn1[1] = fn1; r_fn2[1] = G - tp; r_h[1] = h; }
+            }
+        }
+    }
+    // this group's contribution to its breakdown: one lane per cutoff, zero terms skipped
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int c = lane + 64 * s;
+        if (c >= WM_CUTOFFS) continue;
+        unsigned long long *dst = counts + ((int64_t)bd * WM_CUTOFFS + c) * 4;
+        const long long fp = (long long)kc[s] - r_tp[s];
+        if (r_tp[s]) atomicAdd(dst + 0, (unsigned long long)r_tp[s]);
+        if (fp) atomicAdd(dst + 1, (unsigned long long)fp);
+        if (r_fn1[s]) atomicAdd(dst + 2, (unsigned long long)r_fn1[s]);
+        if (r_fn2[s]) atomicAdd(dst + 3, (unsigned long long)r_fn2[s]);
+        if (r_h[s]) atomicAdd(heading + (int64_t)bd * WM_CUTOFFS + c, (unsigned long long)r_h[s]);
+    }
+}
+
+extern "C" int64_t cm3d_waymo_metrics_workspace_bytes(int64_t total_pairs)
+{
+    const int64_t n = total_pairs > 0 ? total_pairs : 1;
+    return (n + (n + 255) / 256) * (int64_t)sizeof(int32_t);           // weights + the first group of every 256-pair block
+}
+
+extern "C" int cm3d_waymo_metrics(const double *pred_box, const float *pred_heading, const float *pred_score,
+                                  const int32_t *pred_off, const double *gt_box, const float *gt_heading, const int32_t *gt_level,
+                                  const int32_t *gt_off, const int32_t *group_bd, const int64_t *pair_off, int32_t n_groups,
+                                  int64_t total_pairs, int32_t per_cutoff, int64_t *counts, int64_t *heading_sum, int32_t *status,
+                                  void *workspace, int64_t workspace_bytes, cm3d_stream_t stream)
+{
+    if (!pred_off || !gt_off || !group_bd || !pair_off || !counts || !heading_sum || !status || n_groups < 0 || total_pairs < 0)
+        return CM3D_ERR_ARG;
+    if (total_pairs >= ((int64_t)1 << 31) * 256) return CM3D_ERR_ARG;
+    if (total_pairs > 0 && (!pred_box || !gt_box || !workspace || workspace_bytes < cm3d_waymo_metrics_workspace_bytes(total_pairs)))
+        return total_pairs > 0 && (!pred_box || !gt_box) ? CM3D_ERR_ARG : CM3D_ERR_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_wm_zero, dim3((WM_BREAKDOWNS * WM_CUTOFFS * 4 + 255) / 256), dim3(256), 0, st, (long long *)counts,
+                       (long long *)heading_sum);
+    CM3D_CHECK_LAUNCH();
+    if (n_groups == 0) return CM3D_OK;
+    int32_t *weight = (int32_t *)workspace;
+    if (total_pairs > 0) {
+        int32_t *blk_group = weight + total_pairs;
+        const int64_t n_blocks = (total_pairs + 255) / 256;
+        hipLaunchKernelGGL(k_wm_block_groups, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, st, pair_off, n_groups, n_blocks,
+                           blk_group);
+        CM3D_CHECK_LAUNCH();
+        hipLaunchKernelGGL(k_wm_weights, dim3((unsigned)n_blocks), dim3(256), 0, st, pred_box, pred_off, gt_box, gt_off, group_bd,
+                           pair_off, blk_group, n_groups, total_pairs, weight);
+        CM3D_CHECK_LAUNCH();
+    }
+    unsigned long long *c = (unsigned long long *)counts, *h = (unsigned long long *)heading_sum;
+    hipLaunchKernelGGL(k_wm_match<1>, dim3(n_groups), dim3(64), 0, st, pred_heading, pred_score, pred_off, gt_heading, gt_level, gt_off,
+                       group_bd, pair_off, weight, per_cutoff, c, h, status);
+    CM3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_wm_match<2>, dim3(n_groups), dim3(64), 0, st, pred_heading, pred_score, pred_off, gt_heading, gt_level, gt_off,
+                       group_bd, pair_off, weight, per_cutoff, c, h, status);
+    CM3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_wm_match<4>, dim3(n_groups), dim3(64), 0, st, pred_heading, pred_score, pred_off, gt_heading, gt_level, gt_off,
+                       group_bd, pair_off, weight, per_cutoff, c, h, status);
+    CM3D_CHECK_LAUNCH();
+    hipLaunchKernelGGL(k_wm_match<16>, dim3(n_groups), dim3(64), 0, st, pred_heading, pred_score, pred_off, gt_heading, gt_level, gt_off,
+                       group_bd, pair_off, weight, per_cutoff, c, h, status);
+    CM3D_CHECK_LAUNCH();
+    return CM3D_OK;
+}

@@ -354,3 +354,38 @@ def bev_match(pred_boxes, gt_boxes, iou=0.2):
         ids = np.flatnonzero(m >= 0)
         out.append((ids.astype(np.int64), m[ids].astype(np.int64), miou[p_off[f]:p_off[f + 1]][ids]))
     return out
+
+
+def waymo_metrics(packed, per_cutoff=False):
+    """Counts of the Waymo detection metrics for a packed file pair (waymo_eval.pack) in ONE cm3d_waymo_metrics call.
+    Returns (counts int64[16][101][4]: TP, FP, FN L1, FN L2; heading_sum int64[16][101] in 2^-32 units)."""
+    L = _lib.lib()
+    po, go = np.asarray(packed["pred_off"], np.int64), np.asarray(packed["gt_off"], np.int64)
+    n_groups = int(po.size - 1)
+    pair_off = np.concatenate([[0], np.cumsum(np.diff(po) * np.diff(go))]).astype(np.int64)
+    total = int(pair_off[-1])
+    counts = _e(_lib.WM_BREAKDOWNS, _lib.WM_CUTOFFS, 4, dtype=torch.int64)
+    hsum = _e(_lib.WM_BREAKDOWNS, _lib.WM_CUTOFFS, dtype=torch.int64)
+    status = torch.zeros(1, dtype=torch.int32, device=_dev())
+    if n_groups == 0:
+        return np.zeros((_lib.WM_BREAKDOWNS, _lib.WM_CUTOFFS, 4), np.int64), np.zeros((_lib.WM_BREAKDOWNS, _lib.WM_CUTOFFS), np.int64)
+
+    def dev(a, dtype):
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape[0] == 0:
+            a = np.zeros((1,) + a.shape[1:], dtype)
+        return _t(a)
+    d_pb, d_ph, d_ps = dev(packed["pred_box"], np.float64), dev(packed["pred_head"], np.float32), dev(packed["pred_score"], np.float32)
+    d_gb, d_gh, d_gl = dev(packed["gt_box"], np.float64), dev(packed["gt_head"], np.float32), dev(packed["gt_level"], np.int32)
+    d_po, d_go = _t(po.astype(np.int32)), _t(go.astype(np.int32))
+    d_bd, d_pair = _t(np.asarray(packed["group_bd"], np.int32)), _t(pair_off)
+    ws = _ws(L.cm3d_waymo_metrics_workspace_bytes(total))
+    check(L.cm3d_waymo_metrics(d_pb.data_ptr(), d_ph.data_ptr(), d_ps.data_ptr(), d_po.data_ptr(), d_gb.data_ptr(), d_gh.data_ptr(),
+                               d_gl.data_ptr(), d_go.data_ptr(), d_bd.data_ptr(), d_pair.data_ptr(), n_groups, total, int(bool(per_cutoff)),
+                               counts.data_ptr(), hsum.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+          "cm3d_waymo_metrics")
+    st = int(status.item())
+    if st:
+        raise _lib.Cm3dError(f"cm3d_waymo_metrics: status {st} (bit0: more than {_lib.MAX_MATCH_BOXES} boxes of one type in a "
+                             "frame, bit1: unknown breakdown)")
+    return counts.cpu().numpy(), hsum.cpu().numpy()

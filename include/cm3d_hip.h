@@ -48,6 +48,9 @@ extern "C" {
 #define CM3D_MAX_MATCH_BOXES 1024 /* boxes per sample and side, see cm3d_bev_match    */
 #define CM3D_MATCH_BOX_STRIDE 6  /* doubles per box of cm3d_bev_match                  */
 #define CM3D_OBB_ROT_STRIDE 9    /* doubles per mask in cm3d_obb's rot_opt (row-major 3x3, ABI v5) */
+#define CM3D_WM_BOX_STRIDE 8     /* doubles per box of cm3d_waymo_metrics                */
+#define CM3D_WM_BREAKDOWNS 16    /* breakdowns of cm3d_waymo_metrics: (type - 1) * 4 + shard */
+#define CM3D_WM_CUTOFFS 101      /* score cutoffs of cm3d_waymo_metrics: float32(c * 0.01) */
 
 /* status word written by kernels (int32[4] in device memory, zero it per batch):
  *  [0] bit0: point capacity overflow (cm3d_sweep_prep), bit1: hit-index capacity
@@ -393,6 +396,32 @@ int cm3d_obb(const float *hit_xyz, const int32_t *hit_off, int32_t n_masks, int3
 /* Diagnostic for the tests: the yaw step of cm3d_obb alone -- as_euler('zyx')[0] of n row-major 3x3 rotation matrices R
  * (double[n][9]) into yaw (double[n]). */
 int cm3d_selftest_obb_yaw(const double *R, int32_t n, double *yaw, cm3d_stream_t stream);
+
+/* ---- Waymo 3D detection metrics: the counting of waymo-open-dataset's compute_detection_metrics_main --------
+ * The host side (cm3d_amd/waymo_eval.py) groups the boxes of a file pair and turns the counts into mAP / mAPH.
+ * A group is (frame, type 1..4, shard): shard 0 holds every box of the type, shards 1..3 the boxes whose centre lies
+ * [0, 30), [30, 50), [50, +inf) m from the origin; its breakdown is group_bd = (type - 1) * 4 + shard.  Group g owns
+ * predictions [pred_off[g], pred_off[g+1]) in descending score order and ground truth [gt_off[g], gt_off[g+1]).
+ * Per group and cutoff c (float32(c * 0.01), c = 0..100) the predictions with score >= cutoff are matched one to one
+ * with the group's ground truth: maximum-weight assignment on int(3D IoU x 1e6), pairs below the IoU threshold of the
+ * type (vehicle 0.7, else 0.5) never match.  One solve per group serves every cutoff (rows are added in score order);
+ * per_cutoff != 0 solves each cutoff on its own instead (same counts; for tests).
+ *  pred_box, gt_box double[n][CM3D_WM_BOX_STRIDE]  cx, cy, length, width, cos(heading), sin(heading), cz, height
+ *  pred_heading, gt_heading float[n]  heading (float32) for the heading accuracy 1 - |d| / pi, d wrapped to [-pi, pi]
+ *  pred_score float[n_pred]; gt_level int32[n_gt] 1 or 2
+ *  pair_off int64[n_groups+1]  prefix sums of P_g * G_g; total_pairs = pair_off[n_groups]
+ *  counts int64[CM3D_WM_BREAKDOWNS][CM3D_WM_CUTOFFS][4] OUT: TP, FP, FN at LEVEL_1, FN at LEVEL_2 (written whole: the call
+ *        zeroes them first); a prediction matched to LEVEL_2 ground truth is a TP at LEVEL_1 too
+ *  heading_sum int64[CM3D_WM_BREAKDOWNS][CM3D_WM_CUTOFFS] OUT: heading accuracy of the TPs, in 2^-32 units
+ *  status int32[1] (zero it before the call): bit0 a group with more than CM3D_MAX_MATCH_BOXES boxes on a side, bit1 a
+ *        group_bd outside [0, CM3D_WM_BREAKDOWNS) -- such a group is skipped, nothing is written out of range
+ *  workspace: cm3d_waymo_metrics_workspace_bytes(total_pairs).  Integer atomics only: every run gives the same bits. */
+int64_t cm3d_waymo_metrics_workspace_bytes(int64_t total_pairs);
+int cm3d_waymo_metrics(const double *pred_box, const float *pred_heading, const float *pred_score, const int32_t *pred_off,
+                       const double *gt_box, const float *gt_heading, const int32_t *gt_level, const int32_t *gt_off,
+                       const int32_t *group_bd, const int64_t *pair_off, int32_t n_groups, int64_t total_pairs,
+                       int32_t per_cutoff, int64_t *counts, int64_t *heading_sum, int32_t *status, void *workspace,
+                       int64_t workspace_bytes, cm3d_stream_t stream);
 
 #ifdef __cplusplus
 }
