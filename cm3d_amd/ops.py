@@ -320,14 +320,20 @@ def bev_match(pred_boxes, gt_boxes, iou=0.2):
     """`match(pred_boxes, sam3d_boxes, iou, Type.TYPE_2D)` (linear_matching.py:53-104) for a list of samples in one
     GPU call.  pred_boxes / gt_boxes: lists (one entry per sample) of (n,7) arrays.  Returns one
     (prediction_ids, groundtruth_ids, ious) triple per sample, matches in ascending prediction order."""
+    return bev_match_records([match_records(b) for b in pred_boxes], [match_records(b) for b in gt_boxes], iou)
+
+
+def bev_match_records(pr, gr, iou=0.2):
+    """bev_match on float64 records as cm3d_bev_match takes them: lists (one entry per sample) of (n,6) arrays
+    cx, cy, length, width, cos(heading), sin(heading), passed on unrounded."""
     L = _lib.lib()
-    F = len(pred_boxes)
+    F = len(pr)
     if F == 0:
         return []
-    if len(gt_boxes) != F:
+    if len(gr) != F:
         raise ValueError("bev_match: one gt entry per sample")
-    pr = [match_records(b) for b in pred_boxes]
-    gr = [match_records(b) for b in gt_boxes]
+    pr = [np.asarray(r, np.float64).reshape(-1, 6) for r in pr]
+    gr = [np.asarray(r, np.float64).reshape(-1, 6) for r in gr]
     np_, ng = np.array([r.shape[0] for r in pr], np.int64), np.array([r.shape[0] for r in gr], np.int64)
     if max(np_.max(), ng.max()) > _lib.MAX_MATCH_BOXES:
         raise _lib.Cm3dError(f"bev_match: more than {_lib.MAX_MATCH_BOXES} boxes in a sample")

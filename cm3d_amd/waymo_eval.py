@@ -224,7 +224,7 @@ def _clip_area(a, b):
         return X, Y
     px, py = corners(a, a[:, 0], a[:, 1])
     bx, by = corners(b, a[:, 0], a[:, 1])
-    W = 12
+    W = 20          # clip buffer slots: one clip of an n-gon emits at most floor(1.5 n) vertices, 4 -> 6 -> 9 -> 13 -> 19
     PX, PY = np.zeros((m, W)), np.zeros((m, W))
     PX[:, :4], PY[:, :4] = px, py
     cnt = np.full(m, 4)
@@ -236,7 +236,7 @@ def _clip_area(a, b):
         k = np.zeros(m, np.int64)
         prx, pry = PX[rows, np.maximum(cnt - 1, 0)], PY[rows, np.maximum(cnt - 1, 0)]
         dp = ex * (pry - y1) - ey * (prx - x1)
-        for i in range(W - 4):
+        for i in range(int(cnt.max())):                # every input vertex
             act = i < cnt
             cx, cy = PX[:, i], PY[:, i]
             dc = ex * (cy - y1) - ey * (cx - x1)

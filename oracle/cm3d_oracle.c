@@ -510,7 +510,9 @@ ORC_API double orc_bev_iou(const double *a, const double *b)
         const double r = 0.5 * (sqrt(ra2) + sqrt(rb2));
         if (dx * dx + dy * dy > r * r) return 0.0;
     }
-    double px[12], py[12], qx[12], qy[12], bx[4], by[4];
+    /* 20 slots: one clip of an n-gon emits at most floor(1.5 n) vertices whatever the rounded signs (one per point
+     * inside, one per sign change), 4 -> 6 -> 9 -> 13 -> 19; exact clipping would stop at 8 (see bev_iou.h). */
+    double px[20], py[20], qx[20], qy[20], bx[4], by[4];
     orc_bev_corners(a, a[0], a[1], px, py);
     orc_bev_corners(b, a[0], a[1], bx, by);
     int n = 4;
