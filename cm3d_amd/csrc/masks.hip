@@ -512,43 +512,13 @@ static __device__ __forceinline__ void rw_one_runs(int run, const int (&v)[RW_PE
     }
 }
 
-#ifdef CM3D_DIAG
-// Diagnostic build only (tools/rw_diag.py): s_memtime at the start and the end of every mask's wave, its placement and its run count
-#define RW_DIAG_WAVES 32768
-__device__ int g_rw_diag;
-__device__ unsigned long long g_rw_wave[4 * RW_DIAG_WAVES];
-static __device__ __forceinline__ unsigned long long rw_now()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-extern "C" int cm3d_rw_diag_set(int flags)
-{
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_rw_diag), &flags, sizeof(int)) != hipSuccess) return CM3D_ERR_LAUNCH;
-    void *wv = nullptr;
-    if (hipGetSymbolAddress(&wv, HIP_SYMBOL(g_rw_wave)) != hipSuccess || hipMemset(wv, 0, sizeof(g_rw_wave)) != hipSuccess) return CM3D_ERR_LAUNCH;
-    return hipDeviceSynchronize() == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
-}
-extern "C" int cm3d_rw_diag_read_waves(unsigned long long *out_host, int n_waves)
-{
-    if (n_waves > RW_DIAG_WAVES) return CM3D_ERR_ARG;
-    return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_rw_wave), 4 * (size_t)n_waves * sizeof(unsigned long long)) == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
-}
-#endif
-
 struct RwBegin { int32_t *status; int32_t *hit_count; uint32_t *removed_bits; long long removed_words; int n_masks; };
 
 __global__ __launch_bounds__(RW_THREADS, 5) void k_rle_erode_pack_wave(const uint32_t *__restrict__ cnts_all, const int32_t *__restrict__ rle_off,
                                                                         int n_masks, int W, int H, int Wp, int lds_words,
-                                                                        uint32_t *__restrict__ packed, int32_t *__restrict__ bbox, int max_bands, int diag,
+                                                                        uint32_t *__restrict__ packed, int32_t *__restrict__ bbox, int max_bands,
                                                                         const RwBegin begin)
 {
-#ifndef CM3D_DIAG
-    diag = 0;                                                   // (the ablation switches exist in the diagnostic build only: each was a loop-invariant mask in scalar registers)
-#endif
     // cm3d_rle_erode_pack_begin: the per-pass reset (cm3d_batch_begin's: status word, hit counts, removed-row bits) rides on this launch -- the
     // first of a pass -- instead of a launch of its own.  Nothing in this kernel reads or writes those arrays; whatever does runs behind it.
     if (begin.status) {
@@ -560,15 +530,11 @@ __global__ __launch_bounds__(RW_THREADS, 5) void k_rle_erode_pack_wave(const uin
     extern __shared__ __align__(16) uint32_t s_all[];
     __shared__ int s_part[RW_WAVES][4];                         // the bands' shares of the bounding box
     const int lane = cm3d_lane(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    // max_bands > 1: one workgroup per mask, wave w its band w; 1: one wave per mask, and a wave goes on to mask + (waves of the
-    // launch) when the grid is smaller than the number of masks (the launcher holds it to a few waves per SIMD: see there)
+    // max_bands > 1: one workgroup per mask, wave w its band w; 1: one wave per mask.  The launch's grid covers the masks in both forms,
+    // so the loop below runs once: its stride is kept only so that the kernel's code stays what it was when a smaller grid could be forced.
     const int m_first = max_bands > 1 ? (int)blockIdx.x : (int)blockIdx.x * RW_WAVES + wave;
     const int m_stride = max_bands > 1 ? (int)gridDim.x : (int)gridDim.x * RW_WAVES;
     for (int m = m_first; m < n_masks; m += m_stride) {         // (max_bands > 1: the grid covers the masks, one round, uniform over the workgroup)
-#ifdef CM3D_DIAG
-    const int wdiag = g_rw_diag;
-    const unsigned long long t_start = wdiag ? rw_now() : 0ull;
-#endif
     const int band = max_bands > 1 ? wave : 0;
     uint32_t *s_rows = s_all + (size_t)wave * lds_words;
     const int o = rle_off[m], n = rle_off[m + 1] - o;
@@ -610,7 +576,7 @@ __global__ __launch_bounds__(RW_THREADS, 5) void k_rle_erode_pack_wave(const uin
         ylo = __builtin_amdgcn_readfirstlane(cm3d_wave_min(ylo)); xlo = __builtin_amdgcn_readfirstlane(cm3d_wave_min(xlo));
         yhi = __builtin_amdgcn_readfirstlane(cm3d_wave_max(yhi)); xhi = __builtin_amdgcn_readfirstlane(cm3d_wave_max(xhi));
     }
-    if (!(yhi < 0 || (diag & 8))) {             // (an empty mask: nothing to paint, the box stays empty)
+    if (!(yhi < 0)) {                        // (an empty mask: nothing to paint, the box stays empty)
     const int my0 = ylo, my1 = min(yhi, H - 1);                        // rows of the mask's set pixels; this wave's band of them:
     const int bandr = (my1 - my0 + nb) / nb;
     const int ry0 = my0 + band * bandr, ry1 = min(my1, ry0 + bandr - 1);
@@ -649,7 +615,7 @@ __global__ __launch_bounds__(RW_THREADS, 5) void k_rle_erode_pack_wave(const uin
         {
             int carry = 0;
 #pragma unroll 1
-            for (int base = 0; base < ((diag & 4) ? 0 : n); base += RW_CHUNK) {
+            for (int base = 0; base < n; base += RW_CHUNK) {
                 int s1[RW_PER / 2], l1[RW_PER / 2];
                 if (base == 0) {                                    // uniform
 #pragma unroll
@@ -690,7 +656,7 @@ __global__ __launch_bounds__(RW_THREADS, 5) void k_rle_erode_pack_wave(const uin
         rw_lds_sync();
         // erosion, sliding window down a word column: h(r) = centre & left & right of LDS row r; out(r) = h(r-1) & h(r) & h(r+1)
         const int rps = (rows + nseg - 1) / nseg;           // output rows per band
-        for (int cb = 0; cb < ((diag & 2) ? 0 : wc); cb += 64) {
+        for (int cb = 0; cb < wc; cb += 64) {
             const int seg = wc >= 64 ? 0 : lane / wc, c = wc >= 64 ? cb + lane : lane - seg * wc;
             const int r0 = seg * rps, r1 = min(rows, r0 + rps);                  // output rows [r0, r1) of the tile (LDS rows r0+1 .. r1)
             if (c < wc && seg < nseg && r0 < r1) {
@@ -706,7 +672,7 @@ __global__ __launch_bounds__(RW_THREADS, 5) void k_rle_erode_pack_wave(const uin
                 // the eroded words go out as PACKED ROWS OF THE RECTANGLE of the mask's set pixels (word columns xw0 .. xw0 + wc - 1, rows
                 // my0 .. my1), one row behind the other: consecutive stores fill whole cache lines.  At the image's row stride a mask's
                 // 40-byte row pieces were 1.5 M partial-line writes per batch, and with three batches in flight they cost every kernel
-                // that streams from HBM beside them: 20 of 142 us per pass (tools/stage_ablate.py), 4 in this form.
+                // that streams from HBM beside them: 20 of 142 us per pass, 4 in this form.
                 uint32_t *dst = out_mask + (size_t)(ya + 1 + r0 - my0) * wc + (xw - xw0);
                 uint32_t colany = 0u;
                 int first = 0x7FFFFFFF, last = -1;
@@ -714,7 +680,7 @@ __global__ __launch_bounds__(RW_THREADS, 5) void k_rle_erode_pack_wave(const uin
                     const uint32_t h2 = hrow(row);
                     const uint32_t e = h0 & h1 & h2 & keep;
                     h0 = h1; h1 = h2;
-                    if (!(diag & 1)) *dst = e;
+                    *dst = e;
                     colany |= e;
                     if (e) { first = min(first, r); last = r; }
                 }
@@ -730,13 +696,6 @@ __global__ __launch_bounds__(RW_THREADS, 5) void k_rle_erode_pack_wave(const uin
     }
     }
     bminx = cm3d_wave_min(bminx); bminy = cm3d_wave_min(bminy); bmaxx = cm3d_wave_max(bmaxx); bmaxy = cm3d_wave_max(bmaxy);
-#ifdef CM3D_DIAG
-    if (wdiag && lane == 0 && band == 0 && m < RW_DIAG_WAVES) {
-        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        g_rw_wave[4 * m] = t_start; g_rw_wave[4 * m + 1] = rw_now();
-        g_rw_wave[4 * m + 2] = ((unsigned long long)xcc << 32) | hw; g_rw_wave[4 * m + 3] = (unsigned long long)n;
-    }
-#endif
     if (nb == 1) {                              // uniform over the workgroup (or max_bands == 1): one band, no hand-over
         if (band == 0 && lane < 8)
             bbox[CM3D_BBOX_STRIDE * m + lane] = lane == 0 ? bminx : lane == 1 ? bminy : lane == 2 ? bmaxx : lane == 3 ? bmaxy
@@ -796,19 +755,18 @@ static int rle_erode_pack_impl(const uint32_t *rle_counts, const int32_t *rle_of
     if (workspace_bytes < cm3d_rle_workspace_bytes(total_runs)) return CM3D_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int Wp = (W + 31) / 32;
-    static int lds_words = 0;
-    if (!lds_words) { const char *e = getenv("CM3D_RLE_LDS_WORDS"); lds_words = e ? atoi(e) : RLE_LDS_WORDS; }
+    const int lds_words = RLE_LDS_WORDS;
     if (lds_words / (Wp + 2) - 2 < 1) return CM3D_ERR_ARG;      // tile height of a full-width mask
     (void)workspace;                                            // reserved (the run ends are not materialised)
     // ordinary masks (on average at most 1024 runs): one wave per mask; lists of thousands of runs: one workgroup per mask
     static int form = -1, lds_wave = 0, bands = 1;
     if (form < 0) {
-        const char *bd = getenv("CM3D_RLE_BANDS");                // 1: a wave per mask; 2..4: a workgroup per mask, its rows in up to that many bands
+        const char *bd = getenv("CM3D_RLE_BANDS");                // test hook (the product runs 1): 1 a wave per mask; 2..4 a workgroup per mask, its rows in up to that many bands
         bands = bd ? atoi(bd) : 1;
         if (bands < 1 || bands > RW_WAVES) bands = 1;
-        const char *e = getenv("CM3D_RLE_FORM");                  // "wave" / "block" force one form (experiments, tests)
+        const char *e = getenv("CM3D_RLE_FORM");                  // test hook: "wave" / "block" force the form the run counts choose below
         form = e ? (e[0] == 'w' ? 1 : 2) : 0;
-        const char *w = getenv("CM3D_RLEW_LDS_WORDS");
+        const char *w = getenv("CM3D_RLEW_LDS_WORDS");            // test hook: a small slice per wave makes masks of test size span several tiles
         lds_wave = w ? atoi(w) : RW_LDS_WORDS;
         if (lds_wave < 3 * (EP_MAX_WP + 2)) lds_wave = 3 * (EP_MAX_WP + 2);
         lds_wave = (lds_wave + 3) & ~3;
@@ -821,14 +779,9 @@ static int rle_erode_pack_impl(const uint32_t *rle_counts, const int32_t *rle_of
             if (hipFuncSetAttribute((const void *)k_rle_erode_pack_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return CM3D_ERR_LAUNCH;
             lds_allowed = lds;
         }
-        const char *dg = getenv("CM3D_RLE_DIAG");                     // experiments only (read per call: tools/stage_ablate.py switches it
-        const int rle_diag = dg ? atoi(dg) : 0;                       // between passes): 1 no stores, 2 no erosion, 4 no paint, 8 stop behind pass 1
-        int grid = bands > 1 ? n_masks : (n_masks + RW_WAVES - 1) / RW_WAVES;
-        static int gcap = -1;
-        if (gcap < 0) { const char *e = getenv("CM3D_RLE_GRID"); gcap = e ? atoi(e) : 0; }
-        if (bands == 1 && gcap > 0 && grid > gcap) grid = gcap;
+        const int grid = bands > 1 ? n_masks : (n_masks + RW_WAVES - 1) / RW_WAVES;
         hipLaunchKernelGGL(k_rle_erode_pack_wave, dim3(grid), dim3(RW_THREADS), lds, st,
-                           rle_counts, rle_off, n_masks, W, H, Wp, lds_wave, packed, bbox, bands, rle_diag, begin);
+                           rle_counts, rle_off, n_masks, W, H, Wp, lds_wave, packed, bbox, bands, begin);
     } else {
         if (begin.status) {                 // (the workgroup-per-mask form does not carry the reset: a launch of its own, as cm3d_batch_begin makes it)
             const int rc = cm3d_batch_begin(begin.status, begin.hit_count, begin.n_masks, begin.removed_bits, begin.removed_words, stream);

@@ -122,40 +122,6 @@ static __device__ __forceinline__ bool md_sqrt_okz(float x) { return x == 0.0f |
 
 struct TileBest { float s; int j; };
 
-#ifdef CM3D_DIAG
-// Diagnostic build only (make diag; tools/md_diag.py): s_memtime of every tile's wave at its start, after its first staged
-// chunk and at its end, its placement (XCC_ID << 32 | HW_ID) and its list length.
-#define MD_DIAG_WAVES 65536
-__device__ int g_md_diag;
-__device__ unsigned long long g_md_wave[5 * MD_DIAG_WAVES];
-__device__ unsigned long long g_md_clock[4];          // s_memtime and the 100 MHz s_memrealtime at the first wave's start and the last wave's end
-static __device__ __forceinline__ unsigned long long md_now()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-extern "C" int cm3d_md_diag_set(int flags)
-{
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_md_diag), &flags, sizeof(int)) != hipSuccess) return CM3D_ERR_LAUNCH;
-    unsigned long long z[4] = {~0ull, ~0ull, 0ull, 0ull};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_md_clock), z, sizeof(z)) != hipSuccess) return CM3D_ERR_LAUNCH;
-    void *wv = nullptr;
-    if (hipGetSymbolAddress(&wv, HIP_SYMBOL(g_md_wave)) != hipSuccess || hipMemset(wv, 0, sizeof(g_md_wave)) != hipSuccess) return CM3D_ERR_LAUNCH;
-    return hipDeviceSynchronize() == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
-}
-extern "C" int cm3d_md_diag_read_clock(unsigned long long *out_host)
-{
-    return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_md_clock), 4 * sizeof(unsigned long long)) == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
-}
-extern "C" int cm3d_md_diag_read_waves(unsigned long long *out_host, int n_waves)
-{
-    if (n_waves > MD_DIAG_WAVES) return CM3D_ERR_ARG;
-    return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_md_wave), 5 * (size_t)n_waves * sizeof(unsigned long long)) == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
-}
-#endif
 __global__ __launch_bounds__(1024) void k_medoid_desc(int n_masks, const int32_t *__restrict__ hit_off,
                                                       const int32_t *__restrict__ tile_off, int idx_cap, int tile_cap,
                                                       TileDesc *__restrict__ desc)
@@ -231,9 +197,6 @@ static __device__ __forceinline__ float md_rows(const float4 *s4, int cnt, float
 #endif
     constexpr int U = MD_U;                   // pairs per step
     int ii = 0;
-#ifdef CM3D_DIAG
-    const int ab = __builtin_amdgcn_readfirstlane(g_md_diag);      // ablations (results wrong by construction): 2 no root, 4 no domain test, 8 no LDS reads, 16 one add per step
-#endif
     for (; ii + 2 * U <= cnt; ii += 2 * U) {
         f2 d[U];
         if (DIRECT) {
@@ -245,12 +208,6 @@ static __device__ __forceinline__ float md_rows(const float4 *s4, int cnt, float
             float4 A[U], B[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) { A[u] = s4[ii + 2 * u]; B[u] = s4[ii + 2 * u + 1]; }
-#ifdef CM3D_DIAG
-            if (ab & 8) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) { A[u] = make_float4(qx + u, qy, qz, qn + ii); B[u] = make_float4(qy, qz + u, qx, qn + 3.0f); }
-            }
-#endif
 #pragma unroll
             for (int u = 0; u < U; ++u) d[u] = (f2){A[u].x, A[u].y} * qx;                       // (-2 x_i) * x_j
 #pragma unroll
@@ -282,16 +239,6 @@ static __device__ __forceinline__ float md_rows(const float4 *s4, int cnt, float
 #pragma unroll
         for (int u = 1; u < U; ++u) { lo2 = __builtin_elementwise_min(lo2, d[u]); hi2 = __builtin_elementwise_max(hi2, d[u]); }
         const float lo = fminf(lo2.x, lo2.y), hi = fmaxf(hi2.x, hi2.y);
-#ifdef CM3D_DIAG
-        if (!APPROX && (ab & 6)) {
-            if (!(ab & 2)) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) d[u] = md_sqrt_core2(d[u]);
-            } else if (!(ab & 4)) {
-                s += (lo >= 1.0e-30f && hi < 1.0e30f) ? 0.0f : 1.0f;
-            }
-        } else
-#endif
         if (APPROX) {
 #pragma unroll
             for (int u = 0; u < U; ++u) d[u] = (f2){md_asqrt(d[u].x), md_asqrt(d[u].y)};
@@ -312,15 +259,6 @@ static __device__ __forceinline__ float md_rows(const float4 *s4, int cnt, float
                 for (int u = 0; u < U; ++u) d[u] = (f2){sqrtf(d[u].x), sqrtf(d[u].y)};
             }
         }
-#ifdef CM3D_DIAG
-        if (ab & 16) {
-            f2 a2 = d[0];
-#pragma unroll
-            for (int u = 1; u < U; ++u) a2 = a2 + d[u];
-            s = s + (a2.x + a2.y);
-            continue;
-        }
-#endif
 #pragma unroll
         for (int u = 0; u < U; ++u) { s = s + d[u].x; s = s + d[u].y; }
     }
@@ -433,13 +371,7 @@ static __device__ __forceinline__ void md_approx_tile(Fetch fetch, float *s_rows
     const float bx = qx * MDA_S, by = qy * MDA_S, bz = qz * MDA_S, bn = qn * MDA_S2;
     f2 s = {0.f, 0.f};                                        // in units of s: columns lane % 32 and 32 + lane % 32, this half's rows
     bool scaled = false;                                      // (uniform) the staged rows are in the scaled form
-#ifdef CM3D_DIAG
-    const int ab = __builtin_amdgcn_readfirstlane(g_md_diag);  // ablation (results wrong by construction; tools/md_long_ablate.py): 128 rows staged once per tile
-#endif
     for (int i0 = 0; i0 < M; i0 += MDA_STAGE) {
-#ifdef CM3D_DIAG
-        if (!((ab & 128) && i0 > 0)) {
-#endif
         __builtin_amdgcn_wave_barrier();                      // the previous rows' readers are done
         float4 rr[MDA_STAGE / 64];
         bool rows_ok = true;
@@ -465,9 +397,6 @@ static __device__ __forceinline__ void md_approx_tile(Fetch fetch, float *s_rows
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#ifdef CM3D_DIAG
-        }
-#endif
         const int cnt = min(MDA_STAGE, M - i0), full = cnt & ~31;
         const float a5 = full + (lane & 31) < cnt ? 1.0f : 0.0f;            // the last, partial step's rows
         if (scaled) {
@@ -517,12 +446,6 @@ __global__ __launch_bounds__(MD_THREADS, 4) void k_medoid_tiles(const float4 *__
         if (feedback) feedback[0] = md_batch_long(desc, min(tile_off[n_masks], tile_cap)) ? 1 : 0;
     }
     const int wave = threadIdx.x >> 6, lane = cm3d_lane();
-#ifdef CM3D_DIAG
-    const int diag = g_md_diag & 1;
-    const unsigned long long t_start = diag ? md_now() : 0ull;
-    unsigned long long t_staged = 0ull;
-    const unsigned long long w_start = diag ? wall_clock64() : 0ull;
-#endif
     float4 *s_row = s_row_all[wave];
     const int ntiles = min(tile_off[n_masks], tile_cap);
     if (ntiles <= 0) return;
@@ -557,25 +480,8 @@ __global__ __launch_bounds__(MD_THREADS, 4) void k_medoid_tiles(const float4 *__
         const bool col_scal = !__ballot(act && !mda_point_ok(qx, qy, qz, qn));           // the column side of the scaled form (md_rows<.., SCALED>)
         const bool direct = M <= 25;
         const bool approx = WITH_LONG && md_two_pass(M);                  // long list (of a batch with the first pass: this instantiation): approximate sums, k_medoid_long later
-#ifdef CM3D_DIAG
-        if (WITH_LONG && ((g_md_diag & 512) ? !approx : ((g_md_diag & 1024) ? approx : false))) continue;      // 512: first-pass tiles only, 1024: exact tiles only
-#endif
-#ifdef CM3D_DIAG
-        const unsigned long long t_tile = diag ? md_now() : 0ull;           // (per tile; t_start is the wave's)
-        auto stamp = [&](unsigned long long staged) {
-            if (diag && lane == 0 && t < MD_DIAG_WAVES) {
-                const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-                g_md_wave[5 * t] = t_tile; g_md_wave[5 * t + 1] = staged; g_md_wave[5 * t + 2] = md_now();
-                g_md_wave[5 * t + 3] = ((unsigned long long)xcc << 32) | hw; g_md_wave[5 * t + 4] = (unsigned long long)M;
-                if (t == 0) { g_md_clock[0] = t_start; g_md_clock[1] = w_start; g_md_clock[2] = md_now(); g_md_clock[3] = wall_clock64(); }       // same wave, same XCD as the start stamps
-            }
-        };
-#endif
         if (WITH_LONG && approx && MD_APPROX_MFMA) {
             md_approx_tile(fetch, reinterpret_cast<float *>(s_row), off, M, jt, approx_opt);
-#ifdef CM3D_DIAG
-            stamp(t_tile);
-#endif
             continue;
         }
         // Rows are staged MD_STAGE (256) at a time: all their index loads, then all their point gathers are in
@@ -622,9 +528,6 @@ __global__ __launch_bounds__(MD_THREADS, 4) void k_medoid_tiles(const float4 *__
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#ifdef CM3D_DIAG
-            if (diag && i0 == 0) t_staged = md_now();
-#endif
             const bool safe = col_safe && !__ballot(!rows_safe);
             if (scaled)         // s goes in and comes out in its own units: the powers of two are exact both ways
                 s = md_rows<false, false, true, true>(s_row, cnt, qx * MDA_S, qy * MDA_S, qz * MDA_S, qn * MDA_S2, s * MDA_S) * 65536.0f;
@@ -652,9 +555,6 @@ __global__ __launch_bounds__(MD_THREADS, 4) void k_medoid_tiles(const float4 *__
             bs = red.s; bj = red.j;
         }
         if (lane == 0) { tile_best[d.t].s = bs; tile_best[d.t].j = bj; }
-#ifdef CM3D_DIAG
-        stamp(t_staged);
-#endif
     }
 }
 
@@ -768,9 +668,6 @@ __global__ __launch_bounds__(64 * MDL_WAVES, 3) void k_medoid_long(const float4 
     // a wave takes entries blockIdx.x + wave * gridDim.x, + gridDim.x * MDL_WAVES, ... of the list of long masks (k_medoid_reduce): a short list
     // goes to the first waves of many workgroups, i.e. to many CUs
     const int n_long = min(long_list[0], n_masks);
-#ifdef CM3D_DIAG
-    if (g_md_diag & 256) return;                                           // ablation: no second pass
-#endif
     auto wave_sync = [] {                                                  // this wave's LDS writes before its reads (and reads before the next writes)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -931,9 +828,6 @@ __global__ __launch_bounds__(64 * MDL_WAVES, 3) void k_medoid_long(const float4 
         }
         if (lane == 0) {
             int bj = best_j == 0x7FFFFFFF ? -1 : best_j;
-#ifdef CM3D_DIAG
-            if (g_md_diag & 2048) bj = C;                                  // diagnostic: the number of candidates in place of the position
-#endif
             medoid_pos[m] = bj;
             float cx = 0.f, cy = 0.f, cz = 0.f;
             if (bj >= 0) {
@@ -983,12 +877,10 @@ extern "C" int cm3d_medoid2(const float *points, const int32_t *pt_off, const in
     const int tile_cap = (int)(tile_cap64 > 0x7FFFFFFF ? 0x7FFFFFFF : tile_cap64);
     TileDesc *own = (TileDesc *)workspace;
     TileBest *best = (TileBest *)(own + tile_cap);
-    // two passes for long lists unless the caller wants every exact column sum (colsum_opt) or CM3D_MD_TWO_PASS=0
-    static int two_pass_env = -1;
-    if (two_pass_env < 0) { const char *e = getenv("CM3D_MD_TWO_PASS"); two_pass_env = e ? atoi(e) : 1; }
+    // two passes for long lists unless the caller wants every exact column sum (colsum_opt)
     // (flags & 1: the caller expects no long list in this batch -- the one-pass route is exact for every length, so a wrong
     // expectation costs time, never a result -- and two launches that would find nothing to do are not made)
-    float *approx = (two_pass_env && !colsum_opt && !(flags & 1)) ? (float *)(best + tile_cap) : nullptr;
+    float *approx = (!colsum_opt && !(flags & 1)) ? (float *)(best + tile_cap) : nullptr;
     int32_t *long_list = (int32_t *)((float *)(best + tile_cap) + idx_cap);         // [0] = number of long masks, then their numbers
     const TileDesc *desc = (const TileDesc *)tile_work;
     if (!desc) {                                   // no work list from cm3d_compact_hits: build it here
@@ -1002,8 +894,7 @@ extern "C" int cm3d_medoid2(const float *points, const int32_t *pt_off, const in
     // workgroups the hardware hands out as others finish (C5: 2048 workgroups +2 %, 1024 +7 % on the stage).  Half a workgroup
     // per mask lies between the two.
     int grid = (tile_cap + MD_WAVES - 1) / MD_WAVES;
-    int gmax = n_masks / 2 < 1024 ? 1024 : (n_masks / 2 > 4096 ? 4096 : n_masks / 2);
-    if (const char *e = getenv("CM3D_MD_GRID")) gmax = atoi(e);
+    const int gmax = n_masks / 2 < 1024 ? 1024 : (n_masks / 2 > 4096 ? 4096 : n_masks / 2);
     if (grid > gmax) grid = gmax;
     // (hit_row == NULL, the product's call: `points` holds the listed points themselves, cm3d_compact_hits' hit_xyz)
     auto tiles_light = hit_row ? k_medoid_tiles<false, true> : k_medoid_tiles<false, false>;
@@ -1012,7 +903,7 @@ extern "C" int cm3d_medoid2(const float *points, const int32_t *pt_off, const in
     hipLaunchKernelGGL(tiles_light, dim3(grid), dim3(MD_THREADS), 0, st, (const float4 *)points, pt_off, mask_frame, n_masks,
                        tile_off, hit_row, desc, best, tile_cap, colsum_opt, approx, long_list, feedback);
     CM3D_CHECK_LAUNCH();
-    if (approx) {             // (without a first pass -- colsum_opt, CM3D_MD_TWO_PASS=0 -- the light instantiation takes every batch)
+    if (approx) {             // (without a first pass -- colsum_opt, flags & 1 -- the light instantiation takes every batch)
         hipLaunchKernelGGL(tiles_heavy, dim3(grid), dim3(MD_THREADS), 0, st, (const float4 *)points, pt_off, mask_frame, n_masks,
                            tile_off, hit_row, desc, best, tile_cap, colsum_opt, approx, long_list, feedback);
         CM3D_CHECK_LAUNCH();

@@ -26,72 +26,12 @@
 #include <cstdlib>
 #include <type_traits>
 
-#ifdef CM3D_DIAG
-// Diagnostic build only (make diag -> libcm3d_hip_diag.so; tools/ph_diag.py): ablation switches and per-phase
-// s_memtime sums of k_project_hits.  Nothing of this exists in the product library.
-__device__ int g_ph_diag;                         // bit1 no mask loop, bit2 no camera loop, bit3 synthetic rows, bit4 stamps
-__device__ unsigned long long g_ph_stamp[8];
-#define PH_DIAG_WAVES 16384
-__device__ unsigned long long g_ph_wave[3 * PH_DIAG_WAVES];      // bit7: s_memtime at the start and the end of every wave, XCC_ID << 32 | HW_ID
-__device__ unsigned long long g_ph_count[8];     // bit6: wave-chunks, (chunk, camera) pairs behind the wedge / pre-test / projection, mask batches, masks
-static __device__ __forceinline__ unsigned long long ph_now()
-{
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define PH_DIAG(bit) (diag & (bit))
-#define PH_COUNT(k, v) do { if (diag & 64) cntk[k] += (v); } while (0)
-#define PH_STAMP(k)                                                     \
-    do {                                                                \
-        if (diag & 16) { const unsigned long long t_ = ph_now(); acc[k] += t_ - t_prev; t_prev = t_; } \
-    } while (0)
-extern "C" int cm3d_diag_set(int flags)
-{
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_ph_diag), &flags, sizeof(int)) != hipSuccess) return CM3D_ERR_LAUNCH;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_ph_stamp), z, sizeof(z)) != hipSuccess) return CM3D_ERR_LAUNCH;
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_ph_count), z, sizeof(z)) != hipSuccess) return CM3D_ERR_LAUNCH;
-    void *wv = nullptr;
-    if (hipGetSymbolAddress(&wv, HIP_SYMBOL(g_ph_wave)) != hipSuccess || hipMemset(wv, 0, sizeof(g_ph_wave)) != hipSuccess) return CM3D_ERR_LAUNCH;
-    if (hipDeviceSynchronize() != hipSuccess) return CM3D_ERR_LAUNCH;
-    return CM3D_OK;
-}
-extern "C" int cm3d_diag_read_waves(unsigned long long *out_host, int n_waves)
-{
-    if (n_waves > PH_DIAG_WAVES) return CM3D_ERR_ARG;
-    return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_ph_wave), 3 * (size_t)n_waves * sizeof(unsigned long long)) == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
-}
-extern "C" int cm3d_diag_read_counts(unsigned long long *out_host)
-{
-    return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_ph_count), 8 * sizeof(unsigned long long)) == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
-}
-extern "C" int cm3d_diag_read(unsigned long long *out_host)
-{
-    return hipMemcpyFromSymbol(out_host, HIP_SYMBOL(g_ph_stamp), 8 * sizeof(unsigned long long)) == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
-}
-// k_project_q: stages of the chunk loop that run (project_q.h); CM3D_PQ_STAGE sets the start value (PMC passes per stage)
-int g_pq_stage = getenv("CM3D_PQ_STAGE") ? atoi(getenv("CM3D_PQ_STAGE")) : 99;
-extern "C" int cm3d_diag_pq_stage(int stage) { g_pq_stage = stage; return CM3D_OK; }
-#else
-#define PH_DIAG(bit) 0
-#define PH_STAMP(k) do { } while (0)
-#define PH_COUNT(k, v) do { } while (0)
-#endif
-
-#ifndef PH_LOADMODE
-#define PH_LOADMODE 1          // how a full chunk's rows are fetched: 0 lane-strided non-temporal, 1 lane-strided (plain: measured faster)
-#endif
 #define PH_THREADS 256                            // k_compact_hits
 #ifndef PHK_THREADS
 #define PHK_THREADS 256                           // k_project_hits (its waves are independent: any multiple of 64)
 #endif
 #define PHK_WAVES (PHK_THREADS / 64)
 #define PH_WAVES (PH_THREADS / 64)
-#define PH_OVERSUB_NUM 1                          // waves launched : waves resident (k_project_hits header)
-#define PH_OVERSUB_DEN 1
 #ifndef PH_STEAL_LISTS
 #define PH_STEAL_LISTS 6                          // chunk lists of other slots a wave tries after its own (k_project_hits header)
 #endif
@@ -540,19 +480,9 @@ struct PhRows { static constexpr int S = KEEP ? 4 : 3; float v[4 * S]; };
 
 template <int STRIDE, bool KEEP>
 static __device__ __forceinline__ void ph_load_rows(PhRows<KEEP> &r, const float *__restrict__ src, const float *__restrict__ aux, int stride,
-                                                    size_t row0, int nvalid, int lane, int diag = 0)
+                                                    size_t row0, int nvalid, int lane)
 {
     constexpr int S = PhRows<KEEP>::S;
-    if (PH_DIAG(8)) {
-#pragma unroll
-        for (int j = 0; j < PH_PT; ++j) {
-            const int i = (int)row0 + 4 * lane + j;
-            r.v[j * S] = (float)(i & 1023) * 0.05f - 20.f; r.v[j * S + 1] = (float)((i >> 10) & 63) * 0.5f - 8.f;
-            r.v[j * S + 2] = -1.f;
-            if (KEEP) r.v[j * S + 3] = 0.f;
-        }
-        return;
-    }
     if (STRIDE == CM3D_RAW_QUADS) {
         // quad layout (cm3d_hip.h): rows 4q..4q+3 of the batch are 12 floats x0..3 y0..3 z0..3 -- the lane's four rows are one
         // 48-byte piece, three 16-byte loads; 12 bytes per row cross HBM and nothing else.  The fourth column, when the cloud
@@ -654,13 +584,6 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
     int n_frames, int tpf, int32_t *__restrict__ queue, int32_t *__restrict__ wc_info, int32_t *__restrict__ grp, int zstride,
     int32_t *__restrict__ frame_hits)
 {
-#ifdef CM3D_DIAG
-    const int diag = g_ph_diag;
-    unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_prev = 0;
-    int cntk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (diag & 16) t_prev = ph_now();
-    const unsigned long long t_start = (diag & 128) ? ph_now() : 0ull;
-#endif
     const int lane = cm3d_lane(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int planes_cap = (nm_cap + 31) >> 5;
     // per-wave copies of the frame's tables (nothing here is shared between waves, so nothing needs a workgroup barrier)
@@ -685,14 +608,8 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
     // the chunk lists of the frame: taken[s] = entries of list s handed out so far (zeroed by k_frame_tables)
     int32_t *const taken = queue + (size_t)f * tpf;
     int list = slot, lists_left = PH_STEAL_LISTS;
-#ifdef CM3D_DIAG
-    int static_next = 0;                                            // diag bit 512: fixed shares, no draws (timing only)
-#endif
     auto draw = [&](int l) {                                        // request the next entry of list l; the answer is read later
         int v = 0;
-#ifdef CM3D_DIAG
-        if (diag & 512) return l == slot ? static_next++ : (1 << 20);
-#endif
         if (lane == 0) v = atomicAdd(&taken[l], 1);
         return v;
     };
@@ -729,7 +646,7 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
         return c;
     };
     PhRows<KEEP> cur;
-    ph_load_rows<STRIDE, KEEP>(cur, src, src_aux, src_stride, (size_t)p0 + (size_t)slot * PH_WC, min(PH_WC, n - slot * PH_WC), lane, PH_DIAG(8));
+    ph_load_rows<STRIDE, KEEP>(cur, src, src_aux, src_stride, (size_t)p0 + (size_t)slot * PH_WC, min(PH_WC, n - slot * PH_WC), lane);
     {
 #pragma unroll
         for (int q = 0; q < CAM_Q; ++q) reinterpret_cast<float4 *>(s_cam)[lane + 64 * q] = t_cam[q];
@@ -744,9 +661,8 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
     int chunk = chunk_of(draw_v, slot);
     if (chunk >= nwc) return;                                       // a late start: the others have been through this frame's lists
     if (chunk != slot)                                              // entry 0 was gone
-        ph_load_rows<STRIDE, KEEP>(cur, src, src_aux, src_stride, (size_t)p0 + (size_t)chunk * PH_WC, min(PH_WC, n - chunk * PH_WC), lane, PH_DIAG(8));
+        ph_load_rows<STRIDE, KEEP>(cur, src, src_aux, src_stride, (size_t)p0 + (size_t)chunk * PH_WC, min(PH_WC, n - chunk * PH_WC), lane);
     int c_nxt = chunk_of(draw2_v, slot);
-    PH_STAMP(0);                                                    // frame setup
 
     const int4 *ment = ment_all + (size_t)f * nm_cap * 2;           // two int4 per entry
     int acc_cnt = 0;                                                // ONE_PLANE: lane k = hits of mask k over this wave's chunks
@@ -779,7 +695,7 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
             }
             if (lane < 32) {
                 cnt_row[lane] = pend_cnt;
-                if (pend_cnt && !PH_DIAG(256)) atomicAdd(&grp_f[(pend_chunk / PH_GRP) * nm_cap + lane], pend_cnt);
+                if (pend_cnt) atomicAdd(&grp_f[(pend_chunk / PH_GRP) * nm_cap + lane], pend_cnt);
             }
         } else {
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -813,7 +729,7 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
         // what the compaction wants to know about the chunk before it touches anything else of it
         if (lane == 0) {
             wc_info_f[pend_chunk] = pend_drop | (any ? (int)0x80000000 : 0);
-            if (pend_drop && !PH_DIAG(256)) atomicAdd(&grp_f[ngrp_max * nm_cap + pend_chunk / PH_GRP], pend_drop);
+            if (pend_drop) atomicAdd(&grp_f[ngrp_max * nm_cap + pend_chunk / PH_GRP], pend_drop);
         }
     };
     int draw_from = list;
@@ -821,7 +737,6 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
     do {
         const int cb = chunk * PH_WC;
         const int nvalid = min(PH_WC, n - cb);                      // uniform
-        PH_COUNT(0, 1);
         f2 X[PH_NP], Y[PH_NP], Z[PH_NP];                           // rows (2h, 2h+1) of this lane side by side
         int drop_now = 0;                                           // rows of this chunk the reference drops (uniform)
         if (FUSED) {
@@ -874,7 +789,6 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
                 Z[j >> 1][j & 1] = live ? cur.v[j * S + 2] : qnan;
             }
         }
-        PH_STAMP(1);                                                // rows arrive, transform, [cloud store]
         // vmcnt counts loads and stores together and in order, and the waits the compiler places are "everything so far":
         // the one memory wait of an iteration that can be long is the one above, for rows requested a whole camera loop
         // ago.  Right behind it go the previous chunk's result stores and the request for the next chunk's rows; both
@@ -882,7 +796,7 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
         flush_results();
         PhRows<KEEP> nxt;
         if (c_nxt < nwc) {
-            ph_load_rows<STRIDE, KEEP>(nxt, src, src_aux, src_stride, (size_t)p0 + (size_t)c_nxt * PH_WC, min(PH_WC, n - c_nxt * PH_WC), lane, PH_DIAG(8));
+            ph_load_rows<STRIDE, KEEP>(nxt, src, src_aux, src_stride, (size_t)p0 + (size_t)c_nxt * PH_WC, min(PH_WC, n - c_nxt * PH_WC), lane);
             draw_from = list;
             draw_v = draw(list);                                    // the chunk after that one: answered during the camera loop
         }
@@ -902,7 +816,7 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
         // of (k_frame_tables).
         uint32_t vis = 0u;
 #pragma unroll 1
-        for (int cg = 0; cg < (PH_DIAG(4) ? 0 : n_cams); cg += PH_CG) {
+        for (int cg = 0; cg < n_cams; cg += PH_CG) {
             if (!((cam_has >> cg) & ((1u << PH_CG) - 1u))) continue;                    // no camera of the group has anything to hit
             float inside[PH_CG];
 #pragma unroll
@@ -924,20 +838,18 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
             for (int q = 0; q < PH_CG; ++q)
                 if (__ballot(inside[q] >= 0.0f)) vis |= 1u << (cg + q);
         }
-        PH_STAMP(2);                                                // wedge tests
 #pragma unroll 1
         while (vis) {
             const int c = __builtin_ctz(vis);
             vis &= vis - 1u;
             const int e0 = __builtin_amdgcn_readfirstlane(s_first[c]), e1 = __builtin_amdgcn_readfirstlane(s_first[c + 1]);
             if (e0 >= e1) continue;                                 // a camera without (non-empty) masks: nothing to hit
-            PH_COUNT(1, 1);
             // Pre-test on the approximate projection (wedge_setup): which masks of this camera can any of the wave's points
             // hit?  A point in a mask lies in the mask's bounding box; its approximate pixel is within apx_margin pixels of the
             // exact one, so it lies in the box grown by that margin.  Two thirds of the (wave, camera) pairs that reach this
             // point end here, and the exact projection below then only meets the masks that have a candidate.
             const int ne = e1 - e0;
-            const bool pretest = ne <= 32 && ((apx_okmask >> c) & 1) && !PH_DIAG(32);
+            const bool pretest = ne <= 32 && ((apx_okmask >> c) & 1);
             uint32_t cmask = ne >= 32 ? 0xFFFFFFFFu : ((1u << ne) - 1u);          // bit i = entry e0 + i is a candidate
             if (pretest) {
                 const float *ap = s_apx[c];
@@ -979,10 +891,8 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
                         if (__ballot(any)) cmask |= 1u << (e + b - e0);
                     }
                 }
-                PH_STAMP(3);
                 if (!cmask) continue;                               // no point of the wave near any mask of this camera
             }
-            PH_COUNT(2, 1);
             const int cns = __builtin_amdgcn_readfirstlane((int)s_cam[c * CM3D_CAM_STRIDE + 54]);
             const int cfl = __builtin_amdgcn_readfirstlane((int)s_cam[c * CM3D_CAM_STRIDE + 55]);
             const float *cm = s_cam + c * CM3D_CAM_STRIDE;
@@ -994,11 +904,9 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
             int pxall = px[0];
 #pragma unroll
             for (int j = 1; j < PH_PT; ++j) pxall &= px[j];
-            PH_STAMP(3);                                            // projection
-            if (!__ballot(pxall >= 0) || PH_DIAG(2)) continue;      // no point of the wave in this image
+            if (!__ballot(pxall >= 0)) continue;     // no point of the wave in this image
             // px = iv << 16 | iu (two 16-bit halves; -1 = outside): byte offset of the point's word inside a mask and its bit,
             // once per camera
-            PH_COUNT(3, 1);
             uint32_t xw4[PH_PT], iv4[PH_PT];                        // word column and row of the pixel: a mask's rows have its own stride
 #pragma unroll
             for (int j = 0; j < PH_PT; ++j) {
@@ -1019,7 +927,6 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
                     ei[b] = rem ? eb + __builtin_ctz(rem) : -1;
                     rem = rem ? (rem & (rem - 1)) : 0u;
                 }
-                PH_COUNT(4, 1);
                 int4 en[PH_MB];
 #pragma unroll
                 for (int b = 0; b < PH_MB; ++b) en[b] = ment[2 * max(ei[b], e0)];                  // uniform: scalar loads
@@ -1033,7 +940,6 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
                     kb[b] = kw < 0 ? -1 : (kw & 0xFFFF);
                     if (kb[b] < 0) continue;                        // past the last candidate (wave-uniform)
                     const uint32_t wcm = (uint32_t)kw >> 16;        // words per stored row of this mask
-                    PH_COUNT(5, 1);
                     const us2 org = __builtin_bit_cast(us2, __builtin_amdgcn_readfirstlane(en[b].x));
                     const us2 ext = __builtin_bit_cast(us2, __builtin_amdgcn_readfirstlane(en[b].y));
                     const char *mw = reinterpret_cast<const char *>(packed) + ((long long)__builtin_amdgcn_readfirstlane(en[b].w) << 2);
@@ -1065,9 +971,7 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
                 }
               }
             }
-            PH_STAMP(4);                                            // mask loop of one camera
         }
-        PH_STAMP(2);
         // The chunk's results stay in registers (LDS) until the top of the next iteration (flush_results): vmcnt counts loads
         // and stores together and in order, so a store issued here would sit in front of the very next wait -- the one for
         // the prefetched rows -- and every chunk would pay a store's whole round trip to memory.
@@ -1082,7 +986,6 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
         cur = nxt;
         chunk = c_nxt;
         if (c_nxt < nwc) c_nxt = chunk_of(draw_v, draw_from);
-        PH_STAMP(5);                                                // wait for the next rows
     } while (chunk < nwc);
     flush_results();
     if (ONE_PLANE && lane < nm && acc_cnt) atomicAdd(&hit_count[m0 + lane], acc_cnt);
@@ -1090,22 +993,6 @@ __global__ __launch_bounds__(PHK_THREADS, PH_MIN_BLOCKS) void k_project_hits(
         const int tot = cm3d_wave_sum(ONE_PLANE ? (lane < nm ? acc_cnt : 0) : acc_multi);
         if (lane == 0 && tot) atomicAdd(&frame_hits[f], tot);
     }
-#ifdef CM3D_DIAG
-    if ((diag & 16) && lane == 0)
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_ph_stamp[k], k == 7 ? 1ull : acc[k]);
-    if ((diag & 64) && lane == 0) {
-        for (int k = 0; k < 8; ++k) atomicAdd(&g_ph_count[k], (unsigned long long)cntk[k]);
-    }
-    if ((diag & 128) && lane == 0) {
-        const unsigned long long t_end = ph_now();
-        const int wid = (int)blockIdx.x * PHK_WAVES + wave;
-        const unsigned hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
-        if (wid < PH_DIAG_WAVES) {
-            g_ph_wave[3 * wid] = t_start; g_ph_wave[3 * wid + 1] = t_end;
-            g_ph_wave[3 * wid + 2] = ((unsigned long long)xcc << 32) | hw;
-        }
-    }
-#endif
 }
 
 #include "project_q.h"
@@ -1467,12 +1354,12 @@ extern "C" int cm3d_project_workgroups_per_cu(int32_t n)
     return prev;
 }
 
-// workgroups of the projection kernel the chip holds at once.  CM3D_PH_BLOCKS overrides (experiments).
+// workgroups of the projection kernel the chip holds at once
 static int ph_target_blocks(const void *kernel, size_t lds, bool share)
 {
     static int forced = -1, cus = 0;
     if (forced < 0) {
-        const char *e = getenv("CM3D_PH_BLOCKS");
+        const char *e = getenv("CM3D_PH_BLOCKS");                   // test hook: the occupancy query below decides otherwise
         forced = e ? atoi(e) : 0;
         int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
@@ -1491,6 +1378,19 @@ static int ph_target_blocks(const void *kernel, size_t lds, bool share)
     // C5, four in flight: 47.9 k frames/s with its full grid, 47.4 k at one workgroup per CU)
     if (share && g_ph_wg_per_cu > 0 && g_ph_wg_per_cu < per_cu) per_cu = g_ph_wg_per_cu;
     return cus * per_cu;
+}
+
+// The one launch site of the projection kernels.  `fn` is the variant that runs; `signature` is any instantiation of the same
+// template and only lends its parameter list, so that the arguments are converted to, and checked against, what the kernel takes.
+// The template parameters of k_project_hits and of k_project_q appear nowhere in their parameter lists: every instantiation of a
+// template has the one signature, so the borrowed one cannot be wrong.  Launch errors are left to CM3D_CHECK_LAUNCH, as before.
+template <typename T> struct ph_param { typedef T type; };           // (keeps the arguments out of the deduction of P)
+template <typename... P>
+static void ph_enqueue(const void *fn, void (*signature)(P...), dim3 grid, size_t lds, hipStream_t st, typename ph_param<P>::type... p)
+{
+    (void)signature;
+    void *args[] = {(void *)&p...};
+    (void)hipLaunchKernel(fn, grid, dim3(PHK_THREADS), args, lds, st);
 }
 
 static int ph_launch(const PhSweepIn *fused, const float *points, const int32_t *pt_off, int32_t n_frames, int32_t max_pts_per_frame,
@@ -1522,72 +1422,50 @@ static int ph_launch(const PhSweepIn *fused, const float *points, const int32_t 
     // ... | quad layout (12 bytes per row), with and without the cloud store
     const int which = !fused ? 0 : stride == CM3D_RAW_QUADS ? (keep ? 8 : 7) : (stride == 5 ? 1 : (stride == 4 ? 2 : 3)) + (keep ? 3 : 0);
     const bool one = planes_cap == 1;
-    const void *fn;
-#define PH_PICK(ONE)                                                                                                             \
-    (which == 0 ? (const void *)k_project_hits<ONE, false, 4, false>                                                             \
-     : which == 1 ? (const void *)k_project_hits<ONE, true, 5, false>                                                            \
-     : which == 2 ? (const void *)k_project_hits<ONE, true, 4, false>                                                            \
-     : which == 3 ? (const void *)k_project_hits<ONE, true, 0, false>                                                            \
-     : which == 4 ? (const void *)k_project_hits<ONE, true, 5, true>                                                             \
-     : which == 5 ? (const void *)k_project_hits<ONE, true, 4, true>                                                             \
-     : which == 6 ? (const void *)k_project_hits<ONE, true, 0, true>                                                             \
-     : which == 7 ? (const void *)k_project_hits<ONE, true, CM3D_RAW_QUADS, false> : (const void *)k_project_hits<ONE, true, CM3D_RAW_QUADS, true>)
-    if (one) fn = PH_PICK(true);
-    else fn = PH_PICK(false);
-#undef PH_PICK
-    // the quad layout has its own kernel (project_q.h) for frames of up to 96 masks; CM3D_PQ=0: k_project_hits reads the quads
-    static int pq_on = -1;
-    if (pq_on < 0) { const char *e = getenv("CM3D_PQ"); pq_on = e ? atoi(e) : 1; }
-    // (one hit-word plane only: with 80 masks per frame -- three planes in registers, 13 entries per camera -- k_project_q<3> takes
-    //  418 us per 64 frames of the 10-sweep configuration where k_project_hits with its planes in LDS takes 344: CM3D_PQ=3 to compare)
-    const bool pq = pq_on && (which == 7 || which == 8) && planes_cap <= (pq_on >= 3 ? 3 : 1);
-    if (pq) fn = one ? (keep ? (const void *)k_project_q<1, true> : (const void *)k_project_q<1, false>)
-                     : (keep ? (const void *)k_project_q<3, true> : (const void *)k_project_q<3, false>);
-    size_t lds = (one || pq) ? 0 : (size_t)PHK_WAVES * ((size_t)planes_cap * PH_WC * sizeof(uint32_t) + (size_t)nm_cap * sizeof(int));
-    if (!one && !pq) {
+    // The quad layout with one hit-word plane (up to 32 masks per frame) has its own kernel (project_q.h).  One plane only: with 80
+    // masks per frame -- three planes in registers, 13 entries per camera -- that kernel took 418 us per 64 frames of the 10-sweep
+    // configuration where k_project_hits with its planes in LDS takes 344.
+    const bool pq = one && which >= 7;
+    // the one table of the variants: kernels[one plane][which]
+    static const void *const kernels[2][9] = {
+        {(const void *)k_project_hits<false, false, 4, false>, (const void *)k_project_hits<false, true, 5, false>,
+         (const void *)k_project_hits<false, true, 4, false>, (const void *)k_project_hits<false, true, 0, false>,
+         (const void *)k_project_hits<false, true, 5, true>, (const void *)k_project_hits<false, true, 4, true>,
+         (const void *)k_project_hits<false, true, 0, true>, (const void *)k_project_hits<false, true, CM3D_RAW_QUADS, false>,
+         (const void *)k_project_hits<false, true, CM3D_RAW_QUADS, true>},
+        {(const void *)k_project_hits<true, false, 4, false>, (const void *)k_project_hits<true, true, 5, false>,
+         (const void *)k_project_hits<true, true, 4, false>, (const void *)k_project_hits<true, true, 0, false>,
+         (const void *)k_project_hits<true, true, 5, true>, (const void *)k_project_hits<true, true, 4, true>,
+         (const void *)k_project_hits<true, true, 0, true>, (const void *)k_project_q<1, false>, (const void *)k_project_q<1, true>}};
+    const void *const fn = kernels[one][which];
+    // several planes: hit words and counts in dynamic LDS; one plane: registers only, and the grid that fills the chip is cached per variant
+    const size_t lds = one ? 0 : (size_t)PHK_WAVES * ((size_t)planes_cap * PH_WC * sizeof(uint32_t) + (size_t)nm_cap * sizeof(int));
+    if (!one) {
         static size_t lds_allowed[9] = {48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024, 48 * 1024};
         if (lds > lds_allowed[which]) {
             if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return CM3D_ERR_LAUNCH;
             lds_allowed[which] = lds;
         }
     }
-    static int blocks_one[9 + 4] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};       // cached for the register-only variants (no dynamic LDS)
+    static int blocks_one[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     static int blocks_hint = 0;                                                   // ... under this value of cm3d_project_workgroups_per_cu
     if (blocks_hint != g_ph_wg_per_cu) {
         for (int &b : blocks_one) b = 0;
         blocks_hint = g_ph_wg_per_cu;
     }
-    const int slot_id = pq ? 9 + (one ? 0 : 2) + (keep ? 1 : 0) : which;
-    int target = (one || pq) ? blocks_one[slot_id] : 0;
+    int target = one ? blocks_one[which] : 0;
     if (!target) {
         target = ph_target_blocks(fn, lds, pq);
-        if (one || pq) blocks_one[slot_id] = target;
+        if (one) blocks_one[which] = target;
     }
-    // tickets per frame: about PH_OVERSUB times as many waves as the chip holds at once (see the kernel's header), at least
-    // two wave-chunks per ticket when the frames are that long
+    // tickets per frame: as many waves as the chip holds at once (see the kernel's header), at least two wave-chunks per ticket
+    // when the frames are that long
     static int tpf_forced = -1;
-    if (tpf_forced < 0) { const char *e = getenv("CM3D_PH_TICKETS"); tpf_forced = e ? atoi(e) : 0; }
-    int tpf = tpf_forced > 0 ? tpf_forced : (int)(((long long)PH_OVERSUB_NUM * target * PHK_WAVES / PH_OVERSUB_DEN + n_frames - 1) / n_frames);
+    if (tpf_forced < 0) { const char *e = getenv("CM3D_PH_TICKETS"); tpf_forced = e ? atoi(e) : 0; }      // test hook: the launch derives it from the chip and the batch
+    int tpf = tpf_forced > 0 ? tpf_forced : (int)(((long long)target * PHK_WAVES + n_frames - 1) / n_frames);
     if (tpf > ph_tpf_max(nwc_max)) tpf = ph_tpf_max(nwc_max);
     if (tpf < 1) tpf = 1;
-    const int gx = (int)(((long long)n_frames * tpf + PHK_WAVES - 1) / PHK_WAVES);
-#define PH_LAUNCH(ONE, FUSED, STRIDE, KEEP)                                                                                      \
-    hipLaunchKernelGGL((k_project_hits<ONE, FUSED, STRIDE, KEEP>), dim3(gx), dim3(PHK_THREADS), lds, st, src, sw.intensity, stride, sw.sweep_xf, \
-                       sw.halfw, sw.points_out, sw.removed_bits, ws.ft, ws.ment, cams, n_cams, packed, W, H, Wp, min_dist, nm_cap, \
-                       nwc_max, n_points_total, hit_words, hit_count, ws.wc_cnt, n_frames, tpf, ws.queue, ws.wc_info, ws.grp, ws.zstride,     \
-                       ws.frame_hits)
-#define PH_LAUNCH_S(ONE)                                                                                                         \
-    do {                                                                                                                         \
-        if (which == 0) PH_LAUNCH(ONE, false, 4, false);                                                                         \
-        else if (which == 1) PH_LAUNCH(ONE, true, 5, false);                                                                     \
-        else if (which == 2) PH_LAUNCH(ONE, true, 4, false);                                                                     \
-        else if (which == 3) PH_LAUNCH(ONE, true, 0, false);                                                                     \
-        else if (which == 4) PH_LAUNCH(ONE, true, 5, true);                                                                      \
-        else if (which == 5) PH_LAUNCH(ONE, true, 4, true);                                                                      \
-        else if (which == 6) PH_LAUNCH(ONE, true, 0, true);                                                                      \
-        else if (which == 7) PH_LAUNCH(ONE, true, CM3D_RAW_QUADS, false);                                                        \
-        else PH_LAUNCH(ONE, true, CM3D_RAW_QUADS, true);                                                                         \
-    } while (0)
+    const dim3 grid((unsigned)(((long long)n_frames * tpf + PHK_WAVES - 1) / PHK_WAVES));
     hipLaunchKernelGGL(k_frame_tables, dim3(n_frames), dim3(64), 0, st, sw, fused ? 1 : 0, pt_off, n_frames, cams, n_cams, mask_off, mask_cam,
                        (const int4 *)bbox, W, H, min_dist, nm_cap, max_pts_per_frame, (uint32_t)H * (uint32_t)Wp, ws.ft, ws.ment, ws.queue, tpf,
                        ws.grp, ws.zstride, ws.frame_hits, status);
@@ -1601,19 +1479,13 @@ static int ph_launch(const PhSweepIn *fused, const float *points, const int32_t 
         qa.wc_cnt = ws.wc_cnt; qa.queue = ws.queue; qa.wc_info = ws.wc_info; qa.grp = ws.grp; qa.frame_hits = ws.frame_hits;
         qa.halfw = sw.halfw; qa.min_dist = min_dist; qa.n_cams = n_cams; qa.W = W; qa.H = H; qa.nm_cap = nm_cap; qa.nwc_max = nwc_max;
         qa.n_points_total = n_points_total; qa.n_frames = n_frames; qa.tpf = tpf; qa.zstride = ws.zstride;
-        qa.stage = 99;
-#ifdef CM3D_DIAG
-        qa.stage = g_pq_stage;
-#endif
-        if (one) { if (keep) hipLaunchKernelGGL((k_project_q<1, true>), dim3(gx), dim3(PHK_THREADS), 0, st, qa);
-                   else hipLaunchKernelGGL((k_project_q<1, false>), dim3(gx), dim3(PHK_THREADS), 0, st, qa); }
-        else { if (keep) hipLaunchKernelGGL((k_project_q<3, true>), dim3(gx), dim3(PHK_THREADS), 0, st, qa);
-               else hipLaunchKernelGGL((k_project_q<3, false>), dim3(gx), dim3(PHK_THREADS), 0, st, qa); }
-    } else if (one) PH_LAUNCH_S(true);
-    else PH_LAUNCH_S(false);
+        ph_enqueue(fn, k_project_q<1, false>, grid, lds, st, qa);
+    } else {
+        ph_enqueue(fn, k_project_hits<false, false, 4, false>, grid, lds, st, src, sw.intensity, stride, sw.sweep_xf, sw.halfw, sw.points_out,
+                   sw.removed_bits, ws.ft, ws.ment, cams, n_cams, packed, W, H, Wp, min_dist, nm_cap, nwc_max, n_points_total, hit_words,
+                   hit_count, ws.wc_cnt, n_frames, tpf, ws.queue, ws.wc_info, ws.grp, ws.zstride, ws.frame_hits);
+    }
     if (ev_stop && hipEventRecord((hipEvent_t)ev_stop, st) != hipSuccess) return CM3D_ERR_LAUNCH;
-#undef PH_LAUNCH_S
-#undef PH_LAUNCH
     CM3D_CHECK_LAUNCH();
     return CM3D_OK;
 }
@@ -1677,7 +1549,7 @@ extern "C" int cm3d_compact_hits(const uint32_t *hit_words, int32_t planes, int3
     PhXyzSrc xs;
     xs.raw = raw; xs.intensity = intensity; xs.raw_stride = raw_stride; xs.sweep_xf = sweep_xf; xs.points = (const float4 *)points;
     // wave-chunks per wave: 4; 8 for frames of 150 k points and more (C4: 906 -> 920 k frames/s; C2 2.59 -> 2.55 M with 8, C1 and C5 no difference);
-    // CM3D_CP_SPAN = 2 / 4 / 8 forces one (experiments, tests/test_gpu_golden.py)
+    // CM3D_CP_SPAN = 2 / 4 / 8: test hook, forces one where the line below picks by the frames' length
     static int span_forced = -1;
     if (span_forced < 0) { const char *e = getenv("CM3D_CP_SPAN"); span_forced = e ? atoi(e) : 0; if (span_forced != 2 && span_forced != 4 && span_forced != 8) span_forced = 0; }
     const int span = span_forced ? span_forced : (nwc_max >= 600 ? 8 : 4);

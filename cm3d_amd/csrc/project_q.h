@@ -15,7 +15,8 @@
 //     common one nothing);
 //   * rows arrive as quads: three 16-byte loads per lane, x / y / z of the lane's four rows already pairwise in consecutive
 //     registers, which is the operand shape of the packed float32 instructions;
-//   * hit words of up to 96 masks stay in registers (NPL = 1 or 3 planes): no LDS traffic for the 80-mask configuration.
+//   * hit words stay in registers (NPL planes).  The launch instantiates NPL = 1 only, frames of up to 32 masks (ph_launch in
+//     project.hip has the measured reason).
 // Work distribution (tickets, per-list counters, stealing inside the frame), the results and their layout are k_project_hits':
 // k_frame_tables before it and k_compact_hits behind it do not know which of the two ran.
 #pragma once
@@ -26,24 +27,13 @@ struct PqArgs {
     uint32_t *hit_words; int32_t *hit_count; int32_t *wc_cnt; int32_t *queue; int32_t *wc_info; int32_t *grp; int32_t *frame_hits;
     float halfw, min_dist;
     int n_cams, W, H, nm_cap, nwc_max, n_points_total, n_frames, tpf, zstride;
-    int stage;                                    // 99 = everything; the diagnostic build stops the chunk loop's stages earlier (timing only)
 };
 
-// the chunk loop's stage cuts and ablation bits exist in the diagnostic build only: in the product every test of `stage` was a loop-invariant
-// condition the compiler kept as a 64-bit mask in two scalar registers (seven of them, in spill lanes)
-#ifdef CM3D_DIAG
-#define PQ_STAGE(a) ((a).stage)
-#else
-#define PQ_STAGE(a) 99
-#endif
 #ifndef PQ_OPT_LDSV
 #define PQ_OPT_LDSV 1       // LDS slices addressed from a vector register
 #endif
 #ifndef PQ_OPT_SCALV
 #define PQ_OPT_SCALV 1      // uniform operands of vector instructions in vector registers
-#endif
-#ifndef PQ_OPT_PTRV
-#define PQ_OPT_PTRV 0       // per-lane base addresses in vector registers (no fewer spills on top of the other two, 1 % slower in flight)
 #endif
 #ifndef PQ_MIN_BLOCKS
 #define PQ_MIN_BLOCKS 3                           // waves per SIMD the register budget is held to (168 registers): what the launch fills anyway
@@ -74,20 +64,6 @@ static __device__ __forceinline__ void pq_xform4(const float *xf, const float (&
     }
 }
 
-#ifdef CM3D_DIAG
-#define PQ_STAMP(k) do { if ((a.stage & 255) == 100) { const unsigned long long t_ = ph_now(); acc[k] += t_ - t_prev; t_prev = t_; } } while (0)
-#else
-#define PQ_STAMP(k) do { } while (0)
-#endif
-#ifdef CM3D_DIAG
-// one interval only (two s_memtime per chunk: little disturbance): stage & 255 == WHICH
-#define PQ_IV_BEGIN(which) unsigned long long iv_t0_##which = 0; if ((a.stage & 255) == (which)) iv_t0_##which = ph_now()
-#define PQ_IV_END(which) do { if ((a.stage & 255) == (which)) { acc[1] += ph_now() - iv_t0_##which; acc[2] += 1; } } while (0)
-#else
-#define PQ_IV_BEGIN(which) do { } while (0)
-#define PQ_IV_END(which) do { } while (0)
-#endif
-
 #ifdef PQ_NUM_VGPR
 #define PQ_VGPR_ATTR __attribute__((amdgpu_num_vgpr(PQ_NUM_VGPR)))
 #else
@@ -96,10 +72,6 @@ static __device__ __forceinline__ void pq_xform4(const float *xf, const float (&
 template <int NPL, bool KEEP>
 __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_project_q(const PqArgs a)
 {
-#ifdef CM3D_DIAG
-    unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_prev = (PQ_STAGE(a) & 255) >= 100 ? ph_now() : 0ull;
-    const unsigned long long t_prev0 = t_prev;
-#endif
     constexpr int NE = NPL == 1 ? 1 : 2;          // sets of 64 mask entries held in register lanes
     constexpr int NC = NPL == 1 ? 1 : 2;          // count registers: lane k of set s = hits of mask 64 s + k
     const int lane = cm3d_lane(), wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -126,14 +98,8 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
     const int32_t *ft = a.ft_all + (size_t)f * FT_WORDS;
     int32_t *const taken = a.queue + (size_t)f * tpf;
     int list = slot, lists_left = PH_STEAL_LISTS;
-#ifdef CM3D_DIAG
-    int static_next = 0;
-#endif
     auto draw = [&](int l) {
         int v = 0;
-#ifdef CM3D_DIAG
-        if (PQ_STAGE(a) & 512) return l == slot ? static_next++ : (1 << 20);     // timing only: fixed shares, no draws
-#endif
         if (lane == 0) v = atomicAdd(&taken[l], 1);
         return v;
     };
@@ -181,17 +147,13 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
         }
         return c;
     };
-    // Per-lane base addresses in VECTOR registers (pinned by the empty asm: the compiler would put the uniform part back into scalar
-    // registers) for everything the chunk loop reads or writes with a per-lane address: a 64-bit base in scalar registers costs two of
-    // the 102 the loop does not have (46 lived in spill lanes), here it is one v_lshl_add_u64 with the chunk's offset per use.
+    // Per-lane base addresses for everything the chunk loop reads or writes with a per-lane address.  (Pinning them in vector registers
+    // with an empty asm was measured: no fewer spills on top of PQ_OPT_LDSV and PQ_OPT_SCALV, 1 % slower in flight.)
     const float *raw_lane = a.raw + ((size_t)p0 + 4 * lane) * 3;
     uint32_t *hw_lane = a.hit_words + (size_t)p0 + 4 * lane;
     uint32_t *rb_lane = a.removed_bits + (size_t)bits_off + (lane >> 3);
     int32_t *cnt_lane = a.wc_cnt + (size_t)f * a.nwc_max * a.nm_cap + lane;
     int32_t *grp_lane = a.grp + (size_t)f * a.zstride + lane;
-#if PQ_OPT_PTRV
-    asm volatile("" : "+v"(raw_lane), "+v"(hw_lane), "+v"(rb_lane), "+v"(cnt_lane), "+v"(grp_lane));
-#endif
     // the lane's four rows of a chunk: x0..3 y0..3 z0..3 [+ the four intensities when the cloud is kept]
     struct Rows { float q[12]; float w[KEEP ? 4 : 1]; };
     auto load_rows = [&](Rows &r, int chunk) {
@@ -228,7 +190,6 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
     if (chunk >= nwc) return;
     if (chunk != slot) load_rows(cur, chunk);
     int c_nxt = chunk_of(draw2_v, slot);
-    PQ_STAMP(0);                                                    // start-up
 
     // the sweep whose coefficients the wave's LDS slice holds; -1: none yet
     int vxf_sweep = -1;
@@ -256,9 +217,6 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
     int pend_chunk = -1, pend_drop = 0;
     auto flush_results = [&]() {
         if (pend_chunk < 0) return;
-#ifdef CM3D_DIAG
-        if (PQ_STAGE(a) & 1024) return;                                 // timing only: no result stores at all
-#endif
         const int pcb = pend_chunk * PH_WC, pvalid = min(PH_WC, n - pcb);
         int32_t *cnt_row = cnt_lane + pend_chunk * a.nm_cap;              // (this lane's entry)
         bool mine = pend_cnt[0] != 0;
@@ -283,12 +241,12 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
             const int k = 64 * s + lane;
             if (k < nm) {
                 cnt_row[64 * s] = pend_cnt[s];
-                if (pend_cnt[s] && !(PQ_STAGE(a) & 256)) atomicAdd(&grp_lane[(pend_chunk / PH_GRP) * a.nm_cap + 64 * s], pend_cnt[s]);
+                if (pend_cnt[s]) atomicAdd(&grp_lane[(pend_chunk / PH_GRP) * a.nm_cap + 64 * s], pend_cnt[s]);
             }
         }
         if (lane == 0) {
             wc_info_f[pend_chunk] = pend_drop | (any ? (int)0x80000000 : 0);
-            if (pend_drop && !(PQ_STAGE(a) & 256)) atomicAdd(&grp_f[ngrp_max * a.nm_cap + pend_chunk / PH_GRP], pend_drop);
+            if (pend_drop) atomicAdd(&grp_f[ngrp_max * a.nm_cap + pend_chunk / PH_GRP], pend_drop);
         }
     };
     int draw_from = list;
@@ -305,17 +263,12 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
     do {
         const int cb = chunk * PH_WC;
         const int nvalid = min(PH_WC, n - cb);
-        PQ_IV_BEGIN(105);
         // ---- sweep preparation (reference :437-465): ego-box drop on the raw coordinates, sensor -> ego -> global
         int sw_lo = 0, sw_hi = 0;
         if (ns > 1) { sw_lo = ph_sweep_of_u(v_srow, cb); sw_hi = ph_sweep_of_u(v_srow, cb + nvalid - 1); }
         if (sw_lo != vxf_sweep) { load_xf(sw_lo, s_xf); vxf_sweep = sw_lo; }
         float g[12];
-        if ((PQ_STAGE(a) & 255) >= 1) pq_xform4(s_xf, cur.q, g);
-        else {
-#pragma unroll
-            for (int k = 0; k < 12; ++k) g[k] = cur.q[k];
-        }
+        pq_xform4(s_xf, cur.q, g);
         if (sw_hi > sw_lo) {                                        // a sweep boundary inside the chunk: once more per further sweep, rows selected
             for (int sw = sw_lo + 1; sw <= sw_hi; ++sw) {
                 load_xf(sw, s_xf2);
@@ -367,15 +320,8 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
             asm volatile("" : "+v"(l7));                            // (not a loop invariant: its mask would sit in two scalar registers for a path few chunks take)
             if (l7 == 0) rb_lane[8 * chunk] = (uint32_t)vv;
         }
-        PQ_STAMP(1);                                                // rows arrive, transform, dropped rows
-        PQ_IV_END(105);
         // ---- the previous chunk's results out, the next chunk's rows and the draw after it in
-        {
-            PQ_IV_BEGIN(106);
-            flush_results();
-            PQ_IV_END(106);
-        }
-        PQ_IV_BEGIN(107);
+        flush_results();
         Rows nxt;
         if (c_nxt < nwc) {
             load_rows(nxt, c_nxt);
@@ -390,13 +336,10 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
         int mycnt[NC];
 #pragma unroll
         for (int s = 0; s < NC; ++s) mycnt[s] = 0;
-        PQ_STAMP(2);                                                // results out, next rows + draw issued
-        PQ_IV_END(107);
         // ---- view wedges (wedge_setup): which cameras can see any of the wave's points
-        PQ_IV_BEGIN(104);
         uint32_t vis = 0u;
 #pragma unroll 1
-        for (int cgp = 0; cgp < ((PQ_STAGE(a) & 255) >= 2 ? n_cams : 0); cgp += PH_CG) {
+        for (int cgp = 0; cgp < n_cams; cgp += PH_CG) {
             if (!((cam_has >> cgp) & ((1u << PH_CG) - 1u))) continue;
             float inside[PH_CG];
 #pragma unroll
@@ -418,13 +361,12 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
             for (int q = 0; q < PH_CG; ++q)
                 if (__ballot(inside[q] >= 0.0f)) vis |= 1u << (cgp + q);
         }
-        PQ_STAMP(3);                                                // view wedges
 #pragma unroll 1
         while (vis) {
             const int c = __builtin_ctz(vis);
             vis &= vis - 1u;
             const int e0 = __builtin_amdgcn_readlane(v_first, c), e1 = __builtin_amdgcn_readlane(v_first, c + 1);
-            if (e0 >= e1 || (PQ_STAGE(a) & 255) < 3) continue;
+            if (e0 >= e1) continue;
             // ---- approximate projection (wedge_setup): pixel codes for the grown boxes
             const bool pretest = (apx_okmask >> c) & 1;
             int pa[PH_PT];
@@ -449,7 +391,6 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
                     }
                 }
             }
-            PQ_STAMP(4);                                            // approximate projection
             bool projected = false;
             int px[PH_PT];
             uint32_t xw4[PH_PT], iv4[PH_PT];
@@ -474,10 +415,8 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
                         }
                         if (__ballot(any)) cmask |= 1u << i;
                     }
-                    PQ_STAMP(5);                                    // grown-box tests
                     if (!cmask) continue;
                 }
-                if ((PQ_STAGE(a) & 255) < 4) break;
                 if (!projected) {
                     projected = true;
                     const int cns = __builtin_amdgcn_readfirstlane((int)s_cam[c * CM3D_CAM_STRIDE + 54]);
@@ -497,8 +436,7 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
                         xw4[j] = ((uint32_t)px[j] & 0xFFFFu) >> 5;
                     }
                 }
-                PQ_STAMP(6);                                        // exact chain
-                uint32_t rem = (PQ_STAGE(a) & 255) >= 5 ? cmask : 0u;
+                uint32_t rem = cmask;
                 // candidate masks of the block, up to PH_MB at a time: all their words are requested before the first is used (one
                 // memory round trip per batch).  A batch is straight-line code for its number of masks (mask_batch<NB>): every load
                 // has its use on the same path, so the compiler's s_waitcnt bookkeeping never carries a "pending" word register
@@ -556,7 +494,6 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
                         else mycnt[NC - 1] += lane == kb[b] - 64 ? cnt : 0;
                     }
                 };
-                PQ_IV_BEGIN(103);
                 while (rem) {
                     const int nb = __builtin_popcount(rem);
                     if (nb >= 4) mask_batch(std::integral_constant<int, 4>());
@@ -564,7 +501,6 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
                     else if (nb == 2) mask_batch(std::integral_constant<int, 2>());
                     else mask_batch(std::integral_constant<int, 1>());
                 }
-                PQ_IV_END(103);
             }
         }
 #pragma unroll
@@ -573,21 +509,11 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
             for (int j = 0; j < PH_PT; ++j) pend_bits[pl][j] = bits[pl][j];
 #pragma unroll
         for (int s = 0; s < NC; ++s) { pend_cnt[s] = mycnt[s]; acc_cnt[s] += mycnt[s]; }
-        PQ_STAMP(7);                                                // gather (the rest of the camera loop)
-        PQ_IV_END(104);
         pend_chunk = chunk;
         pend_drop = drop_now;
-        {
-            PQ_IV_BEGIN(101);
-            cur = nxt;
-            chunk = c_nxt;
-            if (c_nxt < nwc) c_nxt = chunk_of(draw_v, draw_from);
-#ifdef CM3D_DIAG
-            if ((PQ_STAGE(a) & 255) == 101) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-            PQ_IV_END(101);
-        }
-        PQ_STAMP(0);                                                // wait for the draw (and the rows requested before it)
+        cur = nxt;
+        chunk = c_nxt;
+        if (c_nxt < nwc) c_nxt = chunk_of(draw_v, draw_from);
     } while (chunk < nwc);
     flush_results();
     int tot = 0;
@@ -599,17 +525,4 @@ __global__ __launch_bounds__(PHK_THREADS, PQ_MIN_BLOCKS) PQ_VGPR_ATTR void k_pro
     }
     tot = cm3d_wave_sum(tot);
     if (lane == 0 && tot) atomicAdd(&a.frame_hits[f], tot);
-#ifdef CM3D_DIAG
-    if ((PQ_STAGE(a) & 255) >= 100 && lane == 0) {
-        acc[0] = ph_now() - t_prev0;
-        // (per-wave slots, plain stores: thousands of atomics on one address at the end of the early waves held up the draws of the late ones)
-        const int wid = (int)blockIdx.x * PHK_WAVES + wave;
-        if ((PQ_STAGE(a) & 255) == 100) {
-            for (int k = 0; k < 8; ++k) atomicAdd(&g_ph_stamp[k], acc[k]);
-            atomicAdd(&g_ph_count[0], 1ull);
-        } else if (wid < PH_DIAG_WAVES) {
-            g_ph_wave[3 * wid] = acc[0]; g_ph_wave[3 * wid + 1] = acc[1]; g_ph_wave[3 * wid + 2] = acc[2];
-        }
-    }
-#endif
 }
