@@ -7,18 +7,16 @@
 // never match.  Counted per (breakdown, cutoff): TP, FP, FN at LEVEL_1, FN at LEVEL_2 and the heading-accuracy sum of
 // the matches (int64, 2^-32 units), all with integer atomics: the result does not depend on the order in which waves run.
 //
-// Two launches:
+// Launches:
 //   k_wm_weights   one thread per (prediction, ground truth) pair of a group: float64 polygon clipping x z overlap
-//   k_wm_match<C>  one wave per group of at most 64 C columns (C = 1, 2, 4, 16): the Hungarian method with potentials,
-//                  columns in registers (lane (j - 1) % 64, slot (j - 1) / 64) as in fusion.hip's k_bev_assign_small.  Rows
-//                  are predictions in score order, columns the ground truth padded with empty columns to max(P, G).
+//   k_wm_match<C>  one wave per group of at most 64 C columns (C = 1, 2, 4, 16): assign.h's AssignSolver.  Rows are
+//                  predictions in score order, columns the ground truth padded with empty columns to max(P, G).
 //                  The method adds one row per phase and the assignment after phase k is optimal for the first k rows,
 //                  so ONE solve gives the matching of every cutoff: the counts are taken after the phases that end a
 //                  cutoff's prediction subset (at most P + 1 distinct subsets).  per_cutoff != 0 solves every cutoff
 //                  afresh instead (a check of that deduplication).
-#include "bev_iou.h"
+#include "assign.h"
 
-#define WM_KMAX 1000000
 #define WM_BREAKDOWNS 16
 #define WM_CUTOFFS 101
 #define WM_LDS 4096                 // weights of a group up to this many pairs sit in LDS, larger ones are read from L2
@@ -63,21 +61,6 @@ __global__ __launch_bounds__(256) void k_wm_zero(long long *__restrict__ counts,
     if (t < WM_BREAKDOWNS * WM_CUTOFFS) heading[t] = 0;
 }
 
-// first group of every 256-pair block of k_wm_weights
-__global__ __launch_bounds__(256) void k_wm_block_groups(const int64_t *__restrict__ pair_off, int n_groups, int64_t n_blocks,
-                                                         int32_t *__restrict__ blk_group)
-{
-    const int64_t b = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (b >= n_blocks) return;
-    const int64_t t = b * 256;
-    int lo = 0, hi = n_groups;              // last g with pair_off[g] <= t
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pair_off[mid] <= t) lo = mid; else hi = mid;
-    }
-    blk_group[b] = lo;
-}
-
 __global__ __launch_bounds__(256) void k_wm_weights(const double *__restrict__ pred, const int32_t *__restrict__ pred_off,
                                                     const double *__restrict__ gt, const int32_t *__restrict__ gt_off,
                                                     const int32_t *__restrict__ group_bd, const int64_t *__restrict__ pair_off,
@@ -86,50 +69,11 @@ __global__ __launch_bounds__(256) void k_wm_weights(const double *__restrict__ p
 {
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= total_pairs) return;
-    int g = blk_group[blockIdx.x];
-    while (g + 1 < n_groups && pair_off[g + 1] <= t) ++g;
-    const int G = gt_off[g + 1] - gt_off[g];
-    const int64_t r = t - pair_off[g];
-    const int p = (int)(r / G), j = (int)(r - (int64_t)p * G);
-    const double iou = wm_iou3d(pred + (int64_t)(pred_off[g] + p) * CM3D_WM_BOX_STRIDE, gt + (int64_t)(gt_off[g] + j) * CM3D_WM_BOX_STRIDE);
-    weight[t] = iou >= wm_thr(group_bd[g]) ? (int)(iou * (double)WM_KMAX) : 0;
+    const AssignPair q = assign_locate(t, blk_group, pair_off, gt_off, n_groups);
+    const double iou = wm_iou3d(pred + (int64_t)(pred_off[q.group] + q.p) * CM3D_WM_BOX_STRIDE,
+                                gt + (int64_t)(gt_off[q.group] + q.g) * CM3D_WM_BOX_STRIDE);
+    weight[t] = assign_weight(iou, wm_thr(group_bd[q.group]));
 }
-
-static __device__ __forceinline__ long long wm_wave_min(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const long long w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
-static __device__ __forceinline__ long long wm_wave_sum(long long v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-template <int CPL, typename T>
-static __device__ __forceinline__ T wm_get(const T (&a)[CPL], int idx)        // a[] of element idx (uniform idx)
-{
-    T r = a[0];
-    r = __shfl(r, idx & 63, 64);
-#pragma unroll
-    for (int k = 1; k < CPL; ++k) {
-        const T t = __shfl(a[k], idx & 63, 64);
-        r = (idx >> 6) == k ? t : r;
-    }
-    return r;
-}
-
-template <int CPL>
-struct WmSolver {                                // potentials stay within n x WM_KMAX <= 1024 x 10^6 < 2^31
-    int u[CPL], v[CPL];
-    int p[CPL], way[CPL];
-};
 
 template <int CPL>
 __global__ __launch_bounds__(64) void k_wm_match(const float *__restrict__ pred_head, const float *__restrict__ pred_score,
@@ -150,9 +94,7 @@ __global__ __launch_bounds__(64) void k_wm_match(const float *__restrict__ pred_
         if (bd < 0 || bd >= WM_BREAKDOWNS) { if (lane == 0) atomicOr(status, 2); return; }
         if (big > CM3D_MAX_MATCH_BOXES) { if (lane == 0) atomicOr(status, 1); return; }
     }
-    if (bd < 0 || bd >= WM_BREAKDOWNS || big > 64 * CPL) return;
-    if (CPL > 1 && big <= 64 * (CPL == 2 ? 1 : CPL == 4 ? 2 : 4)) return;        // another instance's group
-    if (CPL == 1 && big == 0) return;
+    if (bd < 0 || bd >= WM_BREAKDOWNS || !assign_instance_takes<CPL>(big)) return;       // another instance's group
     const int32_t *__restrict__ Wm = weight + pair_off[g];
     const bool in_lds = P * G <= WM_LDS;
     if (in_lds) {
@@ -180,10 +122,10 @@ __global__ __launch_bounds__(64) void k_wm_match(const float *__restrict__ pred_
     }
     int n_l1 = 0;
     for (int j = lane; j < G; j += 64) n_l1 += gt_level[g0 + j] == 1;
-    n_l1 = (int)wm_wave_sum(n_l1);
+    n_l1 = cm3d_wave_sum(n_l1);
     long long r_tp[2] = {0, 0}, r_fn1[2] = {n_l1, n_l1}, r_fn2[2] = {G, G}, r_h[2] = {0, 0};      // the empty subset's counts
 
-    WmSolver<CPL> S;
+    AssignSolver<CPL> S;
     // counts of the current assignment, taken by the lanes whose cutoff subset has `rows` predictions
     // TP, FN at LEVEL_1 and the heading sum of the current assignment (pairs of zero weight are no match)
     auto count = [&](long long &tp, long long &fn1, long long &h) {
@@ -198,9 +140,9 @@ __global__ __launch_bounds__(64) void k_wm_match(const float *__restrict__ pred_
                 if (matched) h += wm_heading_fx(pred_head[p0 + i - 1], gt_head[g0 + col - 1]);
             }
         }
-        tp = wm_wave_sum(tp);
-        fn1 = wm_wave_sum(fn1);
-        h = wm_wave_sum(h);
+        tp = assign_wave_sum(tp);
+        fn1 = assign_wave_sum(fn1);
+        h = assign_wave_sum(h);
     };
     auto record = [&](int rows) {
         long long tp = 0, fn1 = 0, h = 0;
@@ -209,65 +151,18 @@ __global__ __launch_bounds__(64) void k_wm_match(const float *__restrict__ pred_
         for (int s = 0; s < 2; ++s)
             if (kc[s] == rows) { r_tp[s] = tp; r_fn1[s] = fn1; r_fn2[s] = G - tp; r_h[s] = h; }
     };
-    // Hungarian method over rows 1..n, columns 1..m; after row i: record(i) when some lane's cutoff ends there
-    auto solve = [&](int n, int m, bool every_boundary) {
-#pragma unroll
-        for (int k = 0; k < CPL; ++k) { S.u[k] = 0; S.v[k] = 0; S.p[k] = 0; S.way[k] = 0; }
-        for (int i = 1; i <= n; ++i) {
-            long long minv[CPL];
-            bool used[CPL], row_in_tree[CPL];
-#pragma unroll
-            for (int k = 0; k < CPL; ++k) { minv[k] = 1ll << 50; used[k] = false; row_in_tree[k] = false; }
-            int j0 = 0;
-            while (true) {
-                const int i0 = j0 == 0 ? i : wm_get<CPL, int>(S.p, j0 - 1);
-                const long long ui0 = wm_get<CPL, int>(S.u, i0 - 1);
-                long long key = (1ll << 62);
-#pragma unroll
-                for (int k = 0; k < CPL; ++k) {
-                    const int col = k * 64 + lane + 1;
-                    if (col == j0) used[k] = true;
-                    if (col == i0) row_in_tree[k] = true;
-                    if (col <= m && !used[k]) {
-                        const long long cur = (long long)(WM_KMAX - wgt(i0, col)) - ui0 - S.v[k];
-                        if (cur < minv[k]) { minv[k] = cur; S.way[k] = j0; }
-                        const long long kk = minv[k] * 4096 + (S.p[k] != 0 ? 2048 : 0) + col;     // an unassigned column first
-                        key = kk < key ? kk : key;
-                    }
-                }
-                key = wm_wave_min(key);
-                const long long delta = key >> 12;
-                const int j1 = __builtin_amdgcn_readfirstlane((int)(key & 2047));
-#pragma unroll
-                for (int k = 0; k < CPL; ++k) {
-                    if (row_in_tree[k]) S.u[k] += (int)delta;
-                    if (used[k]) S.v[k] -= (int)delta; else minv[k] -= delta;
-                }
-                j0 = j1;
-                if (wm_get<CPL, int>(S.p, j0 - 1) == 0) break;
-            }
-            do {                                 // augment along the predecessor chain
-                const int j1 = wm_get<CPL, int>(S.way, j0 - 1);
-                const int pr = j1 == 0 ? i : wm_get<CPL, int>(S.p, (j1 == 0 ? 1 : j1) - 1);
-#pragma unroll
-                for (int k = 0; k < CPL; ++k)
-                    if (k * 64 + lane + 1 == j0) S.p[k] = pr;
-                j0 = j1;
-            } while (j0);
-            if (every_boundary) {
-                const bool here = kc[0] == i || kc[1] == i;
-                if (__builtin_amdgcn_ballot_w64(here) != 0ull) record(i);
-            }
-        }
+    auto record_boundary = [&](int i) {          // after row i: record(i) when some lane's cutoff ends there
+        const bool here = kc[0] == i || kc[1] == i;
+        if (__builtin_amdgcn_ballot_w64(here) != 0ull) record(i);
     };
     if (!per_cutoff) {
-        if (P > 0 && G > 0) solve(P, big, true);
+        if (P > 0 && G > 0) S.solve(P, big, wgt, record_boundary);
     } else {
         // every cutoff on its own: a fresh solve over its subset, columns padded to max(k, G)
         for (int c = 0; c < WM_CUTOFFS; ++c) {
             const int k = __shfl(c < 64 ? kc[0] : kc[1], c & 63, 64);
             if (k > 0 && G > 0) {
-                solve(k, k > G ? k : G, false);
+                S.solve(k, k > G ? k : G, wgt, [](int) {});
                 long long tp = 0, fn1 = 0, h = 0;
                 count(tp, fn1, h);
                 if (lane == (c & 63) && c < 64) { r_tp[0] = tp; r_fn1[0] = fn1; r_fn2[0] = G - tp; r_h[0] = h; }
@@ -292,8 +187,7 @@ __global__ __launch_bounds__(64) void k_wm_match(const float *__restrict__ pred_
 
 extern "C" int64_t cm3d_waymo_metrics_workspace_bytes(int64_t total_pairs)
 {
-    const int64_t n = total_pairs > 0 ? total_pairs : 1;
-    return (n + (n + 255) / 256) * (int64_t)sizeof(int32_t);           // weights + the first group of every 256-pair block
+    return assign_workspace_bytes(total_pairs);
 }
 
 extern "C" int cm3d_waymo_metrics(const double *pred_box, const float *pred_heading, const float *pred_score,
@@ -316,7 +210,7 @@ extern "C" int cm3d_waymo_metrics(const double *pred_box, const float *pred_head
     if (total_pairs > 0) {
         int32_t *blk_group = weight + total_pairs;
         const int64_t n_blocks = (total_pairs + 255) / 256;
-        hipLaunchKernelGGL(k_wm_block_groups, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, st, pair_off, n_groups, n_blocks,
+        hipLaunchKernelGGL(k_assign_block_owner, dim3((unsigned)((n_blocks + 255) / 256)), dim3(256), 0, st, pair_off, n_groups, n_blocks,
                            blk_group);
         CM3D_CHECK_LAUNCH();
         hipLaunchKernelGGL(k_wm_weights, dim3((unsigned)n_blocks), dim3(256), 0, st, pred_box, pred_off, gt_box, gt_off, group_bd,

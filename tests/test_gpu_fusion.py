@@ -144,10 +144,11 @@ def test_integration_md_fusion_binding_runs_as_written(oracle):
 
 def test_bev_match_ties_and_kernel_boundaries(oracle):
     """Tie-heavy samples (duplicated boxes: many equal weights, many equally good assignments) at the sizes where the
-    solver changes kernels (64 / 128 boxes per side): the three device kernels and the oracle must take the same steps."""
+    solver changes instance (64 / 128 / 256 boxes on the larger side): every instance and the oracle must take the same steps."""
     rng = np.random.default_rng(33)
     preds, gts = [], []
-    for P, G in [(63, 64), (64, 64), (65, 64), (64, 65), (127, 128), (128, 128), (129, 128), (128, 129), (40, 200), (200, 40), (130, 131)]:
+    for P, G in [(63, 64), (64, 64), (65, 64), (64, 65), (127, 128), (128, 128), (129, 128), (128, 129), (40, 200), (200, 40), (130, 131),
+                 (255, 256), (256, 256), (257, 256), (256, 257), (300, 255)]:
         base = _rand_boxes(rng, 12, (100.0, -50.0), 8.0)
         p = base[rng.integers(0, 12, P)].copy()
         g = base[rng.integers(0, 12, G)].copy()

@@ -68,15 +68,27 @@ def test_two_runs_bit_identical(random_2000):
 
 
 def test_large_groups_match_host():
+    """One type, 200 and 600 boxes in a frame, then the sizes at which k_wm_match changes instance (64 / 128 / 256 columns).
+    The weights are jittered and generic: under exact ties the number of positive pairs of a maximum-weight assignment is
+    not unique and scipy's choice need not be the device's (ties are pinned by the G11 goldens)."""
     rng = np.random.default_rng(5)
-    P, G = [], []
-    for ts, n in ((1, 200), (2, 600)):                                      # one type, 200 and 600 boxes in a frame
+    boundary = (64, 65, 128, 129, 256, 257)
+    frames = []
+    for ts, n in enumerate((200, 600) + boundary, start=1):
         c = rng.uniform(-40, 40, (n, 2))
+        P, G = [], []
         for i in range(n):
             G.append(we.encode_gt_object([c[i, 0], c[i, 1], 0.0], 4.5, 2.0, 1.6, 0.0, 1, "x", ts, 50))
             P.append(wm.encode_object([c[i, 0] + rng.normal(0, 0.2), c[i, 1] + rng.normal(0, 0.2), 0.0], 4.5, 2.0, 1.6,
                                       rng.normal(0, 0.2), 1, float(rng.uniform()), "x", ts))
+        frames.append((n, P, G))
+    for n, P, G in frames:                                                   # host only: no boundary group matches emptily
+        if n in boundary:
+            tp = we.counts_host(we.pack(we.decode_objects(wm.encode_objects(P)), we.decode_objects(wm.encode_objects(G))))[0][0, 0, 0]
+            assert 2 * tp >= n, f"group of {n}: {tp} true positives at cutoff 0"
+    P, G = sum((f[1] for f in frames), []), sum((f[2] for f in frames), [])
     packed = we.pack(we.decode_objects(wm.encode_objects(P)), we.decode_objects(wm.encode_objects(G)))
+    assert set(boundary) <= set(np.diff(packed["gt_off"]).tolist()) and set(boundary) <= set(np.diff(packed["pred_off"]).tolist())
     counts, hsum = ops.waymo_metrics(packed)
     hc, hh = we.counts_host(packed)
     assert np.array_equal(counts, hc) and np.array_equal(hsum, hh)
