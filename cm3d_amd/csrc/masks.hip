@@ -726,7 +726,7 @@ extern "C" int cm3d_rle_to_dense(const uint32_t *rle_counts, const int32_t *rle_
                                  cm3d_stream_t stream)
 {
     if (!rle_counts || !rle_off || !dense || !workspace) return CM3D_ERR_ARG;
-    if (n_masks <= 0 || total_runs <= 0 || n_masks > total_runs || W <= 0 || H <= 0 || (int64_t)W * H >= (1ll << 31)) return CM3D_ERR_ARG;
+    if (n_masks <= 0 || total_runs <= 0 || n_masks > total_runs || W <= 0 || H <= 0 || W > 32 * EP_MAX_WP || (int64_t)W * H >= (1ll << 31)) return CM3D_ERR_ARG;
     if (workspace_bytes < cm3d_rle_workspace_bytes(total_runs)) return CM3D_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     uint32_t *ends = (uint32_t *)workspace;

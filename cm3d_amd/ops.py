@@ -72,14 +72,16 @@ def erode(dense_masks):
     return packed, bbox
 
 
-def erode_rle(rle_counts_list, W, H):
-    """Same result as erode(decode(.)) straight from run lengths (f1)."""
+def erode_rle(rle_counts_list, W, H, fill=0, guard_slots=0):
+    """Same result as erode(decode(.)) straight from run lengths (f1).  `packed` holds `fill` (a 32-bit pattern) in every word
+    before the call and has `guard_slots` more slots than masks: tests of what the kernels leave unwritten set both."""
     L = _lib.lib()
     off = np.concatenate([[0], np.cumsum([len(c) for c in rle_counts_list])]).astype(np.int32)
     allc = np.concatenate([np.asarray(c, np.uint32) for c in rle_counts_list]).astype(np.uint32)
     n = len(rle_counts_list)
     d_c, d_o = _t(allc.view(np.int32)), _t(off)
-    packed = torch.zeros(n, H, (W + 31) // 32, dtype=torch.int32, device=_dev())
+    fill = int(np.array(fill & 0xFFFFFFFF, np.uint32).view(np.int32))
+    packed = torch.full((n + guard_slots, H, (W + 31) // 32), fill, dtype=torch.int32, device=_dev())
     bbox = _e(n, _lib.BBOX_STRIDE)
     ws = _ws(L.cm3d_rle_workspace_bytes(allc.size))
     check(L.cm3d_rle_erode_pack(d_c.data_ptr(), d_o.data_ptr(), n, allc.size, W, H, packed.data_ptr(), bbox.data_ptr(),

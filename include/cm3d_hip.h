@@ -108,6 +108,7 @@ int cm3d_sweep_prep(const float *raw, int32_t raw_stride, const float *intensity
  * lengths -> dense uint8 [n][H][W] image-layout masks of 0/1.
  *  rle_counts uint32[]  run lengths of all masks back to back (alternating 0-run,1-run,...)
  *  rle_off    int32[n+1]
+ *  W          1 .. 4096, like the erosion behind it (CM3D_ERR_ARG otherwise)
  *  workspace: cm3d_rle_workspace_bytes(total_runs) */
 int64_t cm3d_rle_workspace_bytes(int32_t total_runs);
 int cm3d_rle_to_dense(const uint32_t *rle_counts, const int32_t *rle_off, int32_t n_masks, int32_t total_runs,
@@ -122,8 +123,12 @@ int cm3d_rle_to_dense(const uint32_t *rle_counts, const int32_t *rle_off, int32_
  *          RECTANGLE of whole words (ABI v3): word columns xw0 .. xw0+wc-1, image rows y0 .. y0+rows-1, row after row from the start
  *          of the slot, wc words each: bit (x&31) of slot word (y - y0) * wc + (x>>5) - xw0 = eroded pixel (x,y).  cm3d_erode_pack
  *          stores the whole image (xw0 = y0 = 0, wc = Wp, rows = H: the layout of ABI v2); cm3d_rle_erode_pack the rectangle of the
- *          mask's set pixels, so that a mask's words are contiguous in memory.  Words outside the rectangle are unspecified, and
- *          n*H*Wp must stay below 2^31 (mask offsets are signed 32-bit word numbers).
+ *          mask's set pixels, so that a mask's words are contiguous in memory.  Words of `packed` outside the stored rectangles are
+ *          NEVER WRITTEN: the slot words behind a rectangle's rows * wc, the whole slot of a mask without a set pixel and whatever
+ *          lies behind the last slot keep what they held before the call (when cm3d_rle_erode_pack takes its workgroup-per-mask form
+ *          -- lists that average more than 1024 runs -- it reports the whole image as the stored rectangle, writes only the words of
+ *          the set pixels' rectangle, at the image's row stride, and leaves the others as they were; the eroded bounds bbox[0..3] lie
+ *          inside what was written).  n*H*Wp must stay below 2^31 (mask offsets are signed 32-bit word numbers).
  *  bbox    int32[n][CM3D_BBOX_STRIDE] OUT: [0..3] x0,y0,x1,y1 inclusive bounds of the eroded mask (x0>x1 when empty),
  *          [4..7] xw0, y0, wc, rows of the stored rectangle (all 0 for a mask without a set pixel) */
 int cm3d_erode_pack(const uint8_t *dense, int32_t n_masks, int32_t W, int32_t H, uint32_t *packed,
