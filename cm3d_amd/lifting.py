@@ -125,6 +125,8 @@ class HostBatch:
     pose_rt: Optional[np.ndarray] = None      # (F,12) float32, Waymo: vehicle -> global rotate/translate
     pose_inv: Optional[np.ndarray] = None     # (F,16) float32, Waymo: inverse of the float32 frame pose
     ego_box: bool = True                      # nuScenes drops the ego-box points (:442-445); Waymo does not
+    mask_wh: Optional[np.ndarray] = None      # (n_masks, 2) int32 own (w, h) of every mask when they differ (Waymo's side cameras,
+                                              # src/waymo/2d_to_3d.py:520-521); None: every mask has the canvas size (width, height)
 
     @property
     def n_frames(self):
@@ -192,12 +194,19 @@ def default_layout():
 def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane: Sequence[int],
                 classes: Optional[ClassTable] = None, layout: Optional[str] = None, keep_intensity: bool = True) -> HostBatch:
     """frames: objects with the attributes of cm3d_amd.synthetic.Frame.  layout: "rows" (the sweeps as they are) or
-    "quads" (rows_to_quads); None = default_layout()."""
+    "quads" (rows_to_quads); None = default_layout().
+    The masks of a batch may have different image sizes (Waymo's front and side cameras inside one frame, KITTI's frames among each
+    other): the batch's `width`, `height` are the CANVAS -- the elementwise maximum over the frames' and the masks' sizes --, every run
+    list stays as the producer wrote it, and `mask_wh` lists the masks' own sizes (None when they all have the canvas size)."""
     classes = classes or ClassTable.nuscenes()
     layout = layout or default_layout()
     if layout not in ("rows", "quads"):
         raise ValueError(layout)
-    W, H = frames[0].width, frames[0].height
+    W = max([int(fr.width) for fr in frames] + [int(rl["size"][0]) for fr in frames for rl in fr.rles])
+    H = max([int(fr.height) for fr in frames] + [int(rl["size"][1]) for fr in frames for rl in fr.rles])
+    if W > 4096:
+        raise ValueError(f"masks of {W} columns: the mask kernels hold rows of up to 4096 pixels")
+    mask_wh = []
     n_cams = frames[0].cams.shape[0]
     raws, xfs, row_off, fso = [], [], [0], [0]
     cams, mask_off, mask_cam, mask_frame = [], [0], [], []
@@ -205,8 +214,8 @@ def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane:
     pose_rt, pose_inv = [], []
     stride = frames[0].sweeps_raw[0].shape[1]
     for fi, fr in enumerate(frames):
-        if fr.width != W or fr.height != H or fr.cams.shape[0] != n_cams:
-            raise ValueError("all frames of a batch must share mask size and camera count")
+        if fr.cams.shape[0] != n_cams:
+            raise ValueError("all frames of a batch must share the camera count")
         for r in fr.sweeps_raw:
             r = np.ascontiguousarray(r, np.float32)
             if r.shape[1] != stride:
@@ -220,11 +229,13 @@ def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane:
         if not (len(fr.labels) == len(fr.scores) == len(fr.cam_nums) == n):
             raise ValueError("labels / detection_scores / cam_nums / masks differ in length")
         for rl in fr.rles:
-            if list(rl["size"]) != [W, H]:
-                raise ValueError(f"mask size {rl['size']} != [{W},{H}]")
+            w, h = (int(v) for v in rl["size"])
+            if w < 1 or h < 1:
+                raise ValueError(f"mask size {rl['size']}")
             c = rlemod.string_to_counts(rl["counts"]) if isinstance(rl["counts"], (bytes, bytearray)) else np.asarray(rl["counts"], np.uint32)
-            if int(c.astype(np.int64).sum()) != W * H:
+            if int(c.astype(np.int64).sum()) != w * h:
                 raise ValueError("RLE run lengths do not cover the mask")
+            mask_wh.append((w, h))
             cnts.append(c)
             rle_off.append(rle_off[-1] + c.size)
         mask_off.append(mask_off[-1] + n)
@@ -253,7 +264,11 @@ def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane:
     if layout == "quads":
         raw, intensity, row_off, frame_rows = rows_to_quads(raw, row_off, fso, keep_intensity)
         stride = _lib.RAW_QUADS
+    mask_wh = i32(mask_wh).reshape(-1, 2)
+    if bool(np.all(mask_wh == np.array([W, H], np.int32))):
+        mask_wh = None
     return HostBatch(
+        mask_wh=mask_wh,
         raw=raw, raw_stride=stride, intensity=intensity, frame_rows=frame_rows,
         sweep_row_off=row_off, sweep_xf=np.concatenate(xfs, 0), frame_sweep_off=i32(fso),
         max_rows_per_sweep=max(1, int(np.diff(row_off).max())) if len(row_off) > 1 else 1, cams=np.stack(cams), n_cams=n_cams,
@@ -265,6 +280,13 @@ def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane:
         pose_rt=np.stack(pose_rt).astype(np.float32) if len(pose_rt) == len(frames) and frames else None,
         pose_inv=np.stack(pose_inv).astype(np.float32) if len(pose_inv) == len(frames) and frames else None,
         ego_box=not ((len(pose_rt) == len(frames) and len(frames) > 0) or all(getattr(f, "no_ego_box", False) for f in frames)))
+
+
+def require_one_mask_size(hb: HostBatch):
+    """The dense-mask route (decode_masks_dense, cm3d_erode_pack, `--masks dense`) takes one image size per batch."""
+    if hb.mask_wh is not None:
+        raise ValueError(f"masks of different image sizes in one batch (canvas {hb.width}x{hb.height}): the dense-mask route takes one size "
+                         "per batch; use masks=\"rle\"")
 
 
 def pack_manifest(man, lane_tables, frame_lane, classes: Optional[ClassTable], rd, stride=5, alloc=None):
@@ -410,6 +432,12 @@ class LiftEngine:
         b.frame_sweep_off = t(hb.frame_sweep_off)
         b.cams = t(hb.cams); b.mask_off = t(hb.mask_off); b.mask_cam = t(hb.mask_cam); b.mask_frame = t(hb.mask_frame)
         b.rle_off = t(hb.rle_off)
+        # own (w, h) of every mask where they differ: set on every upload, so that a slot never carries the table of its last batch
+        if hb.mask_wh is not None and np.asarray(hb.mask_wh).shape != (M, 2):
+            raise ValueError("mask_wh: one (w, h) per mask")
+        b.mask_wh = t(np.asarray(hb.mask_wh, np.int32)) if hb.mask_wh is not None else None
+        if dense_masks is not None:
+            require_one_mask_size(hb)
         b.class_id = t(hb.class_id); b.score = t(hb.score)
         b.pose_rt = t(hb.pose_rt) if hb.pose_rt is not None else None
         b.pose_inv = t(hb.pose_inv) if hb.pose_inv is not None else None
@@ -496,6 +524,7 @@ class LiftEngine:
     def decode_masks_dense(self):
         """a1: RLE -> dense uint8 (M,H,W) on the device (pycocotools.mask.decode, reference :425)."""
         b = self.b
+        require_one_mask_size(b.hb)
         if b.dense is None:
             b.dense = torch.empty(b.M, b.H, b.W, dtype=torch.uint8, device=self.dev)
         st = torch.cuda.current_stream(self.dev).cuda_stream
@@ -545,15 +574,26 @@ class LiftEngine:
         if reset:
             if masks != "rle":
                 raise ValueError("the per-pass reset rides on the run-length mask launch only")
+            if b.mask_wh is not None:
+                check(self.lib.cm3d_rle_erode_pack_sized_begin(_ptr(b.rle_counts), _ptr(b.rle_off), b.M, b.hb.rle_counts.size, b.W, b.H,
+                                                               _ptr(b.mask_wh), _ptr(b.packed), _ptr(b.bbox), _ptr(b.rle_ws), b.rle_ws_bytes,
+                                                               _ptr(b.status), _ptr(b.hit_count), b.M, _ptr(b.removed_bits), b.removed_words, st),
+                      "cm3d_rle_erode_pack_sized_begin")
+                return
             check(self.lib.cm3d_rle_erode_pack_begin(_ptr(b.rle_counts), _ptr(b.rle_off), b.M, b.hb.rle_counts.size, b.W, b.H,
                                                      _ptr(b.packed), _ptr(b.bbox), _ptr(b.rle_ws), b.rle_ws_bytes,
                                                      _ptr(b.status), _ptr(b.hit_count), b.M, _ptr(b.removed_bits), b.removed_words, st),
                   "cm3d_rle_erode_pack_begin")
             return
         if masks == "dense":
+            require_one_mask_size(b.hb)
             if b.dense is None:
                 raise Cm3dError("dense masks requested but not resident: call decode_masks_dense() or pass dense_masks")
             check(self.lib.cm3d_erode_pack(_ptr(b.dense), b.M, b.W, b.H, _ptr(b.packed), _ptr(b.bbox), st), "cm3d_erode_pack")
+        elif masks == "rle" and b.mask_wh is not None:
+            check(self.lib.cm3d_rle_erode_pack_sized(_ptr(b.rle_counts), _ptr(b.rle_off), b.M, b.hb.rle_counts.size, b.W, b.H, _ptr(b.mask_wh),
+                                                     _ptr(b.packed), _ptr(b.bbox), _ptr(b.rle_ws), b.rle_ws_bytes, st),
+                  "cm3d_rle_erode_pack_sized")
         elif masks == "rle":
             check(self.lib.cm3d_rle_erode_pack(_ptr(b.rle_counts), _ptr(b.rle_off), b.M, b.hb.rle_counts.size, b.W, b.H,
                                                _ptr(b.packed), _ptr(b.bbox), _ptr(b.rle_ws), b.rle_ws_bytes, st),

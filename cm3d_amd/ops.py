@@ -72,9 +72,11 @@ def erode(dense_masks):
     return packed, bbox
 
 
-def erode_rle(rle_counts_list, W, H, fill=0, guard_slots=0):
+def erode_rle(rle_counts_list, W, H, fill=0, guard_slots=0, sizes=None):
     """Same result as erode(decode(.)) straight from run lengths (f1).  `packed` holds `fill` (a 32-bit pattern) in every word
-    before the call and has `guard_slots` more slots than masks: tests of what the kernels leave unwritten set both."""
+    before the call and has `guard_slots` more slots than masks: tests of what the kernels leave unwritten set both.
+    sizes: a list of (w, h), one per mask -- run list k then covers its own w x h image and (W, H) is the canvas it is pasted into,
+    top-left (cm3d_rle_erode_pack_sized, rule R of include/cm3d_hip.h); None: every list covers W x H."""
     L = _lib.lib()
     off = np.concatenate([[0], np.cumsum([len(c) for c in rle_counts_list])]).astype(np.int32)
     allc = np.concatenate([np.asarray(c, np.uint32) for c in rle_counts_list]).astype(np.uint32)
@@ -84,6 +86,14 @@ def erode_rle(rle_counts_list, W, H, fill=0, guard_slots=0):
     packed = torch.full((n + guard_slots, H, (W + 31) // 32), fill, dtype=torch.int32, device=_dev())
     bbox = _e(n, _lib.BBOX_STRIDE)
     ws = _ws(L.cm3d_rle_workspace_bytes(allc.size))
+    if sizes is not None:
+        wh = np.ascontiguousarray(sizes, np.int32).reshape(-1, 2)
+        if wh.shape[0] != n:
+            raise ValueError("erode_rle: one (w, h) per mask")
+        d_wh = _t(wh)
+        check(L.cm3d_rle_erode_pack_sized(d_c.data_ptr(), d_o.data_ptr(), n, allc.size, W, H, d_wh.data_ptr(), packed.data_ptr(),
+                                          bbox.data_ptr(), ws.data_ptr(), ws.numel(), _st()), "cm3d_rle_erode_pack_sized")
+        return packed, bbox
     check(L.cm3d_rle_erode_pack(d_c.data_ptr(), d_o.data_ptr(), n, allc.size, W, H, packed.data_ptr(), bbox.data_ptr(),
                                 ws.data_ptr(), ws.numel(), _st()), "cm3d_rle_erode_pack")
     return packed, bbox

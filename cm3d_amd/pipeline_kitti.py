@@ -56,18 +56,15 @@ def main(argv=None):
             frames.append(kt.frame_from_files(fnum, os.path.join(tr, "velodyne", f"{fnum:06d}.bin"),
                                               os.path.join(tr, "calib", f"{fnum:06d}.txt"), rles, data["labels"],
                                               data["detection_scores"], args.ratio))
-        by_size = {}
-        for f in frames:
-            by_size.setdefault((f.width, f.height), []).append(f)
-        for _, fs in sorted(by_size.items()):
-            hb = lifting.pack_frames(fs, [lane], [0] * len(fs), classes)
+        if frames:         # KITTI's images come in several sizes: they share the batch (lifting.pack_frames)
+            hb = lifting.pack_frames(frames, [lane], [0] * len(frames), classes)
             eng.upload(hb)
             eng.run(masks="rle")
             torch.cuda.synchronize()
             res = eng.download(full=not device_obb)          # device fit: no in-mask points to copy back
             if device_obb and (res["obb_status"] == kt.OBB_OVERFLOW).any():
                 res = eng.download(full=True)                 # ... unless the device could not fit a mask: the host fits that one
-            for i, f in enumerate(fs):
+            for i, f in enumerate(frames):
                 pred, pseudo = kt.labels_of_frame(hb, res, i, classes, pri, obb=args.obb)
                 with open(os.path.join(pred_dir, f"{f.token}.txt"), "a") as fh:
                     fh.writelines(pred)

@@ -62,7 +62,8 @@ def load_scene(frames_dir, mask_dir, scene, tfrecord=None):
             data = json.load(f)
         if not rles:
             continue
-        W, H = rles[0]["size"]
+        # the frame's largest image: FRONT* and SIDE* images differ in height, and the producer thumbnails each on its own (:520-521)
+        W, H = max(int(r["size"][0]) for r in rles), max(int(r["size"][1]) for r in rles)
         cams = [(z["extrinsics"][c], z["intrinsics"][c]) for c in range(z["extrinsics"].shape[0])]
         frames.append(wm.frame_from_extracted(f"{scene}:{fnum}", z["points"], cams, rles, data["labels"], data["detection_scores"],
                                               data["cam_nums"], z["pose"], W, H, int(z["timestamp_micros"]), str(z["context_name"])))
@@ -70,23 +71,20 @@ def load_scene(frames_dir, mask_dir, scene, tfrecord=None):
 
 
 def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0):
-    """One scene through the hot path; returns its kept-box records as device tensors (lifting.kept_box_records with
-    column 5 = scene_index, column 6 = the frame's number inside the scene), one tensor per image size."""
-    recs = []
-    by_size = {}
-    for f in frames:
-        by_size.setdefault((f.width, f.height), []).append(f)     # Waymo has two image sizes (:520-523)
-    for _, fs in sorted(by_size.items()):
-        hb = lifting.pack_frames(fs, [lane_table], [0] * len(fs), classes)
-        eng.upload(hb)
-        if masks == "dense":
-            eng.decode_masks_dense()
-        eng.run(masks=masks)
-        torch.cuda.synchronize()
-        eng.check_status()
-        ids = np.array([[scene_index, int(f.token.rsplit(":", 1)[1])] for f in fs], np.float64)
-        recs.append(lifting.kept_box_records(eng.b, ids))
-    return recs
+    """One scene through the hot path, its frames in one batch; returns its kept-box records as a list of device tensors
+    (lifting.kept_box_records with column 5 = scene_index, column 6 = the frame's number inside the scene).  Masks of different image
+    sizes -- Waymo's side cameras, inside every frame -- share the batch (lifting.pack_frames)."""
+    hb = lifting.pack_frames(frames, [lane_table], [0] * len(frames), classes)
+    if masks == "dense":
+        lifting.require_one_mask_size(hb)
+    eng.upload(hb)
+    if masks == "dense":
+        eng.decode_masks_dense()
+    eng.run(masks=masks)
+    torch.cuda.synchronize()
+    eng.check_status()
+    ids = np.array([[scene_index, int(f.token.rsplit(":", 1)[1])] for f in frames], np.float64)
+    return [lifting.kept_box_records(eng.b, ids)]
 
 
 def objects_from_records(rec, scenes, frames_dir, classes, meta=None):

@@ -149,6 +149,31 @@ int cm3d_rle_erode_pack_begin(const uint32_t *rle_counts, const int32_t *rle_off
                               int32_t *status, int32_t *hit_count, int32_t n_count_masks, uint32_t *removed_bits, int64_t removed_words,
                               cm3d_stream_t stream);
 
+/* f1 for batches whose masks have DIFFERENT IMAGE SIZES (Waymo: 1920x1280 and 1920x886 images in one frame, thumbnailed per image
+ * by the mask producer; the reference decodes every mask at its own size, src/waymo/2d_to_3d.py:520-521, and tests points against
+ * that mask's own shape, :600-606).  W, H is the batch's CANVAS -- the elementwise maximum of the masks' sizes -- and what every
+ * later stage (cm3d_project_hits, ...) is called with; mask m's run list covers its own image of (w, h) = mask_wh[m].
+ *  mask_wh  int32[n][2]  w, h of each mask's own image, 1 <= w <= W, 1 <= h <= H (values outside are clamped into that range on
+ *           the device: no table content moves a write outside the mask's slot).  A run list that overruns w*h is cut off at
+ *           row h-1, like cm3d_rle_erode_pack cuts one at H-1.
+ * RULE R: the result is what cm3d_rle_erode_pack stores for the mask pasted top-left into a W x H canvas of zeros -- pixels
+ * outside w x h but inside the canvas are zeros, pixels outside the canvas are ignored as before.  The in-mask lists that follow
+ * equal the reference's: it can only hit pixels 1 <= floor(u) <= w-2, 1 <= floor(v) <= h-2 (its in-image test and its
+ * floor != 0 quirk), whose 3x3 neighbourhoods lie inside the mask's own image, so that its border rule and the canvas's never
+ * differ there; and where w < W the canvas's column w-1 has zero neighbours and erodes to zero (rows h-1 likewise), so that
+ * nothing the canvas-sized in-image test admits beyond the reference's can be hit.
+ * `packed`, `bbox` and the never-written words are as described at cm3d_erode_pack, slots of H*Wp words of the CANVAS; argument
+ * checks as cm3d_rle_erode_pack's, for the canvas.  The run lists are read as the producer wrote them: nothing is re-encoded. */
+int cm3d_rle_erode_pack_sized(const uint32_t *rle_counts, const int32_t *rle_off, int32_t n_masks, int32_t total_runs,
+                              int32_t W, int32_t H, const int32_t *mask_wh, uint32_t *packed, int32_t *bbox, void *workspace,
+                              int64_t workspace_bytes, cm3d_stream_t stream);
+
+/* cm3d_rle_erode_pack_sized carrying the per-pass reset, as cm3d_rle_erode_pack_begin does for cm3d_rle_erode_pack. */
+int cm3d_rle_erode_pack_sized_begin(const uint32_t *rle_counts, const int32_t *rle_off, int32_t n_masks, int32_t total_runs,
+                                    int32_t W, int32_t H, const int32_t *mask_wh, uint32_t *packed, int32_t *bbox, void *workspace,
+                                    int64_t workspace_bytes, int32_t *status, int32_t *hit_count, int32_t n_count_masks,
+                                    uint32_t *removed_bits, int64_t removed_words, cm3d_stream_t stream);
+
 /* ---- a4-a7: projection + in-image + in-mask test ----------------------------
  * Replaces the per-mask block 2d_to_3d.py:553-613 (clone, 2x translate/rotate,
  * view_points, in-image test, floor, mask gather incl. the floor(u)!=0 && floor(v)!=0
