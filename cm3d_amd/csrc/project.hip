@@ -386,7 +386,10 @@ __global__ __launch_bounds__(64) void k_frame_tables(const PhSweepIn sw, int fus
         }
         const uint64_t okm = __ballot(ok);
         mg = cm3d_wave_max(mg);
-        zmin = -cm3d_wave_max(-zmin);        // the frame's smallest (the cameras' differ by 1e-4 of their distance from the origin)
+        // the frame's smallest (the cameras' differ by 1e-4 of their distance from the origin).  As a float: the int reduction this
+        // used to go through truncated it towards zero (2.105 -> 2, 0.11 -> 0: still below every camera's own, so no result ever
+        // depended on it, but not the bound wedge_setup derived)
+        zmin = cm3d_wave_reduce_t(zmin, [](float a, float b) { return fminf(a, b); });
         ft_margin = mg;
         if (lane == 0) { ft[FT_MARGIN] = mg; ft[FT_APXOK] = (int)(uint32_t)okm; ft[FT_ZMIN] = __float_as_int(zmin); }
     }
@@ -1341,6 +1344,36 @@ extern "C" int cm3d_project_hit_rows(const void *workspace, int64_t workspace_by
                 if (info[(size_t)f * nwc_max + c] < 0) rows += std::min(PH_WC, n - c * PH_WC);
         }
         *rows_out = rows;
+    } catch (...) { return CM3D_ERR_ARG; }
+    return CM3D_OK;
+}
+
+// Accounting aid (the tests of the culling; nothing on the path calls it): what k_frame_tables decided for every frame of the last
+// launch -- 8 words per frame: FT_APXOK, FT_CAMHAS, FT_MARGIN, FT_ZMIN (float bits), bit c = camera c's view wedge is a real
+// one (a non-zero normal: neither wedge_setup's "accept everything" nor the "nothing is inside" of a slot without a camera),
+// three zeros.  Synchronous: a host copy of the frame tables, like cm3d_project_hit_rows.
+extern "C" int cm3d_project_culling(const void *workspace, int64_t workspace_bytes, int32_t n_frames, int32_t max_pts_per_frame,
+                                    int32_t planes, int32_t *out, cm3d_stream_t stream)
+{
+    if (!workspace || !out || n_frames <= 0 || max_pts_per_frame <= 0 || planes <= 0) return CM3D_ERR_ARG;
+    if (workspace_bytes < cm3d_project_workspace_bytes(n_frames, max_pts_per_frame, planes) || ((uintptr_t)workspace & 15)) return CM3D_ERR_WORKSPACE;
+    try {
+        PhWs ws;
+        ph_ws_layout(n_frames, max_pts_per_frame, planes, const_cast<void *>(workspace), &ws);
+        std::vector<int32_t> ft((size_t)n_frames * FT_WORDS);
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return CM3D_ERR_LAUNCH;
+        if (hipMemcpy(ft.data(), ws.ft, ft.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return CM3D_ERR_LAUNCH;
+        for (int f = 0; f < n_frames; ++f) {
+            const int32_t *t = ft.data() + (size_t)f * FT_WORDS;
+            int32_t *o = out + (size_t)f * 8;
+            int32_t wedges = 0;
+            for (int c = 0; c < CM3D_MAX_CAMS; ++c) {
+                const int32_t *w = t + FT_WEDGE + 8 * c;             // float bits: +-0 has no bit below the sign
+                if ((w[0] | w[1] | w[2] | w[4] | w[5] | w[6]) & 0x7FFFFFFF) wedges |= 1 << c;
+            }
+            o[0] = t[FT_APXOK]; o[1] = t[FT_CAMHAS]; o[2] = t[FT_MARGIN]; o[3] = t[FT_ZMIN]; o[4] = wedges;
+            o[5] = o[6] = o[7] = 0;
+        }
     } catch (...) { return CM3D_ERR_ARG; }
     return CM3D_OK;
 }

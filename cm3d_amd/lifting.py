@@ -754,6 +754,17 @@ class LiftEngine:
                                              torch.cuda.current_stream(self.dev).cuda_stream), "cm3d_project_hit_rows")
         return int(out.value)
 
+    def culling(self):
+        """What the projection's per-frame tables decided for the resident batch in the last pass (cm3d_project_culling; an aid of
+        the tests, synchronises the stream): dict of per-frame arrays -- `apx_ok`, `cam_has`, `wedge` (bit c = camera c), `margin_px`,
+        `zmin` (float32)."""
+        b = self.b
+        out = np.zeros((b.F, 8), np.int32)
+        check(self.lib.cm3d_project_culling(_ptr(b.pg_ws), b.pg_ws_bytes, b.F, b.max_pts, b.planes, out.ctypes.data,
+                                            torch.cuda.current_stream(self.dev).cuda_stream), "cm3d_project_culling")
+        return dict(apx_ok=out[:, 0].copy(), cam_has=out[:, 1].copy(), margin_px=out[:, 2].copy(),
+                    zmin=out[:, 3].copy().view(np.float32), wedge=out[:, 4].copy())
+
     # -- results
     def check_status(self):
         s = self.b.status.cpu().numpy()

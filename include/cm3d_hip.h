@@ -199,6 +199,14 @@ int64_t cm3d_project_workspace_bytes(int32_t n_frames, int32_t max_pts_per_frame
  * 256 rows with at least one in-mask point, read back from the workspace of the last cm3d_(sweep_)project_hits on `stream`. */
 int cm3d_project_hit_rows(const void *workspace, int64_t workspace_bytes, int32_t n_frames, int32_t max_pts_per_frame,
                           int32_t planes, int64_t *rows_out, cm3d_stream_t stream);
+/* Accounting aid for the tests of the per-camera culling (nothing on the path calls it; synchronous): what the per-frame table
+ * kernel of the last cm3d_(sweep_)project_hits on `stream` decided, read back from the workspace.
+ *  out  int32[n_frames][8]: [0] bit c = camera c has an approximate projection, [1] bit c = camera c has a non-empty mask,
+ *       [2] the frame's pixel margin (largest of its cameras'), [3] the smallest depth the approximate projection may accept
+ *       (float bits; smallest of the cameras'), [4] bit c = camera c has a view wedge (0: every point is projected exactly),
+ *       [5..7] zero. */
+int cm3d_project_culling(const void *workspace, int64_t workspace_bytes, int32_t n_frames, int32_t max_pts_per_frame,
+                         int32_t planes, int32_t *out, cm3d_stream_t stream);
 int cm3d_project_hits(const float *points, const int32_t *pt_off, int32_t n_frames, int32_t max_pts_per_frame,
                       int32_t n_points_total, const float *cams, int32_t n_cams, const int32_t *mask_off,
                       const int32_t *mask_cam, const int32_t *bbox, const uint32_t *packed, int32_t n_masks,

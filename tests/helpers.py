@@ -3,19 +3,25 @@ reference's execution order and return arrays shaped like LiftEngine.download().
 import numpy as np
 
 
-def oracle_batch(orc, frames, lane_tables, frame_lane, hb):
+def oracle_batch(orc, frames, lane_tables, frame_lane, hb, min_dist=None, halfw=None):
+    """min_dist (default: the reference's 2.3): the projection's depth limit; the ego box then has LiftEngine's half width
+    f32(sqrt(min_dist)) unless `halfw` says otherwise."""
+    if halfw is None:
+        halfw = orc.EGO_HALFW_F32 if min_dist is None else np.float32(np.sqrt(min_dist))
+    min_dist = orc.MIN_DIST_F32 if min_dist is None else np.float32(min_dist)
+    box_halfw = np.float32(halfw)
     pts_all, pt_off = [], [0]
     hit_idx, hit_off = [], [0]
     medoid_pos, centroid = [], []
     lane_idx, lane_dist, box, flags, bbox = [], [], [], [], []
     for fi, fr in enumerate(frames):
-        halfw = orc.EGO_HALFW_F32 if hb.ego_box else np.float32(0.0)
+        halfw = box_halfw if hb.ego_box else np.float32(0.0)
         pts = np.concatenate([orc.sweep_prep(r, x[0:9], x[9:12], x[12:21], x[21:24], halfw)
                               for r, x in zip(fr.sweeps_raw, fr.sweep_xf)], 0)
         pts_all.append(pts)
         pt_off.append(pt_off[-1] + pts.shape[0])
         masks = [orc.rle_decode(r).T for r in fr.rles]     # (H,W) image layout, like depth_images[i]
-        idx_lists, med, cent = orc.lift_frame_reference_order(pts, fr.cams, masks, fr.cam_nums)
+        idx_lists, med, cent = orc.lift_frame_reference_order(pts, fr.cams, masks, fr.cam_nums, min_dist)
         for m in masks:
             er = orc.erode3x3(m)
             ys, xs = np.nonzero(er)
