@@ -293,24 +293,104 @@ def _cutoff_counts(scores_desc):
     return np.searchsorted(-scores_desc.astype(np.float32), -CUTOFFS, side="right")
 
 
-def counts_host(packed):
+_PAIR_CHUNK = 1 << 15          # pairs per vectorised iou3d call of pair_weights
+_SMALL_PAIRS = 4               # counts_host: groups with one box on a side and at most this many pairs skip scipy
+
+
+def pair_weights(packed):
+    """Integer weights of all pairs of all groups, as k_wm_weights writes them: group g's (P, G) matrix is
+    w[pair_off[g]:pair_off[g + 1]], row-major.  Returns (w int64, pair_off).  A pair of equal boxes is clipped once: every
+    pair of a range shard is also a pair of its type's shard 0."""
+    po, go = packed["pred_off"], packed["gt_off"]
+    P, G = np.diff(po), np.diff(go)
+    pair_off = np.concatenate([[0], np.cumsum(P * G)]).astype(np.int64)
+    w = np.zeros(int(pair_off[-1]), np.int64)
+    thr_of = np.array([IOU_THR[bd // 4 + 1] for bd in range(N_BREAKDOWNS)])
+    pid = np.unique(packed["pred_box"], axis=0, return_inverse=True)[1].reshape(-1).astype(np.int64)
+    gid = np.unique(packed["gt_box"], axis=0, return_inverse=True)[1].reshape(-1).astype(np.int64)
+    for lo in range(0, w.size, _PAIR_CHUNK):
+        q = np.arange(lo, min(lo + _PAIR_CHUNK, w.size))
+        g = np.searchsorted(pair_off, q, "right") - 1
+        loc = q - pair_off[g]
+        i, j = po[g] + loc // G[g], go[g] + loc % G[g]
+        _, first, inv = np.unique(pid[i] * (gid.size + 1) + gid[j], return_index=True, return_inverse=True)
+        iou = iou3d(packed["pred_box"][i[first]], packed["gt_box"][j[first]])[inv.reshape(-1)]
+        w[q] = np.where(iou >= thr_of[packed["group_bd"][g]], (iou * IOU_KMAX).astype(np.int64), 0)
+    return w, pair_off
+
+
+def _small_groups(packed, w_all, pair_off, counts, hsum):
+    """counts_host for the groups that need no assignment solver, all at once: a side empty, or one box on a side, at most
+    _SMALL_PAIRS pairs and a unique largest weight in every prefix of the rows (the optimum is then that one pair).
+    Adds to counts / hsum and returns the mask of the groups it took."""
+    po, go, bd = packed["pred_off"], packed["gt_off"], packed["group_bd"].astype(np.int64)
+    P, G = np.diff(po), np.diff(go)
+    n = P.size
+    # K[g, c]: predictions of group g with score >= cutoff c
+    adm = np.searchsorted(CUTOFFS, packed["pred_score"].astype(np.float32), "right")
+    K = np.zeros((n, N_CUTOFFS + 1), np.int32)
+    np.add.at(K, (np.repeat(np.arange(n), P), adm), 1)
+    K = (K[:, ::-1].cumsum(1)[:, ::-1])[:, 1:]
+    lvl1 = np.zeros(packed["gt_level"].size + 1, np.int64)
+    lvl1[1:] = np.cumsum(packed["gt_level"] == 1)
+    n1 = lvl1[go[1:]] - lvl1[go[:-1]]
+    taken = np.zeros(n, bool)
+
+    def add(sel, tp, hs, fn1, fn2):      # per group and k = 0..kmax: (m, kmax + 1) tables, looked up by K
+        k = K[sel].astype(np.int64)
+        t = np.take_along_axis(tp, k, 1)
+        rows = np.stack([t, k - t, np.take_along_axis(fn1, k, 1), np.take_along_axis(fn2, k, 1)], 2)
+        h = np.take_along_axis(hs, k, 1)
+        for b in np.unique(bd[sel]):
+            of = bd[sel] == b
+            counts[b] += rows[of].sum(0)
+            hsum[b] += h[of].sum(0)
+        taken[sel] = True
+    for p, g in sorted({(int(a), int(b_)) for a, b_ in zip(P, G)}):
+        sel = np.flatnonzero((P == p) & (G == g))
+        m = sel.size
+        z = np.zeros((m, p + 1), np.int64)
+        if p == 0 or g == 0:
+            add(sel, z, z, z + n1[sel][:, None], z + g)
+            continue
+        if min(p, g) > 1 or p * g > _SMALL_PAIRS:
+            continue
+        w = w_all[pair_off[sel][:, None] + np.arange(p * g)[None, :]]
+        tp, hs, fn1, fn2 = z.copy(), z.copy(), z + n1[sel][:, None], z + g
+        unique = np.ones(m, bool)
+        for k in range(1, p + 1):
+            sub = w[:, :k * g]
+            best = sub.max(1)
+            at = sub.argmax(1)
+            unique &= (best == 0) | ((sub == best[:, None]).sum(1) == 1)
+            hit = best > 0
+            r, c = po[sel] + at // g, go[sel] + at % g
+            tp[:, k] = hit
+            hs[:, k] = np.where(hit, heading_accuracy_fixed(packed["pred_head"][r], packed["gt_head"][c]), 0)
+            fn1[:, k] -= hit & (packed["gt_level"][c] == 1)
+            fn2[:, k] -= hit
+        add(sel[unique], tp[unique], hs[unique], fn1[unique], fn2[unique])
+    return taken
+
+
+def counts_host(packed, weights=None):
     """Host restatement of cm3d_waymo_metrics: counts int64[16][101][4] (TP, FP, FN L1, FN L2) and heading sums
-    int64[16][101] (fixed point).  Matching by scipy's linear_sum_assignment on the integer weights (max weight)."""
+    int64[16][101] (fixed point).  Matching by scipy's linear_sum_assignment on the integer weights (max weight); groups
+    whose optimum is a single pair with a unique largest weight are counted without it (_small_groups).  weights: the
+    result of pair_weights(packed), if the caller has it."""
     from scipy.optimize import linear_sum_assignment
     counts = np.zeros((N_BREAKDOWNS, N_CUTOFFS, 4), np.int64)
     hsum = np.zeros((N_BREAKDOWNS, N_CUTOFFS), np.int64)
     po, go = packed["pred_off"], packed["gt_off"]
-    for g in range(packed["group_bd"].size):
+    w_all, pair_off = weights if weights is not None else pair_weights(packed)
+    taken = _small_groups(packed, w_all, pair_off, counts, hsum)
+    for g in np.flatnonzero(~taken):
         bd = int(packed["group_bd"][g])
-        thr = IOU_THR[bd // 4 + 1]
         p0, p1, g0, g1 = int(po[g]), int(po[g + 1]), int(go[g]), int(go[g + 1])
         P, G = p1 - p0, g1 - g0
         lvl = packed["gt_level"][g0:g1]
         ks = _cutoff_counts(packed["pred_score"][p0:p1])
-        if P and G:
-            ii, jj = np.meshgrid(np.arange(P), np.arange(G), indexing="ij")
-            iou = iou3d(packed["pred_box"][p0 + ii.ravel()], packed["gt_box"][g0 + jj.ravel()]).reshape(P, G)
-            w = np.where(iou >= thr, (iou * IOU_KMAX).astype(np.int64), 0)
+        w = w_all[pair_off[g]:pair_off[g + 1]].reshape(P, G)
         for k in np.unique(ks):
             sel = ks == k
             tp, hs, fn1, fn2 = 0, 0, int(np.sum(lvl == 1)), G

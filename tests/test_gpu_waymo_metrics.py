@@ -70,7 +70,8 @@ def test_two_runs_bit_identical(random_2000):
 def test_large_groups_match_host():
     """One type, 200 and 600 boxes in a frame, then the sizes at which k_wm_match changes instance (64 / 128 / 256 columns).
     The weights are jittered and generic: under exact ties the number of positive pairs of a maximum-weight assignment is
-    not unique and scipy's choice need not be the device's (ties are pinned by the G11 goldens)."""
+    not unique and scipy's choice need not be the device's (the tie rule is pinned bit for bit against the oracle by the
+    `ties` family of tests/assign_cases.py, up to the widest instance, in tests/test_gpu_assign.py)."""
     rng = np.random.default_rng(5)
     boundary = (64, 65, 128, 129, 256, 257)
     frames = []
