@@ -25,6 +25,7 @@ OBB_ROT_STRIDE = 9       # doubles per mask of cm3d_obb's rot_opt (row-major 3x3
 WM_BOX_STRIDE = 8        # doubles per box of cm3d_waymo_metrics
 WM_BREAKDOWNS = 16
 WM_CUTOFFS = 101
+WM_SWEEP_MAX_ALPHAS = 1024   # alphas of one cm3d_waymo_metrics_sweep call
 RAW_QUADS = 3            # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -74,6 +75,8 @@ SIGNATURES = {
     "cm3d_selftest_obb_yaw": (_i32, [_p, _i32, _p, _p]),
     "cm3d_waymo_metrics_workspace_bytes": (_i64, [_i64]),
     "cm3d_waymo_metrics": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _i64, _p]),
+    "cm3d_waymo_metrics_sweep_workspace_bytes": (_i64, [_i64]),
+    "cm3d_waymo_metrics_sweep": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _p, _i32, _p, _p, _p, _p, _i64, _p]),
 }
 
 

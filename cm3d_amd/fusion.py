@@ -271,3 +271,85 @@ def waymo_grid_search(pred_objs, sam3d_objs, evaluate, out_path, best_path, iou=
             print(f"Best Score: {best_score}, Best Alpha: {best_alpha}")
             print("-" * 80)
     return best_alpha, best_score
+
+
+def waymo_candidates(pb, ps, sb, ss, pm, sm):
+    """Everything fuse_waymo can emit at some alpha, in the order it emits it: (objects, kind, p, s).  kind 0 an unmatched
+    prediction (score p), kind 1 an unmatched SAM3D box (score clip(s * alpha)), then per matched pair two neighbours of
+    which every alpha takes one: kind 2 the prediction's box (score p, taken unless s * alpha > p) and kind 3 the SAM3D box
+    under the prediction's type (score clip(s * alpha)).  The objects hold what a decode of the encoded fused file gives."""
+    objs, kind, p, s = [], [], [], []
+
+    def add(k, b, type_id, kd, p_score, s_score):
+        objs.append(dict(center=[float(b[0]), float(b[1]), float(b[2]) + float(b[5]) / 2], length=float(b[3]), width=float(b[4]),
+                         height=float(b[5]), heading=float(b[6]), type=type_id, context_name=k[0], timestamp_micros=k[1]))
+        kind.append(kd)
+        p.append(p_score)
+        s.append(s_score)
+    for k in pb:
+        matched = set(pm[k])
+        for i, b in enumerate(pb[k]):
+            if i not in matched:
+                add(k, b, ps[k][i]["type"], 0, ps[k][i]["score"], 0.0)
+    for k in sb:
+        matched = set(sm.get(k, []))
+        for i, b in enumerate(sb[k]):
+            if i not in matched:
+                add(k, b, ss[k][i]["type"], 1, 0.0, ss[k][i]["score"])
+    for k in pm:
+        for j, pid in enumerate(pm[k]):
+            sid = sm[k][j]
+            add(k, pb[k][pid], ps[k][pid]["type"], 2, ps[k][pid]["score"], ss[k][sid]["score"])
+            add(k, sb[k][sid], ps[k][pid]["type"], 3, ps[k][pid]["score"], ss[k][sid]["score"])
+    return objs, np.array(kind, np.int32), np.array(p, np.float64), np.array(s, np.float64)
+
+
+def waymo_grid_search_device(pred_objs, sam3d_objs, gt_objs, out_path, best_path, iou=0.2, verbose=True):
+    """waymo_grid_search with every alpha scored in one GPU call (cm3d_waymo_metrics_sweep) instead of a fused file per alpha:
+    match once, pack the candidate superset once, take each alpha's counts to the evaluator's 32 lines and their
+    Overall/L2 mAP, then encode two files only -- the best alpha's to best_path and the last alpha's to out_path, as the loop
+    leaves them.  gt_objs: decoded ground truth (waymo_eval.decode_objects).  Returns (best_alpha, best_score, scores).  A
+    group over the sweep's capacity falls back to waymo_grid_search with the per-alpha GPU evaluator."""
+    import sys
+
+    from . import _lib, waymo as wm, waymo_eval
+    sb, ss, s_max, s_min = waymo_parse(sam3d_objs, zero_min_quirk=True)
+    pb, ps, p_max, p_min = waymo_parse(pred_objs)
+    pm, sm = match_samples(pb, sb, iou)
+    alphas = waymo_alpha_grid(p_min, p_max, s_min, s_max)
+    if not alphas:
+        return 0, -1, []
+    packed = waymo_eval.pack_candidates(*waymo_candidates(pb, ps, sb, ss, pm, sm), gt_objs)
+    if packed["bad_type"]:
+        raise ValueError("waymo metrics: object of unknown type")
+    try:
+        counts, hsum = ops.waymo_metrics_sweep(packed, alphas)
+    except _lib.Cm3dError as e:
+        if getattr(e, "status", 0) != 1:
+            raise
+        print(f"waymo_grid_search_device: {e}; scoring alpha by alpha instead", file=sys.stderr)
+        scores = []
+
+        def evaluate(path):
+            scores.append(waymo_eval.evaluate(waymo_eval.read_objects(path), gt_objs)[0]["Overall/L2 mAP"])
+            return scores[-1]
+        return waymo_grid_search(pred_objs, sam3d_objs, evaluate, out_path, best_path, iou, verbose) + (scores,)
+    scores = []
+    best_alpha, best_score = 0, -1
+    for a, alpha in enumerate(alphas):
+        text = waymo_eval.format_metrics(waymo_eval.metrics_from_counts(counts[a], hsum[a]))
+        score = float(parse_waymo_metrics(text)[1])
+        scores.append(score)
+        if score > best_score:
+            best_score, best_alpha = score, alpha
+        if verbose:
+            print(f"Curr Score: {score},  Curr Alpha: {alpha}")
+            print(f"Best Score: {best_score}, Best Alpha: {best_alpha}")
+            print("-" * 80)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "wb") as f:
+        f.write(wm.encode_objects(fuse_waymo(pb, ps, sb, ss, pm, sm, alphas[-1])))
+    if best_score > -1:
+        with open(best_path, "wb") as f:
+            f.write(wm.encode_objects(fuse_waymo(pb, ps, sb, ss, pm, sm, best_alpha)))
+    return best_alpha, best_score, scores

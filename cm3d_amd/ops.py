@@ -407,3 +407,63 @@ def waymo_metrics(packed, per_cutoff=False):
         raise _lib.Cm3dError(f"cm3d_waymo_metrics: status {st} (bit0: more than {_lib.MAX_MATCH_BOXES} boxes of one type in a "
                              "frame, bit1: unknown breakdown)")
     return counts.cpu().numpy(), hsum.cpu().numpy()
+
+
+SWEEP_ALPHA_CHUNK = 256      # alphas per cm3d_waymo_metrics_sweep call: bounds the output (64 KiB an alpha)
+
+
+def waymo_metrics_sweep(packed_candidates, alphas, device_ms=None):
+    """Counts of the Waymo detection metrics for every alpha of the SAM3D fusion grid search (waymo_eval.pack_candidates),
+    SWEEP_ALPHA_CHUNK alphas per cm3d_waymo_metrics_sweep call.  Returns (counts int64[A][16][101][4], heading_sum
+    int64[A][16][101]).  Raises Cm3dError (its `status` attribute holds the status word) when a group is over capacity.
+    device_ms: a list that receives every call's device time in ms, measured with events (tools/waymo_sweep_rate.py)."""
+    L = _lib.lib()
+    pc = packed_candidates
+    alphas = np.ascontiguousarray(alphas, np.float64).reshape(-1)
+    A = int(alphas.size)
+    co, go = np.asarray(pc["cand_off"], np.int64), np.asarray(pc["gt_off"], np.int64)
+    n_groups = int(co.size - 1)
+    out_c = np.zeros((A, _lib.WM_BREAKDOWNS, _lib.WM_CUTOFFS, 4), np.int64)
+    out_h = np.zeros((A, _lib.WM_BREAKDOWNS, _lib.WM_CUTOFFS), np.int64)
+    if n_groups == 0 or A == 0:
+        return out_c, out_h
+    pair_off = np.concatenate([[0], np.cumsum(np.diff(co) * np.diff(go))]).astype(np.int64)
+    total = int(pair_off[-1])
+
+    def dev(a, dtype):
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape[0] == 0:
+            a = np.zeros((1,) + a.shape[1:], dtype)
+        return _t(a)
+    d_cb, d_ch, d_ck = dev(pc["cand_box"], np.float64), dev(pc["cand_head"], np.float32), dev(pc["cand_kind"], np.int32)
+    d_cp, d_cs = dev(pc["cand_p"], np.float64), dev(pc["cand_s"], np.float64)
+    d_gb, d_gh, d_gl = dev(pc["gt_box"], np.float64), dev(pc["gt_head"], np.float32), dev(pc["gt_level"], np.int32)
+    d_co, d_go = _t(co.astype(np.int32)), _t(go.astype(np.int32))
+    d_bd, d_pair, d_static = _t(np.asarray(pc["group_bd"], np.int32)), _t(pair_off), _t(np.asarray(pc["group_static"], np.int32))
+    ws = _ws(L.cm3d_waymo_metrics_sweep_workspace_bytes(total))
+    status = torch.zeros(1, dtype=torch.int32, device=_dev())
+    for lo in range(0, A, SWEEP_ALPHA_CHUNK):
+        n = min(SWEEP_ALPHA_CHUNK, A - lo)
+        d_al = _t(alphas[lo:lo + n])
+        counts = _e(n, _lib.WM_BREAKDOWNS, _lib.WM_CUTOFFS, 4, dtype=torch.int64)
+        hsum = _e(n, _lib.WM_BREAKDOWNS, _lib.WM_CUTOFFS, dtype=torch.int64)
+        if device_ms is not None:
+            ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev[0].record()
+        check(L.cm3d_waymo_metrics_sweep(d_cb.data_ptr(), d_ch.data_ptr(), d_ck.data_ptr(), d_cp.data_ptr(), d_cs.data_ptr(),
+                                         d_co.data_ptr(), d_gb.data_ptr(), d_gh.data_ptr(), d_gl.data_ptr(), d_go.data_ptr(),
+                                         d_bd.data_ptr(), d_pair.data_ptr(), d_static.data_ptr(), n_groups, total, d_al.data_ptr(), n,
+                                         counts.data_ptr(), hsum.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+              "cm3d_waymo_metrics_sweep")
+        if device_ms is not None:
+            ev[1].record()
+            ev[1].synchronize()
+            device_ms.append(ev[0].elapsed_time(ev[1]))
+        st = int(status.item())
+        if st:
+            err = _lib.Cm3dError(f"cm3d_waymo_metrics_sweep: status {st} (bit0: more than {_lib.MAX_MATCH_BOXES} candidates or ground-truth "
+                                 "boxes of one type in a frame, bit1: unknown breakdown)")
+            err.status = st
+            raise err
+        out_c[lo:lo + n], out_h[lo:lo + n] = counts.cpu().numpy(), hsum.cpu().numpy()
+    return out_c, out_h

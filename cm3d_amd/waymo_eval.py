@@ -169,6 +169,17 @@ def pack(pred_objects, gt_objects):
     return pack_arrays(*arrays_from_objects(pred_objects, gt_objects))
 
 
+def _expand(frame, typ, dist):
+    """Every box goes to its type's shard 0 and to its range shard: (box index, group key) of the boxes of a known type."""
+    n = frame.size
+    idx = np.concatenate([np.arange(n), np.arange(n)])
+    shard = np.concatenate([np.zeros(n, np.int32), _range_shard(dist)])
+    t = np.clip(np.concatenate([typ, typ]), 1, 4)
+    gkey = np.concatenate([frame, frame]).astype(np.int64) * N_BREAKDOWNS + (t - 1) * 4 + shard
+    ok = np.concatenate([(typ >= 1) & (typ <= 4)] * 2)
+    return idx[ok], gkey[ok]
+
+
 def pack_arrays(pred, gt, n_frames):
     """Per-box arrays -> groups.  pred: box (n, BOX_STRIDE), head float32, type, dist (distance of the centre from the
     origin), score float32, frame; gt: the same with level (1, 2) instead of score.  A group is (frame, type, shard):
@@ -176,17 +187,8 @@ def pack_arrays(pred, gt, n_frames):
     breakdown, predictions in a group by descending score (stable)."""
     ptyp, gtyp = pred["type"], gt["type"]
     bad = int(np.sum((ptyp < 1) | (ptyp > 4)) + np.sum((gtyp < 1) | (gtyp > 4)))
-
-    def expand(frame, typ, dist):      # every box goes to its type's shard 0 and to its range shard
-        n = frame.size
-        idx = np.concatenate([np.arange(n), np.arange(n)])
-        shard = np.concatenate([np.zeros(n, np.int32), _range_shard(dist)])
-        t = np.clip(np.concatenate([typ, typ]), 1, 4)
-        gkey = np.concatenate([frame, frame]).astype(np.int64) * N_BREAKDOWNS + (t - 1) * 4 + shard
-        ok = np.concatenate([(typ >= 1) & (typ <= 4)] * 2)
-        return idx[ok], gkey[ok]
-    pidx, pkey = expand(pred["frame"], ptyp, pred["dist"])
-    gidx, gkey = expand(gt["frame"], gtyp, gt["dist"])
+    pidx, pkey = _expand(pred["frame"], ptyp, pred["dist"])
+    gidx, gkey = _expand(gt["frame"], gtyp, gt["dist"])
     order = np.lexsort((pidx, -pred["score"][pidx].astype(np.float64), pkey))
     pidx, pkey = pidx[order], pkey[order]
     order = np.lexsort((gidx, gkey))
@@ -405,6 +407,76 @@ def counts_host(packed, weights=None):
                 fn1, fn2 = int(np.sum((lvl == 1) & ~matched)), int(np.sum(~matched))
             counts[bd, sel] += np.array([tp, int(k) - tp, fn1, fn2], np.int64)
             hsum[bd, sel] += hs
+    return counts, hsum
+
+
+# ------------------------------------------------------------------------------------------------ alpha sweep
+def pack_candidates(cand_objects, kind, p, s, gt_objects):
+    """The candidate superset of the SAM3D fusion grid search (fusion.waymo_candidates) -> the group layout of
+    cm3d_waymo_metrics_sweep.  cand_objects are decoded-Object-like dicts (center, length, width, height, heading, type,
+    context_name, timestamp_micros) in candidate order, kind / p / s as in include/cm3d_hip.h.  Groups are pack_arrays' groups
+    with candidates in the place of predictions: every candidate goes to shard 0 and to its own range shard (the two boxes
+    of a pair may differ there), frames are the union of candidate and ground-truth keys, ground truth without lidar
+    points is dropped; inside a group candidates keep candidate order.  group_static marks the groups of kind 0 only."""
+    kind = np.asarray(kind, np.int32)
+    pred, gt, n_frames = arrays_from_objects([dict(o, score=0.0) for o in cand_objects], gt_objects)
+    ctyp, gtyp = pred["type"], gt["type"]
+    bad = int(np.sum((ctyp < 1) | (ctyp > 4)) + np.sum((gtyp < 1) | (gtyp > 4)))
+    cidx, ckey = _expand(pred["frame"], ctyp, pred["dist"])
+    gidx, gkey = _expand(gt["frame"], gtyp, gt["dist"])
+    order = np.lexsort((cidx, ckey))
+    cidx, ckey = cidx[order], ckey[order]
+    order = np.lexsort((gidx, gkey))
+    gidx, gkey = gidx[order], gkey[order]
+    ukeys = np.unique(np.concatenate([ckey, gkey]))
+    cand_off = np.concatenate([np.searchsorted(ckey, ukeys, "left"), [ckey.size]]).astype(np.int64)
+    gt_off = np.concatenate([np.searchsorted(gkey, ukeys, "left"), [gkey.size]]).astype(np.int64)
+    moving = np.concatenate([[0], np.cumsum(kind[cidx] != 0)])
+    return dict(n_frames=int(n_frames), group_bd=(ukeys % N_BREAKDOWNS).astype(np.int32), group_frame=(ukeys // N_BREAKDOWNS),
+                cand_off=cand_off, gt_off=gt_off, cand_box=pred["box"][cidx], cand_head=pred["head"][cidx], cand_kind=kind[cidx],
+                cand_p=np.asarray(p, np.float64)[cidx], cand_s=np.asarray(s, np.float64)[cidx], cand_index=cidx,
+                gt_box=gt["box"][gidx], gt_head=gt["head"][gidx], gt_level=gt["level"][gidx],
+                group_static=(moving[cand_off[1:]] == moving[cand_off[:-1]]).astype(np.int32), bad_type=bad)
+
+
+def candidate_scores(kind, p, s, alpha):
+    """(active, float32 score) of candidates at one alpha, the rule of fusion.fuse_waymo: s * alpha in float64, compared
+    unclipped with p, then clipped to [0, 1] and rounded once to float32."""
+    prod = s * float(alpha)
+    sam = prod > p
+    active = (kind == 0) | (kind == 1) | ((kind == 2) & ~sam) | ((kind == 3) & sam)
+    score = np.where((kind == 0) | (kind == 2), p, np.clip(prod, 0, 1)).astype(np.float32)
+    return active, score
+
+
+def counts_sweep_host(packed_candidates, alphas):
+    """Host restatement of cm3d_waymo_metrics_sweep: (counts int64[A][16][101][4], hsum int64[A][16][101]).  Per alpha the
+    active candidates of every group are sorted (descending score, then candidate order) and counted by counts_host; the
+    weights of all candidates x ground truth are computed once and their rows gathered."""
+    pc = packed_candidates
+    co, go = pc["cand_off"], pc["gt_off"]
+    full = dict(pred_off=co, gt_off=go, pred_box=pc["cand_box"], gt_box=pc["gt_box"], group_bd=pc["group_bd"])
+    w_full, pair_off = pair_weights(full)
+    n_groups = co.size - 1
+    group_of = np.repeat(np.arange(n_groups), np.diff(co))
+    G = np.diff(go)
+    counts = np.zeros((len(alphas), N_BREAKDOWNS, N_CUTOFFS, 4), np.int64)
+    hsum = np.zeros((len(alphas), N_BREAKDOWNS, N_CUTOFFS), np.int64)
+    pos = np.arange(group_of.size)
+    for a, alpha in enumerate(alphas):
+        active, score = candidate_scores(pc["cand_kind"], pc["cand_p"], pc["cand_s"], alpha)
+        sel = np.flatnonzero(active)
+        sel = sel[np.lexsort((pos[sel], -score[sel].astype(np.float64), group_of[sel]))]
+        pred_off = np.concatenate([[0], np.cumsum(np.bincount(group_of[sel], minlength=n_groups))]).astype(np.int64)
+        g_sel = group_of[sel]
+        row0 = pair_off[g_sel] + (sel - co[g_sel]) * G[g_sel]             # the candidate's row of its group's weight matrix
+        reps = G[g_sel]
+        src = np.repeat(row0, reps) + (np.arange(int(reps.sum())) - np.repeat(np.cumsum(reps) - reps, reps))
+        w_off = np.concatenate([[0], np.cumsum(np.diff(pred_off) * G)]).astype(np.int64)
+        packed = dict(group_bd=pc["group_bd"], pred_off=pred_off, gt_off=go, pred_box=pc["cand_box"][sel],
+                      pred_head=pc["cand_head"][sel], pred_score=score[sel], gt_box=pc["gt_box"], gt_head=pc["gt_head"],
+                      gt_level=pc["gt_level"])
+        counts[a], hsum[a] = counts_host(packed, weights=(w_full[src], w_off))
     return counts, hsum
 
 

@@ -51,6 +51,7 @@ extern "C" {
 #define CM3D_WM_BOX_STRIDE 8     /* doubles per box of cm3d_waymo_metrics                */
 #define CM3D_WM_BREAKDOWNS 16    /* breakdowns of cm3d_waymo_metrics: (type - 1) * 4 + shard */
 #define CM3D_WM_CUTOFFS 101      /* score cutoffs of cm3d_waymo_metrics: float32(c * 0.01) */
+#define CM3D_WM_SWEEP_MAX_ALPHAS 1024 /* alphas of one cm3d_waymo_metrics_sweep call (added within ABI v5) */
 
 /* status word written by kernels (int32[4] in device memory, zero it per batch):
  *  [0] bit0: point capacity overflow (cm3d_sweep_prep), bit1: hit-index capacity
@@ -460,6 +461,44 @@ int cm3d_waymo_metrics(const double *pred_box, const float *pred_heading, const 
                        const int32_t *group_bd, const int64_t *pair_off, int32_t n_groups, int64_t total_pairs,
                        int32_t per_cutoff, int64_t *counts, int64_t *heading_sum, int32_t *status, void *workspace,
                        int64_t workspace_bytes, cm3d_stream_t stream);
+
+/* ---- Waymo metrics of every alpha of the SAM3D fusion grid search in one call --------
+ * Added within ABI v5: two new symbols, no existing call changes, so CM3D_ABI_VERSION stays.
+ * The fused file of src/waymo/linear_matching.py:335-470 differs between alphas only in scores and in which box of a matched pair
+ * it holds, so the host (cm3d_amd/waymo_eval.pack_candidates) packs a CANDIDATE superset once and this call counts every alpha's
+ * file from it.  Groups, breakdowns, ground truth, cutoffs, weights and matching are those of cm3d_waymo_metrics; candidates take
+ * the place of the predictions.  Group g owns candidates [cand_off[g], cand_off[g+1]) in CANDIDATE ORDER (the order in which the
+ * fused file lists the objects; the two candidates of a pair are neighbours).  For alpha a, with prod = s * a in double:
+ *   kind 0  unmatched prediction        always active, score (float)p
+ *   kind 1  unmatched SAM3D box         always active, score (float)clip(prod, 0, 1)
+ *   kind 2  a pair's prediction box     active iff !(prod > p), score (float)p
+ *   kind 3  a pair's SAM3D box          active iff prod > p, score (float)clip(prod, 0, 1)   (any other kind: never active)
+ * The active candidates are ranked by descending score, ties by ascending position in the group (-0 equals +0) -- the order
+ * waymo_eval.pack_arrays gives the decoded fused file -- and counted like the predictions of cm3d_waymo_metrics.
+ *  cand_box double[n_cand][CM3D_WM_BOX_STRIDE], cand_heading float[n_cand]   as pred_box, pred_heading of cm3d_waymo_metrics
+ *  cand_kind int32[n_cand]; cand_p, cand_s double[n_cand]   the prediction's and the SAM3D box's score (the one a kind lacks is ignored)
+ *  cand_off int32[n_groups+1]; gt_box, gt_heading, gt_level, gt_off, group_bd as in cm3d_waymo_metrics
+ *  pair_off int64[n_groups+1]  prefix sums of C_g * G_g (candidates x ground truth); total_pairs = pair_off[n_groups]
+ *  group_static int32[n_groups]  non-zero: every candidate of the group is kind 0.  Such a group does not depend on alpha: it is
+ *        solved once and its counts are added to every alpha (a non-zero flag on a group with other kinds gives that group's
+ *        counts at alpha 0 everywhere)
+ *  alphas double[n_alphas], 1 <= n_alphas <= CM3D_WM_SWEEP_MAX_ALPHAS (the caller hands a longer grid over in several calls)
+ *  counts int64[n_alphas][CM3D_WM_BREAKDOWNS][CM3D_WM_CUTOFFS][4] OUT, heading_sum int64[n_alphas][CM3D_WM_BREAKDOWNS][CM3D_WM_CUTOFFS]
+ *        OUT: per alpha what cm3d_waymo_metrics writes for that alpha's fused file (written whole)
+ *  status int32[1] (zero it before the call): bit0 a group with more than CM3D_MAX_MATCH_BOXES ground-truth boxes or more than
+ *        CM3D_MAX_MATCH_BOXES CANDIDATES (the ranking holds that many; a group whose active candidates would fit
+ *        cm3d_waymo_metrics at every alpha while its superset does not is refused here -- score such a grid alpha by alpha),
+ *        bit1 a group_bd outside [0, CM3D_WM_BREAKDOWNS) -- such a group is skipped, nothing is written out of range
+ *  workspace: cm3d_waymo_metrics_sweep_workspace_bytes(total_pairs), 8-byte aligned.  The weights are computed once for all
+ *        alphas; one wave per group and slice of the alphas ranks in LDS and solves.  Integer atomics only: every run gives the
+ *        same bits. */
+int64_t cm3d_waymo_metrics_sweep_workspace_bytes(int64_t total_pairs);
+int cm3d_waymo_metrics_sweep(const double *cand_box, const float *cand_heading, const int32_t *cand_kind, const double *cand_p,
+                             const double *cand_s, const int32_t *cand_off, const double *gt_box, const float *gt_heading,
+                             const int32_t *gt_level, const int32_t *gt_off, const int32_t *group_bd, const int64_t *pair_off,
+                             const int32_t *group_static, int32_t n_groups, int64_t total_pairs, const double *alphas,
+                             int32_t n_alphas, int64_t *counts, int64_t *heading_sum, int32_t *status, void *workspace,
+                             int64_t workspace_bytes, cm3d_stream_t stream);
 
 #ifdef __cplusplus
 }
