@@ -7,7 +7,8 @@ Mirrors the stages of the reference's src/nuscenes/2d_to_3d.py main loop
 at once; names follow the reference (`get_detection_name`, `ATTRIBUTE_NAMES`,
 `threshs_by_label`, ...).
 """
-from dataclasses import dataclass
+from contextlib import contextmanager
+from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
 import os
@@ -96,8 +97,8 @@ class ClassTable:
 # ---- batch packing ------------------------------------------------------------
 @dataclass
 class HostBatch:
-    """numpy view of one lift batch (see include/cm3d_hip.h for the layout)."""
-    raw: np.ndarray
+    """numpy view of one lift batch (see include/cm3d_hip.h for the layout).  Built by assemble_batch and nowhere else."""
+    raw: Optional[np.ndarray]                 # None while the sweeps wait in shared memory (raw_shm) and once they have been uploaded
     raw_stride: int
     sweep_row_off: np.ndarray
     sweep_xf: np.ndarray
@@ -118,8 +119,8 @@ class HostBatch:
     ego_xyz: np.ndarray
     width: int
     height: int
-    tokens: List[str]
-    labels: List[List[str]]
+    tokens: Optional[List[str]] = None        # None on the route through reader.Manifest: its frames are rows of sample.json, not tokens
+    labels: Optional[List[List[str]]] = None  # None on that route too: the labels arrive as class ids
     intensity: Optional[np.ndarray] = None    # quad layout only: (rows,) float32, the rows' fourth column (None: not uploaded)
     frame_rows: Optional[np.ndarray] = None   # quad layout only: (F,) rows of each frame without its padding rows
     pose_rt: Optional[np.ndarray] = None      # (F,12) float32, Waymo: vehicle -> global rotate/translate
@@ -127,10 +128,21 @@ class HostBatch:
     ego_box: bool = True                      # nuScenes drops the ego-box points (:442-445); Waymo does not
     mask_wh: Optional[np.ndarray] = None      # (n_masks, 2) int32 own (w, h) of every mask when they differ (Waymo's side cameras,
                                               # src/waymo/2d_to_3d.py:520-521); None: every mask has the canvas size (width, height)
+    lane_key: Optional[tuple] = None          # which lane tables these are, from a caller that knows (pipeline_nuscenes: the map locations)
+    raw_shm: Optional[tuple] = None           # (segment name, shape): the sweeps a reader process left in shared memory instead of `raw`
+    _lane_crc: Optional[tuple] = field(default=None, init=False, repr=False, compare=False)
+
+    def lane_tables_key(self):
+        """What LiftEngine keys its cache of lane tables and their spatial index by: lane_key, else a checksum of the tables (kept)."""
+        if self.lane_key is not None:
+            return self.lane_key
+        if self._lane_crc is None:
+            self._lane_crc = (self.lane.shape, self.lane_off.tobytes(), zlib.crc32(np.ascontiguousarray(self.lane).view(np.uint8)))
+        return self._lane_crc
 
     @property
     def n_frames(self):
-        return len(self.tokens)
+        return len(self.mask_off) - 1
 
     @property
     def n_masks(self):
@@ -191,6 +203,76 @@ def default_layout():
     return os.environ.get("CM3D_RAW_LAYOUT", "quads")
 
 
+class BatchDeclined(Exception):
+    """The native reader does not take this batch -- a pickle its parser does not know, masks of different image sizes, (Manifest route
+    only) frames without masks to be dropped --; the caller hands the batch to the Python reader.  Nothing else means "fall back"."""
+
+
+@contextmanager
+def declining_unknown_formats():
+    """The one place where a file the native parser does not know (reader.ReaderError with ERR_FORMAT) becomes BatchDeclined."""
+    from .reader import ERR_FORMAT, ReaderError
+    try:
+        yield
+    except ReaderError as exc:
+        if exc.code != ERR_FORMAT:
+            raise
+        raise BatchDeclined(str(exc)) from exc
+
+
+def _as(a, dtype):
+    """`a` itself when it already is an array of that type (a page-locked staging buffer stays the object it is)."""
+    return a if isinstance(a, np.ndarray) and a.dtype == dtype else np.asarray(a, dtype)
+
+
+def assemble_batch(*, raw, raw_stride, sweep_row_off, sweep_xf, frame_sweep_off, cams, mask_off, mask_cam, rle_counts, rle_off, class_id, score,
+                   detections_per_frame, lane_tables, frame_lane, ego_xyz, width, height, mask_wh=None, **optional) -> HostBatch:
+    """The primary arrays of a batch -> HostBatch: the one place that coerces types, derives what can be derived (n_cams,
+    max_rows_per_sweep, mask_frame, lane, lane_off, whether mask_wh says anything) and checks the fields against each other.
+    cams: one (n_cams, 64) record array per frame, or all of them stacked.  detections_per_frame: for every list that names a frame's
+    detections beside the masks themselves (labels, scores, cam_nums), its length per frame.  optional: the remaining HostBatch fields."""
+    i32 = lambda a: _as(a, np.int32)
+    if not isinstance(cams, np.ndarray):
+        if len({np.shape(c)[0] for c in cams}) > 1:
+            raise ValueError("all frames of a batch must share the camera count")
+        cams = np.stack([np.asarray(c, np.float32) for c in cams])
+    mask_off, mask_cam, class_id, score = i32(mask_off), i32(mask_cam), i32(class_id), _as(score, np.float64)
+    n_per = np.diff(mask_off)
+    if not (all(np.array_equal(n, n_per) for n in detections_per_frame) and mask_cam.size == class_id.size == score.size == int(mask_off[-1])):
+        raise ValueError("labels / detection_scores / cam_nums / masks differ in length")
+    sweep_row_off = i32(sweep_row_off)
+    if mask_wh is not None:
+        mask_wh = i32(mask_wh).reshape(-1, 2)
+        if bool(np.all(mask_wh == np.array([width, height], np.int32))):
+            mask_wh = None
+    # torch.Tensor(...) at :278: through float64 to float32; a table that already is float32 is taken as it is (the identity, DESIGN 11)
+    lane32 = [(t if isinstance(t, np.ndarray) and t.dtype == np.float32 else np.asarray(t, np.float64).astype(np.float32)).reshape(-1, 3)
+              for t in lane_tables]
+    return HostBatch(
+        raw=raw, raw_stride=raw_stride, sweep_row_off=sweep_row_off, sweep_xf=sweep_xf, frame_sweep_off=i32(frame_sweep_off),
+        max_rows_per_sweep=max(1, int(np.diff(sweep_row_off).max())) if len(sweep_row_off) > 1 else 1, cams=cams, n_cams=cams.shape[1],
+        mask_off=mask_off, mask_cam=mask_cam, mask_frame=np.repeat(np.arange(len(n_per), dtype=np.int32), n_per),
+        rle_counts=_as(rle_counts, np.uint32), rle_off=i32(rle_off), class_id=class_id, score=score,
+        lane=np.concatenate(lane32, 0), lane_off=np.concatenate([[0], np.cumsum([t.shape[0] for t in lane32])]).astype(np.int32),
+        frame_lane=i32(frame_lane), ego_xyz=_as(ego_xyz, np.float64), width=width, height=height, mask_wh=mask_wh, **optional)
+
+
+def frame_detections(frames, classes: ClassTable):
+    """labels, scores and cam_nums of frames (or frame manifests) -> what assemble_batch takes of them: (class_id, score, mask_cam,
+    labels per frame, detections_per_frame)."""
+    class_id, score, mask_cam = [], [], []
+    for fr in frames:
+        for l in fr.labels:
+            ci = classes.index(get_detection_name(l))
+            if classes.out_names is not None and classes.out_names[ci] == "":
+                raise ValueError(f"label {l!r} has no output type")     # the reference raises ValueError (src/waymo/2d_to_3d.py:1054-1062)
+            class_id.append(ci)
+        score.extend(float(s) for s in fr.scores)
+        mask_cam.extend(int(c) for c in fr.cam_nums)
+    per_frame = [[len(getattr(fr, k)) for fr in frames] for k in ("labels", "scores", "cam_nums")]
+    return class_id, score, mask_cam, [list(fr.labels) for fr in frames], per_frame
+
+
 def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane: Sequence[int],
                 classes: Optional[ClassTable] = None, layout: Optional[str] = None, keep_intensity: bool = True) -> HostBatch:
     """frames: objects with the attributes of cm3d_amd.synthetic.Frame.  layout: "rows" (the sweeps as they are) or
@@ -206,16 +288,11 @@ def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane:
     H = max([int(fr.height) for fr in frames] + [int(rl["size"][1]) for fr in frames for rl in fr.rles])
     if W > 4096:
         raise ValueError(f"masks of {W} columns: the mask kernels hold rows of up to 4096 pixels")
-    mask_wh = []
-    n_cams = frames[0].cams.shape[0]
     raws, xfs, row_off, fso = [], [], [0], [0]
-    cams, mask_off, mask_cam, mask_frame = [], [0], [], []
-    cnts, rle_off, class_id, score, ego, tokens, labels = [], [0], [], [], [], [], []
+    mask_wh, mask_off, cnts, rle_off = [], [0], [], [0]
     pose_rt, pose_inv = [], []
     stride = frames[0].sweeps_raw[0].shape[1]
-    for fi, fr in enumerate(frames):
-        if fr.cams.shape[0] != n_cams:
-            raise ValueError("all frames of a batch must share the camera count")
+    for fr in frames:
         for r in fr.sweeps_raw:
             r = np.ascontiguousarray(r, np.float32)
             if r.shape[1] != stride:
@@ -224,10 +301,6 @@ def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane:
             row_off.append(row_off[-1] + r.shape[0])
         xfs.append(np.asarray(fr.sweep_xf, np.float32).reshape(-1, _lib.SWEEP_XF_STRIDE))
         fso.append(fso[-1] + len(fr.sweeps_raw))
-        cams.append(np.asarray(fr.cams, np.float32))
-        n = len(fr.rles)
-        if not (len(fr.labels) == len(fr.scores) == len(fr.cam_nums) == n):
-            raise ValueError("labels / detection_scores / cam_nums / masks differ in length")
         for rl in fr.rles:
             w, h = (int(v) for v in rl["size"])
             if w < 1 or h < 1:
@@ -238,48 +311,27 @@ def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane:
             mask_wh.append((w, h))
             cnts.append(c)
             rle_off.append(rle_off[-1] + c.size)
-        mask_off.append(mask_off[-1] + n)
-        mask_cam.extend(int(c) for c in fr.cam_nums)
-        mask_frame.extend([fi] * n)
-        for l in fr.labels:
-            ci = classes.index(get_detection_name(l))
-            if classes.out_names is not None and classes.out_names[ci] == "":
-                raise ValueError(f"label {l!r} has no output type")     # the reference raises ValueError (src/waymo/2d_to_3d.py:1054-1062)
-            class_id.append(ci)
-        score.extend(float(s) for s in fr.scores)
-        ego.append(np.asarray(fr.ego_xyz, np.float64))
-        tokens.append(fr.token)
-        labels.append(list(fr.labels))
+        mask_off.append(mask_off[-1] + len(fr.rles))
         if getattr(fr, "pose", None) is not None:
             from . import waymo as wm
             rt, inv = wm.pose_records(fr.pose)
             pose_rt.append(rt)
             pose_inv.append(inv)
-    lane32 = [np.asarray(t, np.float64).astype(np.float32).reshape(-1, 3) for t in lane_tables]   # torch.Tensor(...) at :278
-    lane_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in lane32])]).astype(np.int32)
-    i32 = lambda a: np.asarray(a, np.int32)
+    class_id, score, mask_cam, labels, per_frame = frame_detections(frames, classes)
     raw = np.concatenate(raws, 0) if raws else np.zeros((0, stride), np.float32)
     intensity = frame_rows = None
-    row_off = i32(row_off)
     if layout == "quads":
-        raw, intensity, row_off, frame_rows = rows_to_quads(raw, row_off, fso, keep_intensity)
+        raw, intensity, row_off, frame_rows = rows_to_quads(raw, np.asarray(row_off, np.int32), fso, keep_intensity)
         stride = _lib.RAW_QUADS
-    mask_wh = i32(mask_wh).reshape(-1, 2)
-    if bool(np.all(mask_wh == np.array([W, H], np.int32))):
-        mask_wh = None
-    return HostBatch(
-        mask_wh=mask_wh,
-        raw=raw, raw_stride=stride, intensity=intensity, frame_rows=frame_rows,
-        sweep_row_off=row_off, sweep_xf=np.concatenate(xfs, 0), frame_sweep_off=i32(fso),
-        max_rows_per_sweep=max(1, int(np.diff(row_off).max())) if len(row_off) > 1 else 1, cams=np.stack(cams), n_cams=n_cams,
-        mask_off=i32(mask_off), mask_cam=i32(mask_cam), mask_frame=i32(mask_frame),
-        rle_counts=np.concatenate(cnts).astype(np.uint32) if cnts else np.zeros(0, np.uint32), rle_off=i32(rle_off),
-        class_id=i32(class_id), score=np.asarray(score, np.float64),
-        lane=np.concatenate(lane32, 0), lane_off=lane_off, frame_lane=i32(frame_lane),
-        ego_xyz=np.stack(ego), width=W, height=H, tokens=tokens, labels=labels,
-        pose_rt=np.stack(pose_rt).astype(np.float32) if len(pose_rt) == len(frames) and frames else None,
-        pose_inv=np.stack(pose_inv).astype(np.float32) if len(pose_inv) == len(frames) and frames else None,
-        ego_box=not ((len(pose_rt) == len(frames) and len(frames) > 0) or all(getattr(f, "no_ego_box", False) for f in frames)))
+    posed = len(pose_rt) == len(frames) and len(frames) > 0
+    return assemble_batch(
+        raw=raw, raw_stride=stride, intensity=intensity, frame_rows=frame_rows, sweep_row_off=row_off, sweep_xf=np.concatenate(xfs, 0),
+        frame_sweep_off=fso, cams=[fr.cams for fr in frames], mask_off=mask_off, mask_cam=mask_cam, mask_wh=mask_wh,
+        rle_counts=np.concatenate(cnts).astype(np.uint32) if cnts else np.zeros(0, np.uint32), rle_off=rle_off,
+        class_id=class_id, score=score, detections_per_frame=per_frame, lane_tables=lane_tables, frame_lane=frame_lane,
+        ego_xyz=[np.asarray(fr.ego_xyz, np.float64) for fr in frames], width=W, height=H, tokens=[fr.token for fr in frames], labels=labels,
+        pose_rt=np.stack(pose_rt).astype(np.float32) if posed else None, pose_inv=np.stack(pose_inv).astype(np.float32) if posed else None,
+        ego_box=not (posed or all(getattr(f, "no_ego_box", False) for f in frames)))
 
 
 def require_one_mask_size(hb: HostBatch):
@@ -293,53 +345,34 @@ def pack_manifest(man, lane_tables, frame_lane, classes: Optional[ClassTable], r
     """Frame manifests (nusc_io.scene_manifest) -> HostBatch, with the bulk data read by the native loader `rd`
     (cm3d_amd.reader.Reader): all sweeps of the batch land in one (page-locked) `raw` buffer, all RLE strings are parsed
     to run lengths by its thread pool.  Frames without masks are left out, like pack_frames' callers do.
-    Returns (HostBatch or None when no frame has a mask, indices of the frames it holds)."""
+    Returns (HostBatch or None when no frame has a mask, indices of the frames it holds); BatchDeclined for a batch that
+    needs the Python reader."""
     classes = classes or ClassTable.nuscenes()
-    counts, rle_off, fmo, wh = rd.load_masks([m.mask_path for m in man])
-    n_per = np.diff(fmo)
-    live = [i for i in range(len(man)) if n_per[i] > 0]
-    if not live:
-        return None, []
-    if len(live) != len(man):                       # rare: repack the frames that have masks
-        hb, sub = pack_manifest([man[i] for i in live], lane_tables, [frame_lane[i] for i in live], classes, rd, stride, alloc)
-        return hb, [live[k] for k in sub]
-    W, H = int(wh[0, 0]), int(wh[0, 1])
-    if np.any(wh[:, 0] != W) or np.any(wh[:, 1] != H):
-        raise ValueError("all frames of a batch must share mask size and camera count")
-    fso = np.concatenate([[0], np.cumsum([len(m.sweep_paths) for m in man])]).astype(np.int32)
-    intensity = frame_rows = None
-    if default_layout() == "quads":     # the files' rows go straight into the quad layout (no intensity plane: no output holds it)
-        raw, intensity, row_off, frame_rows = rd.load_sweeps_quads([p for m in man for p in m.sweep_paths], fso, stride, False, alloc)
-        stride = _lib.RAW_QUADS
-    else:
-        raw, row_off = rd.load_sweeps([p for m in man for p in m.sweep_paths], stride, alloc)
-    n_cams = man[0].cams.shape[0]
-    mask_cam, mask_frame, class_id, score = [], [], [], []
-    for fi, m in enumerate(man):
-        n = int(n_per[fi])
-        if not (len(m.labels) == len(m.scores) == len(m.cam_nums) == n):
-            raise ValueError("labels / detection_scores / cam_nums / masks differ in length")
-        if m.cams.shape[0] != n_cams:
-            raise ValueError("all frames of a batch must share mask size and camera count")
-        mask_cam.extend(int(c) for c in m.cam_nums)
-        mask_frame.extend([fi] * n)
-        for l in m.labels:
-            ci = classes.index(get_detection_name(l))
-            if classes.out_names is not None and classes.out_names[ci] == "":
-                raise ValueError(f"label {l!r} has no output type")
-            class_id.append(ci)
-        score.extend(float(s) for s in m.scores)
-    lane32 = [np.asarray(t, np.float64).astype(np.float32).reshape(-1, 3) for t in lane_tables]
-    lane_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in lane32])]).astype(np.int32)
-    i32 = lambda a: np.asarray(a, np.int32)
-    hb = HostBatch(
+    with declining_unknown_formats():
+        counts, rle_off, fmo, wh = rd.load_masks([m.mask_path for m in man])
+        n_per = np.diff(fmo)
+        live = [i for i in range(len(man)) if n_per[i] > 0]
+        if not live:
+            return None, []
+        if len(live) != len(man):                       # rare: repack the frames that have masks
+            hb, sub = pack_manifest([man[i] for i in live], lane_tables, [frame_lane[i] for i in live], classes, rd, stride, alloc)
+            return hb, [live[k] for k in sub]
+        if np.any(wh != wh[0]):
+            raise BatchDeclined("masks of different image sizes in one batch")
+        fso = np.concatenate([[0], np.cumsum([len(m.sweep_paths) for m in man])]).astype(np.int32)
+        intensity = frame_rows = None
+        if default_layout() == "quads":     # the files' rows go straight into the quad layout (no intensity plane: no output holds it)
+            raw, intensity, row_off, frame_rows = rd.load_sweeps_quads([p for m in man for p in m.sweep_paths], fso, stride, False, alloc)
+            stride = _lib.RAW_QUADS
+        else:
+            raw, row_off = rd.load_sweeps([p for m in man for p in m.sweep_paths], stride, alloc)
+    class_id, score, mask_cam, labels, per_frame = frame_detections(man, classes)
+    hb = assemble_batch(
         raw=raw, raw_stride=stride, intensity=intensity, frame_rows=frame_rows, sweep_row_off=row_off,
         sweep_xf=np.concatenate([np.asarray(m.sweep_xf, np.float32).reshape(-1, _lib.SWEEP_XF_STRIDE) for m in man], 0),
-        frame_sweep_off=fso, max_rows_per_sweep=max(1, int(np.diff(row_off).max())), cams=np.stack([np.asarray(m.cams, np.float32) for m in man]),
-        n_cams=n_cams, mask_off=fmo.astype(np.int32), mask_cam=i32(mask_cam), mask_frame=i32(mask_frame), rle_counts=counts, rle_off=rle_off,
-        class_id=i32(class_id), score=np.asarray(score, np.float64), lane=np.concatenate(lane32, 0), lane_off=lane_off,
-        frame_lane=i32(frame_lane), ego_xyz=np.stack([m.ego_xyz for m in man]), width=W, height=H, tokens=[m.token for m in man],
-        labels=[list(m.labels) for m in man], ego_box=True)
+        frame_sweep_off=fso, cams=[m.cams for m in man], mask_off=fmo, mask_cam=mask_cam, mask_wh=wh, rle_counts=counts, rle_off=rle_off,
+        class_id=class_id, score=score, detections_per_frame=per_frame, lane_tables=lane_tables, frame_lane=frame_lane,
+        ego_xyz=[m.ego_xyz for m in man], width=int(wh[0, 0]), height=int(wh[0, 1]), tokens=[m.token for m in man], labels=labels)
     return hb, list(range(len(man)))
 
 
@@ -492,11 +525,7 @@ class LiftEngine:
         # (the key first: on a hit the tables are neither uploaded -- a pageable, host-blocking copy of megabytes -- nor read for a
         # checksum; the checksum of a table set is kept on the host batch.  The cache is shared by the engines of a LiftPipeline:
         # consecutive batches of a job alternate between them.)
-        key = getattr(hb, "lane_key", None)
-        if key is None:
-            key = getattr(hb, "_lane_crc", None)
-            if key is None:
-                key = hb._lane_crc = (hb.lane.shape, hb.lane_off.tobytes(), zlib.crc32(np.ascontiguousarray(hb.lane).view(np.uint8)))
+        key = hb.lane_tables_key()
         hit = self._lane_cache.get(key)
         if hit is not None:
             self._lane = hit

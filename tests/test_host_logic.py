@@ -232,20 +232,21 @@ def test_direct_json_writer_equals_json_dumps_of_the_dicts():
 def test_prepare_scene_batch_in_reader_processes(tmp_path):
     """pipeline_nuscenes.prepare_scene_batch (file reads + RLE strings + packing; no GPU) gives the same host batches in
     spawned reader processes as in this process."""
+    import dataclasses
     import multiprocessing as mp
     import numpy as np
     from cm3d_amd import nusc_io, pipeline_nuscenes as pn, synthetic as syn
     cfg = syn.config("tiny")
     dataroot, mask_dir, names = nusc_io.write_synthetic_dataset(str(tmp_path), cfg, n_scenes=2, frames_per_scene=2)
-    tasks = [("v1.0-synth", dataroot, mask_dir, [n], 3, cfg.ratio, False, None) for n in names]
+    tasks = [pn.BatchTask("v1.0-synth", dataroot, mask_dir, [n], 3, cfg.ratio, False, None) for n in names]
     here = [pn.prepare_scene_batch(t) for t in tasks]
     with mp.get_context("spawn").Pool(2) as pool:
-        there = list(pool.imap(pn.prepare_scene_batch, [t + (True,) for t in tasks]))       # sweeps through shared memory
+        there = list(pool.imap(pn.prepare_scene_batch, [dataclasses.replace(t, through_shm=True) for t in tasks]))       # sweeps through shared memory
     keep = []
     for (tok_a, hbs_a, _), (tok_b, hbs_b, _) in zip(here, there):
         assert tok_a == tok_b and len(tok_a) == 2 and len(hbs_a) == len(hbs_b) == 1
         a, b = hbs_a[0], hbs_b[0]
-        assert isinstance(b.raw, tuple)
+        assert b.raw is None and isinstance(b.raw_shm, tuple)
         pn._attach_raw(b, keep)
         assert a.tokens == b.tokens and a.labels == b.labels and (a.width, a.height, a.n_cams) == (b.width, b.height, b.n_cams)
         for k in ("raw", "sweep_row_off", "sweep_xf", "frame_sweep_off", "cams", "mask_off", "mask_cam", "rle_counts", "rle_off", "class_id",

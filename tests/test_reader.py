@@ -1,6 +1,7 @@
 """CPU: the native host-side loader (libcm3d_reader.so, include/cm3d_reader.h) against the Python reader that mirrors the
 reference's per-frame `pickle.load` / `np.fromfile` -- same host batches, error codes instead of crashes on bad input."""
 import ctypes
+import dataclasses
 import json
 import os
 import pickle
@@ -95,9 +96,9 @@ def test_native_batches_equal_the_python_reader(tmp_path):
     import json
     json.dump({"labels": [], "detection_scores": [], "cam_nums": []}, open(os.path.join(mask_dir, names[0], "2_data.json"), "w"))
     rd = reader.Reader(4, pinned=False)
-    base = ("v1.0-synth", dataroot, mask_dir, names, 3, cfg.ratio, True, None)
+    base = pn.BatchTask("v1.0-synth", dataroot, mask_dir, names, 3, cfg.ratio, True, None)
     a = pn.prepare_scene_batch(base)
-    b = pn.prepare_scene_batch(base + (False, rd))
+    b = pn.prepare_scene_batch(dataclasses.replace(base, reader=rd))
     assert a[0] == b[0] and len(a[0]) == 6 and len(a[1]) == len(b[1]) == 1
     x, y = a[1][0], b[1][0]
     assert x.n_frames == 4
@@ -341,3 +342,119 @@ def test_native_quads_equal_the_numpy_packing(tmp_path):
     assert int(want_off[-1]) % 4 == 0 and np.all(want_off[fso[:-1]] % 4 == 0) and want_rows.tolist() == [20, 1, 261, 7]
     with pytest.raises(reader.ReaderError):
         rd.load_sweeps_quads(paths, np.array([0, 3, 9], np.int32), 5)          # frames that do not cover the files
+
+
+# ----------------------------------------------------------------------------- one assembler, declined batches
+def _tiny_dataset(tmp_path):
+    """2 scenes x 3 frames: the smallest set with a scene boundary and a batch boundary."""
+    cfg = syn.config("tiny")
+    return (cfg,) + nusc_io.write_synthetic_dataset(str(tmp_path), cfg, n_scenes=2, frames_per_scene=3)
+
+
+def _assert_same_batches(a, b, skip=()):
+    from cm3d_amd import lifting
+    assert len(a) == len(b)
+    for x, y in zip(a, b):
+        for fld in dataclasses.fields(lifting.HostBatch):
+            u, v = getattr(x, fld.name), getattr(y, fld.name)
+            if fld.name not in skip:
+                assert (np.array_equal(u, v, equal_nan=True) if isinstance(u, np.ndarray) else u == v), fld.name
+
+
+def _at_size(rles, w, h):
+    out = []
+    for r in rles:
+        img = rle.counts_to_dense(rle.string_to_counts(r["counts"]), *r["size"])[:h, :w]
+        out.append({"size": [w, h], "counts": rle.counts_to_string(rle.dense_to_counts(np.ascontiguousarray(img)))})
+    return out
+
+
+@pytest.mark.parametrize("why", ["another size", "no mask file", "not a list", "protocol 0"])
+def test_declined_batches_go_to_the_python_reader(tmp_path, why):
+    """Each reason for which the native route declines a batch raises lifting.BatchDeclined -- from pack_manifest and from
+    _native_batch_head -- and prepare_scene_batch then gives what the Python reader alone gives, field for field: one mask file
+    rewritten at another size; one frame's mask file removed under missing_ok (a decline of _native_batch_head only: pack_manifest
+    repacks the frames that have masks); a pickle the native parser rejects -- `notalist.pkl` of
+    test_malformed_mask_files_are_errors_not_crashes, which the Python reader cannot use either, so both end in its error, and a
+    protocol-0 pickle of the same masks, which only the Python reader knows."""
+    from cm3d_amd import lifting
+    cfg, dataroot, mask_dir, names = _tiny_dataset(tmp_path)
+    p = os.path.join(mask_dir, names[1], "1_masks.pkl")
+    rles = pickle.load(open(p, "rb"))
+    if why == "another size":
+        pickle.dump(_at_size(rles, cfg.width - 16, cfg.height - 8), open(p, "wb"))
+    elif why == "no mask file":
+        os.remove(p)
+    elif why == "not a list":
+        open(p, "wb").write(pickle.dumps({"size": [4, 4]}))
+    else:
+        pickle.dump(rles, open(p, "wb"), protocol=0)
+    rd = reader.Reader(4, pinned=False)
+    classes = lifting.ClassTable.nuscenes()
+    pt = nusc_io.NuscTables("v1.0-synth", dataroot, annotations=False)
+    man, lanes, frame_lane = pn._batch_manifest(pt, names, mask_dir, 3, cfg.ratio, True)
+    if why == "no mask file":
+        hb, kept = lifting.pack_manifest(man, lanes, frame_lane, classes, rd)
+        assert kept == [0, 1, 2, 3, 5] and hb.n_frames == 5
+    else:
+        with pytest.raises(lifting.BatchDeclined):
+            lifting.pack_manifest(man, lanes, frame_lane, classes, rd)
+    with pytest.raises(lifting.BatchDeclined):
+        pn._native_batch_head(reader.Tables(rd, dataroot, "v1.0-synth"), names, mask_dir, 3, cfg.ratio, classes, True, {})
+    task = pn.BatchTask("v1.0-synth", dataroot, mask_dir, names, 3, cfg.ratio, True, None)
+    if why == "not a list":
+        with pytest.raises(Exception) as python_alone:
+            pn.prepare_scene_batch(task)
+        with pytest.raises(python_alone.type):
+            pn.prepare_scene_batch(dataclasses.replace(task, reader=rd))
+        assert not issubclass(python_alone.type, (lifting.BatchDeclined, reader.ReaderError))
+        return
+    a = pn.prepare_scene_batch(task)
+    b = pn.prepare_scene_batch(dataclasses.replace(task, reader=rd))
+    assert a[0] == b[0] and len(a[0]) == 6 and len(a[1]) == (2 if why == "another size" else 1)
+    # (a batch the native loader does take leaves the intensity behind, and its checksum of the lane tables is made on demand)
+    _assert_same_batches(a[1], b[1], skip=("intensity",) if why == "no mask file" else ())
+    assert sum(hb.n_frames for hb in a[1]) == (5 if why == "no mask file" else 6)
+
+
+def test_camera_count_mismatch_is_an_error_of_the_native_route(tmp_path, monkeypatch):
+    """Frames with different camera counts in one batch: a ValueError from the reader that sees it first -- not a decline that the
+    Python reader would have to report."""
+    cfg, dataroot, mask_dir, names = _tiny_dataset(tmp_path)
+    walk = nusc_io.scene_manifest
+
+    def one_camera_less(*args, **kw):
+        ms = walk(*args, **kw)
+        ms[1].cams = ms[1].cams[:5]
+        return ms
+
+    def python_reader(*args, **kw):
+        raise AssertionError("the Python reader was entered")
+    monkeypatch.setattr(nusc_io, "scene_manifest", one_camera_less)
+    monkeypatch.setattr(nusc_io, "frames_of_scene", python_reader)
+    task = pn.BatchTask("v1.0-synth", dataroot, mask_dir, names, 3, cfg.ratio, False, None, reader=reader.Reader(2, pinned=False))
+    with pytest.raises(ValueError, match="camera count"):
+        pn.prepare_scene_batch(task)
+
+
+def test_native_tail_batch_equals_pack_manifest(tmp_path):
+    """reader.Manifest + _native_batch_tail against nusc_io.scene_manifest + lifting.pack_manifest: every HostBatch field that both
+    set, the derived ones (n_cams, max_rows_per_sweep, mask_frame, lane, lane_off) among them; the former names its frames by their
+    rows in sample.json and knows which lane tables it carries, the latter has tokens and label strings."""
+    from cm3d_amd import lifting
+    cfg, dataroot, mask_dir, names = _tiny_dataset(tmp_path)
+    rd = reader.Reader(4, pinned=False)
+    nt = reader.Tables(rd, dataroot, "v1.0-synth")
+    classes = lifting.ClassTable.nuscenes()
+    x, rows = pn._native_batch_tail(nt, pn._native_batch_head(nt, names, mask_dir, 3, cfg.ratio, classes, False, {}))
+    pt = nusc_io.NuscTables("v1.0-synth", dataroot, annotations=False)
+    man, _, _ = pn._batch_manifest(pt, names, mask_dir, 3, cfg.ratio, False)
+    _, frame_lane, locs = pn._native_batch_lanes(nt, names, {})
+    y, kept = lifting.pack_manifest(man, [nusc_io.load_lane_points(dataroot, loc) for loc in locs], frame_lane, classes, rd)   # float64 tables
+    assert kept == list(range(6)) and x.n_frames == y.n_frames == 6 and x.n_cams == 6 and x.mask_wh is None
+    assert (x.tokens, x.labels, y.lane_key) == (None, None, None) and x.lane_key == (dataroot, tuple(locs))
+    assert [list(pt.t["sample"].keys())[r] for r in rows] == y.tokens
+    assert x.lane.dtype == np.float32 and x.lane_off.dtype == x.mask_frame.dtype == np.int32
+    _assert_same_batches([x], [y], skip=("tokens", "labels", "lane_key"))
+    # the key of the lane tables: what the caller says, else a checksum of the tables, made once
+    assert x.lane_tables_key() == x.lane_key and y.lane_tables_key() is y.lane_tables_key() and y.lane_tables_key()[0] == y.lane.shape

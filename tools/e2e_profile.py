@@ -27,7 +27,7 @@ for rep in range(3):
         if rep == 2:
             print(f"batch {b0 // 8}: manifest {1e3 * (t[1] - t[0]):.1f}  masks {1e3 * (t[2] - t[1]):.1f}  sweeps {1e3 * (t[3] - t[2]):.1f} ms "
                   f"({raw.nbytes / 1e6:.0f} MB, {raw.nbytes / (t[3] - t[2]) / 1e9:.1f} GB/s)  upload {1e3 * (t[4] - t[3]):.1f} ms")
-# the same batches through _native_batch + LiftEngine.upload / run, timed on the host
+# the same batches through _native_batch_head / _native_batch_tail + LiftEngine.upload / run, timed on the host
 from cm3d_amd import pipeline_nuscenes as pn
 eng = lifting.LiftEngine()
 lane_cache = {}
@@ -35,7 +35,7 @@ import cProfile, pstats
 for rep in range(3):
     for b0 in range(0, 32, 8):
         t = [time.perf_counter()]
-        hb, rows = pn._native_batch(nt, names[b0:b0 + 8], mask_dir, 1, 1.0, classes, False, lane_cache); t.append(time.perf_counter())
+        hb, rows = pn._native_batch_tail(nt, pn._native_batch_head(nt, names[b0:b0 + 8], mask_dir, 1, 1.0, classes, False, lane_cache)); t.append(time.perf_counter())
         if rep == 2 and b0 == 8:
             h = torch.from_numpy(np.ascontiguousarray(hb.raw))
             torch.cuda.synchronize(); q0 = time.perf_counter(); x = h.to("cuda:0", non_blocking=h.is_pinned()); q1 = time.perf_counter(); torch.cuda.synchronize(); q2 = time.perf_counter()

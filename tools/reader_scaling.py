@@ -2,6 +2,7 @@
 """Host side of the nuScenes entry point (file reads, RLE strings, packing: pipeline_nuscenes.prepare_scene_batch) on a
 synthetic C1-shaped dataset written to a temporary directory: frames/s in this process and with N spawned reader
 processes.  CPU only."""
+import dataclasses
 import multiprocessing as mp
 import os
 import shutil
@@ -19,7 +20,7 @@ def main():
     try:
         n_scenes, fps = 8, 6
         dataroot, mask_dir, names = nusc_io.write_synthetic_dataset(d, cfg, n_scenes=n_scenes, frames_per_scene=fps)
-        tasks = [("v1.0-synth", dataroot, mask_dir, [n], 3, cfg.ratio, False, None) for n in names]
+        tasks = [pn.BatchTask("v1.0-synth", dataroot, mask_dir, [n], 3, cfg.ratio, False, None) for n in names]
         t0 = time.time()
         for t in tasks:
             pn.prepare_scene_batch(t)
@@ -33,7 +34,7 @@ def main():
                             pn._attach_raw(hb, keep)
                             hb.raw.sum()                                 # touch the mapped sweeps
                             pn._release(keep)
-                shm_tasks = [t + (True,) for t in tasks]
+                shm_tasks = [dataclasses.replace(t, through_shm=True) for t in tasks]
                 for _ in range(3):                                      # start-up (imports, tables) outside the timing
                     consume(pool.imap(pn.prepare_scene_batch, shm_tasks))
                 t0 = time.time()
