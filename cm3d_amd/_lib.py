@@ -77,7 +77,36 @@ SIGNATURES = {
     "cm3d_waymo_metrics": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _i64, _p]),
     "cm3d_waymo_metrics_sweep_workspace_bytes": (_i64, [_i64]),
     "cm3d_waymo_metrics_sweep": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _p, _i32, _p, _p, _p, _p, _i64, _p]),
+    "cm3d_lift_pass": (_i32, [_p, _p]),
+    "cm3d_pipe_exec_streams_for": (_i32, [_i32, _i32]),
+    "cm3d_pipe_create": (_p, [_i32, _i32, _p]),
+    "cm3d_pipe_destroy": (None, [_p]),
+    "cm3d_pipe_exec_streams": (_i32, [_p]),
+    "cm3d_pipe_submit": (_i32, [_p, _i32, _p]),
+    "cm3d_pipe_submit_timed": (_i32, [_p, _i32, _p, _p, _p]),
+    "cm3d_pipe_acquire": (_i32, [_p, _i32]),
+    "cm3d_pipe_release": (_i32, [_p, _i32]),
+    "cm3d_pipe_wait": (_i32, [_p, _i32]),
+    "cm3d_pipe_pin": (_i32, [_p]),
+    "cm3d_pipe_last_stream": (_i32, [_p, _i32]),
 }
+
+
+class LiftPassDesc(C.Structure):
+    """cm3d_lift_pass_desc of include/cm3d_hip.h, field for field."""
+    _fields_ = (
+        [("size", _i64)]
+        + [(n, _p) for n in ("rle_counts", "rle_off", "packed", "bbox", "rle_ws")] + [("rle_ws_bytes", _i64)]
+        + [(n, _p) for n in ("status", "hit_count", "removed_bits")] + [("removed_words", _i64)]
+        + [(n, _p) for n in ("raw", "intensity", "sweep_row_off", "sweep_xf", "frame_sweep_off", "points", "pt_off", "cams", "mask_off",
+                             "mask_cam", "hit_words", "pg_ws")] + [("pg_ws_bytes", _i64)]
+        + [(n, _p) for n in ("hit_off", "tile_off", "hit_idx", "hit_xyz", "tile_work", "medoid_pos", "centroid", "colsum", "ws")]
+        + [("ws_bytes", _i64), ("md_feedback", _p)]
+        + [(n, _p) for n in ("centroid_g", "mask_frame", "lane", "lane_off", "frame_lane", "grid", "lane_idx", "lane_dist", "class_id", "score",
+                             "prior_wlh", "is_vehicle", "nms_group", "nms_thr", "ego_xyz", "box", "flags")]
+        + [(n, _i32) for n in ("n_masks", "total_runs", "W", "H", "raw_stride", "n_sweeps", "max_sweeps_per_frame", "pt_cap", "n_frames",
+                               "max_pts_per_frame", "n_cams", "planes", "idx_cap", "n_tables", "n_lane_points", "n_classes", "md_hint")]
+        + [("halfw", _f32), ("min_dist", _f32)])
 
 
 class Cm3dError(RuntimeError):

@@ -1,0 +1,169 @@
+// Host side of a pass: one call that enqueues the six launches of a steady-state nuScenes pass (cm3d_lift_pass), and the pipeline
+// object that decides which stream a slot's pass goes to (csrc/pipe_sched.h) and keeps two passes of one slot in order when they
+// land on different streams.  No kernel lives here: every launch goes through the entry points of include/cm3d_hip.h, with the
+// arguments and in the order cm3d_amd.lifting.LiftEngine.run hands them over.
+#include <hip/hip_runtime_api.h>
+
+#include <cstdlib>
+#include <new>
+
+#include "../../include/cm3d_hip.h"
+#include "pipe_sched.h"
+
+static int lift_pass(const cm3d_lift_pass_desc *d, void *ev_start, void *ev_stop, cm3d_stream_t st)
+{
+    if (!d || d->size != (int64_t)sizeof(cm3d_lift_pass_desc)) return CM3D_ERR_ARG;
+    int rc = cm3d_rle_erode_pack_begin(d->rle_counts, d->rle_off, d->n_masks, d->total_runs, d->W, d->H, d->packed, d->bbox, d->rle_ws,
+                                       d->rle_ws_bytes, d->status, d->hit_count, d->n_masks, d->removed_bits, d->removed_words, st);
+    if (rc != CM3D_OK) return rc;
+    rc = cm3d_sweep_project_hits(d->raw, d->raw_stride, d->intensity, d->sweep_row_off, d->n_sweeps, d->max_sweeps_per_frame, d->sweep_xf,
+                                 d->frame_sweep_off, d->halfw, d->points, d->pt_cap, d->pt_off, d->removed_bits, d->n_frames,
+                                 d->max_pts_per_frame, d->pt_cap, d->cams, d->n_cams, d->mask_off, d->mask_cam, d->bbox, d->packed, d->n_masks,
+                                 d->W, d->H, d->min_dist, d->planes, d->hit_words, d->hit_count, d->status, d->pg_ws, d->pg_ws_bytes,
+                                 ev_start, ev_stop, st);
+    if (rc != CM3D_OK) return rc;
+    // coordinates of the in-mask points: from the cloud when it exists, else re-derived from the raw rows
+    const bool from_raw = d->points == nullptr;
+    rc = cm3d_compact_hits(d->hit_words, d->planes, d->n_frames, d->max_pts_per_frame, d->pt_cap, d->mask_off, d->n_masks, d->hit_count,
+                           d->removed_bits, from_raw ? d->raw : nullptr, d->raw_stride, from_raw ? d->intensity : nullptr,
+                           from_raw ? d->sweep_xf : nullptr, d->points, d->hit_off, d->tile_off, d->hit_idx, nullptr, d->hit_xyz, d->idx_cap,
+                           d->tile_work, d->status, d->pg_ws, d->pg_ws_bytes, st);
+    if (rc != CM3D_OK) return rc;
+    // the hint: whatever the device has written into the page-locked word by now (a stale value costs time on one pass, never a result)
+    int32_t md_flags = 0;
+    if (d->md_hint && d->md_feedback && *(const volatile int32_t *)d->md_feedback == 0) md_flags = 1;
+    rc = cm3d_medoid2(d->hit_xyz, nullptr, nullptr, d->n_masks, d->hit_off, d->tile_off, nullptr, d->idx_cap, d->tile_work, d->medoid_pos,
+                      d->centroid, d->colsum, d->ws, d->ws_bytes, md_flags, d->md_feedback, st);
+    if (rc != CM3D_OK) return rc;
+    rc = cm3d_lane_nn(d->centroid_g, d->medoid_pos, d->mask_frame, d->n_masks, d->lane, d->lane_off, d->frame_lane, d->n_tables,
+                      d->n_lane_points, d->grid, d->lane_idx, d->lane_dist, d->ws, d->ws_bytes, st);
+    if (rc != CM3D_OK) return rc;
+    return cm3d_box_nms(d->centroid_g, d->medoid_pos, d->mask_off, d->n_frames, d->n_masks, d->class_id, d->score, d->lane, d->lane_off,
+                        d->frame_lane, d->lane_idx, d->lane_dist, d->prior_wlh, d->is_vehicle, d->nms_group, d->nms_thr, d->n_classes,
+                        d->ego_xyz, nullptr, d->box, d->flags, st);
+}
+
+extern "C" int cm3d_lift_pass(const cm3d_lift_pass_desc *d, cm3d_stream_t st) { return lift_pass(d, nullptr, nullptr, st); }
+
+extern "C" int cm3d_pipe_exec_streams_for(int32_t depth, int32_t hw_queues)
+{
+    if (hw_queues <= 0) hw_queues = cm3d::pipe_hw_queues(std::getenv("GPU_MAX_HW_QUEUES"));
+    return cm3d::pipe_exec_streams(depth, hw_queues);
+}
+
+namespace {
+
+struct Pipe {
+    cm3d::PipeSched sched;
+    hipStream_t streams[cm3d::kPipeMaxDepth];
+    hipEvent_t done[cm3d::kPipeMaxDepth];      // behind the slot's last pass (timing disabled)
+    bool recorded[cm3d::kPipeMaxDepth];
+    Pipe(int depth, int n_exec) : sched(depth, n_exec) {}
+};
+
+// the stream of the slot's next pass, ordered behind the slot's previous pass where that ran elsewhere; < 0: error
+int pipe_take(Pipe *p, int32_t slot)
+{
+    if (!p || slot < 0 || slot >= p->sched.depth) return CM3D_ERR_ARG;
+    const cm3d::PipeTicket t = p->sched.next(slot);
+    if (t.wait && p->recorded[slot] && hipEventQuery(p->done[slot]) != hipSuccess) {
+        (void)hipGetLastError();                // hipErrorNotReady is the expected answer, not a sticky error
+        if (hipStreamWaitEvent(p->streams[t.stream], p->done[slot], 0) != hipSuccess) return CM3D_ERR_LAUNCH;
+    }
+    return t.stream;
+}
+
+int pipe_mark(Pipe *p, int32_t slot)
+{
+    const int s = p->sched.last[slot];
+    if (s < 0) return CM3D_ERR_ARG;
+    if (hipEventRecord(p->done[slot], p->streams[s]) != hipSuccess) return CM3D_ERR_LAUNCH;
+    p->recorded[slot] = true;
+    return CM3D_OK;
+}
+
+}  // namespace
+
+extern "C" void *cm3d_pipe_create(int32_t depth, int32_t exec_streams, const cm3d_stream_t *streams)
+{
+    if (depth < 1 || depth > cm3d::kPipeMaxDepth || !streams) return nullptr;
+    const int n_exec = exec_streams > 0 ? (exec_streams < depth ? exec_streams : depth) : cm3d_pipe_exec_streams_for(depth, 0);
+    Pipe *p = new (std::nothrow) Pipe(depth, n_exec);
+    if (!p) return nullptr;
+    for (int i = 0; i < cm3d::kPipeMaxDepth; ++i) {
+        p->streams[i] = nullptr;
+        p->done[i] = nullptr;
+        p->recorded[i] = false;
+    }
+    for (int i = 0; i < depth; ++i) {
+        p->streams[i] = (hipStream_t)streams[i];
+        if (hipEventCreateWithFlags(&p->done[i], hipEventDisableTiming) != hipSuccess) {
+            cm3d_pipe_destroy(p);
+            return nullptr;
+        }
+    }
+    return p;
+}
+
+extern "C" void cm3d_pipe_destroy(void *pipe)
+{
+    Pipe *p = (Pipe *)pipe;
+    if (!p) return;
+    for (int i = 0; i < p->sched.depth; ++i)
+        if (p->done[i]) (void)hipEventDestroy(p->done[i]);
+    delete p;
+}
+
+extern "C" int cm3d_pipe_exec_streams(const void *pipe)
+{
+    return pipe ? ((const Pipe *)pipe)->sched.n_exec : CM3D_ERR_ARG;
+}
+
+extern "C" int cm3d_pipe_submit(void *pipe, int32_t slot, const cm3d_lift_pass_desc *desc)
+{
+    return cm3d_pipe_submit_timed(pipe, slot, desc, nullptr, nullptr);
+}
+
+extern "C" int cm3d_pipe_submit_timed(void *pipe, int32_t slot, const cm3d_lift_pass_desc *desc, void *ev_start, void *ev_stop)
+{
+    Pipe *p = (Pipe *)pipe;
+    if (!desc) return CM3D_ERR_ARG;
+    const int s = pipe_take(p, slot);
+    if (s < 0) return s;
+    const int rc = lift_pass(desc, ev_start, ev_stop, (cm3d_stream_t)p->streams[s]);
+    // (the event also behind a pass that stopped half-way: what it did enqueue is what the slot's next pass must wait for)
+    const int rm = pipe_mark(p, slot);
+    if (rc != CM3D_OK) return rc;
+    return rm != CM3D_OK ? rm : s;
+}
+
+extern "C" int cm3d_pipe_acquire(void *pipe, int32_t slot) { return pipe_take((Pipe *)pipe, slot); }
+
+extern "C" int cm3d_pipe_release(void *pipe, int32_t slot)
+{
+    Pipe *p = (Pipe *)pipe;
+    if (!p || slot < 0 || slot >= p->sched.depth) return CM3D_ERR_ARG;
+    return pipe_mark(p, slot);
+}
+
+extern "C" int cm3d_pipe_wait(void *pipe, int32_t slot)
+{
+    Pipe *p = (Pipe *)pipe;
+    if (!p || slot < 0 || slot >= p->sched.depth) return CM3D_ERR_ARG;
+    if (!p->recorded[slot]) return CM3D_OK;
+    return hipEventSynchronize(p->done[slot]) == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
+}
+
+extern "C" int cm3d_pipe_pin(void *pipe)
+{
+    if (!pipe) return CM3D_ERR_ARG;
+    ((Pipe *)pipe)->sched.pin();
+    return CM3D_OK;
+}
+
+extern "C" int cm3d_pipe_last_stream(const void *pipe, int32_t slot)
+{
+    const Pipe *p = (const Pipe *)pipe;
+    if (!p || slot < 0 || slot >= p->sched.depth) return CM3D_ERR_ARG;
+    return p->sched.last[slot];
+}

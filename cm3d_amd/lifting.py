@@ -11,6 +11,7 @@ from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence
 
+import ctypes
 import os
 import zlib
 
@@ -435,6 +436,7 @@ class LiftEngine:
         self._md_hint = os.environ.get("CM3D_MD_HINT", "1") == "1"
         self._md_fb = torch.ones(4, dtype=torch.int32).pin_memory()
         self._md_fb_np = self._md_fb.numpy()
+        self.graph_captured = False                          # capture_graph: a LiftPipeline then keeps every slot on its own stream
         self.prior_wlh = torch.from_numpy(self.classes.prior_wlh).to(d)
         self.is_vehicle = torch.from_numpy(self.classes.is_vehicle).to(d)
         self.nms_thr = torch.from_numpy(self.classes.nms_thr).to(d)
@@ -547,8 +549,57 @@ class LiftEngine:
         b.rle_counts = t(hb.rle_counts.view(np.int32))
         b.intensity = t(hb.intensity) if hb.intensity is not None else None
         b.raw = t(hb.raw)
+        # what a steady-state pass hands to the library, filled once (cm3d_lift_pass: LiftPipeline's native submitter)
+        b.native_ok = b.fused and b.pose_rt is None and b.pose_inv is None and b.mask_wh is None and not self.obb
+        b.desc = self._pass_descriptor(b) if b.native_ok else None
+        b.desc_ref = ctypes.byref(b.desc) if b.native_ok else None
         self.b = b
         return b
+
+    def _pass_descriptor(self, b):
+        """cm3d_lift_pass_desc of the resident batch: the arguments of the six calls `run` makes for run-length masks on the fused-sweeps
+        path (stage_masks(reset=True), stage_sweep_project, stage_compact, stage_medoid, stage_lanes, stage_boxes), name for name."""
+        d = _lib.LiftPassDesc()
+        d.size = ctypes.sizeof(_lib.LiftPassDesc)
+        for name in ("rle_counts", "rle_off", "packed", "bbox", "rle_ws", "status", "hit_count", "removed_bits", "raw", "intensity",
+                     "sweep_row_off", "sweep_xf", "frame_sweep_off", "points", "pt_off", "cams", "mask_off", "mask_cam", "hit_words", "pg_ws",
+                     "hit_off", "tile_off", "hit_idx", "hit_xyz", "tile_work", "medoid_pos", "centroid", "colsum", "ws", "centroid_g",
+                     "mask_frame", "lane", "lane_off", "frame_lane", "grid", "lane_idx", "lane_dist", "class_id", "score", "ego_xyz", "box",
+                     "flags"):
+            setattr(d, name, _ptr(getattr(b, name)) or None)
+        for name in ("prior_wlh", "is_vehicle", "nms_group", "nms_thr"):
+            setattr(d, name, _ptr(getattr(self, name)))
+        d.md_feedback = self._md_fb.data_ptr()
+        d.rle_ws_bytes, d.removed_words, d.pg_ws_bytes, d.ws_bytes = b.rle_ws_bytes, b.removed_words, b.pg_ws_bytes, b.ws_bytes
+        d.n_masks, d.total_runs, d.W, d.H = b.M, b.hb.rle_counts.size, b.W, b.H
+        d.raw_stride, d.n_sweeps, d.max_sweeps_per_frame, d.pt_cap = b.hb.raw_stride, b.S, b.max_sweeps, b.pt_cap
+        d.n_frames, d.max_pts_per_frame, d.n_cams, d.planes, d.idx_cap = b.F, b.max_pts, b.hb.n_cams, b.planes, b.idx_cap
+        d.n_tables, d.n_lane_points, d.n_classes = b.n_tables, b.n_lane, len(self.classes.names)
+        d.md_hint, d.halfw, d.min_dist = int(self._md_hint), b.halfw, self.min_dist
+        return d
+
+    def native_pass_ready(self, masks, project_events=None, stage_events=None):
+        """True when the next pass over the resident batch is the steady-state nuScenes pass cm3d_lift_pass makes: run-length masks, fused
+        sweeps, one mask size, no Waymo pose, no OBB, no per-stage timing events, and the lane index built and seen complete (a pass that has to build
+        it, or to wait for the build, goes through `run`)."""
+        b = self.b
+        if masks != "rle" or project_events is not None or stage_events is not None or b is None or not b.native_ok:
+            return False
+        ln = self._lane
+        if not ln["built"]:
+            return False
+        if not ln.get("done"):
+            if not ln["built_event"].query():
+                return False
+            ln["done"] = True                # the build has completed: nothing left to wait for (wait_lane_grid)
+        return os.environ.get("CM3D_FUSED_RESET", "1") != "0"
+
+    def refresh_pass_descriptor(self):
+        """What may change between two passes over one resident batch: the hint switch and the lane index in use."""
+        d = self.b.desc
+        d.md_hint = int(self._md_hint)
+        d.grid = self.b.grid.data_ptr()
+        return self.b.desc_ref
 
     def decode_masks_dense(self):
         """a1: RLE -> dense uint8 (M,H,W) on the device (pycocotools.mask.decode, reference :425)."""
@@ -768,6 +819,7 @@ class LiftEngine:
         torch.cuda.synchronize(self.dev)
         if self._lane is not None and self._lane["built"]:
             self._lane["done"] = True            # everything issued so far has completed, the lane index among it
+        self.graph_captured = True
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             self.run(masks=masks)
@@ -866,13 +918,26 @@ class LiftEngine:
 
 
 class LiftPipeline:
-    """Keeps `depth` independent lift batches in flight: one LiftEngine (own device buffers) per HIP stream, batches
-    issued round-robin.  Frames are independent (SURVEY 8e), so consecutive batches of a job never wait for each other;
-    a pass is a chain of ~12 dependent launches whose tail (scans, lane search, boxes: a few hundred waves) leaves most
-    of the 256 CUs idle, and the next batch's HBM-bound stages run there.  Measured on the C2 batch: 863 k frames/s with
-    one batch in flight, 997 k with two, 1.05-1.08 M with three (four or more: no further gain)."""
+    """Keeps `depth` independent lift batches in flight: one LiftEngine (own device buffers) per slot, batches issued round-robin.
+    Frames are independent, so consecutive batches of a job never wait for each other; a pass is a chain of ~12
+    dependent launches whose tail (scans, lane search, boxes: a few hundred waves) leaves most of the 256 CUs idle, and the next
+    batch's HBM-bound stages run there.
 
-    def __init__(self, device="cuda:0", depth=3, **engine_kw):
+    Which stream a pass runs on is decided by the library (cm3d_pipe_*, csrc/pipe_sched.h): work of streams that share a hardware queue
+    runs in order, so no more streams execute passes than the process has queues for -- min(depth, 4, GPU_MAX_HW_QUEUES - 1), the
+    variable read, never set; 4 queues when it is unset.  With that many streams or more than slots, slot s runs on `streams[s]` as
+    it always did.  With fewer, pass number k runs on `streams[k % n]`, the slots take turns, and a slot's event keeps two passes of
+    one slot in order when they land on different streams ("Passes rotate over as many streams as the process has queues
+    for").  `exec_streams` overrides the policy (tests).  A steady-state nuScenes pass is enqueued by one library call (cm3d_lift_pass);
+    every other pass is `LiftEngine.run` on the chosen stream.
+
+    Rule for callers that use `streams[slot]` or `engines[slot]` directly (an upload, a pass stage by stage, a graph capture): the device
+    must be idle before and after -- `torch.cuda.synchronize()` on both sides --, because the slot's last pass need not have run on
+    `streams[slot]`.  Once an engine of the pipeline has captured a graph the pipeline stops rotating for good: the graph replays on the
+    stream it was captured on, so slot s stays on `streams[s]`.  `submit` needs the slot collected (`collect`, `collect_records`,
+    `check_status`) before it comes round again: the buffers it replaces may be in use on another stream until then."""
+
+    def __init__(self, device="cuda:0", depth=3, exec_streams=None, **engine_kw):
         if depth < 1:
             raise ValueError("depth >= 1")
         self.dev = torch.device(device)
@@ -882,58 +947,124 @@ class LiftPipeline:
         self.masks = [None] * depth
         self.uploaded = [torch.cuda.Event() for _ in range(depth)]      # recorded behind a slot's H2D copies (submit)
         self._next = 0
-        # With batches in flight the projection launch leaves part of the chip to the other batches' kernels (two workgroups per CU
-        # instead of three, one with four batches in flight: cm3d_project_workgroups_per_cu -- process-wide, results unaffected): +1-2 %
-        # frames/s at depth 3, +4 % at depth 4, while one batch at a time runs fastest with the launch filling the chip.
-        # CM3D_PIPE_WG_PER_CU overrides (0: never ask).  Four batches in flight need GPU_MAX_HW_QUEUES >= 8 in the environment before the HIP
-        # runtime starts (bench.py sets it): on the default four hardware queues a fourth stream shares one and the pass gets slower.
-        want = int(os.environ.get("CM3D_PIPE_WG_PER_CU", "1" if depth >= 4 else "2"))       # (four in flight: 2.51 M frames/s at 1, 2.46 at 2, 2.40 at 3)
-        if depth >= 2 and want > 0:
-            self.engines[0].lib.cm3d_project_workgroups_per_cu(want)
-        elif depth == 1:
-            self.engines[0].lib.cm3d_project_workgroups_per_cu(0)
+        self.native_passes = 0                               # passes enqueued by cm3d_lift_pass
+        self._pinned = False
+        L = self.lib = self.engines[0].lib
+        handles = (ctypes.c_void_p * depth)(*[s.cuda_stream for s in self.streams])
+        with torch.cuda.device(self.dev):
+            self._h = L.cm3d_pipe_create(depth, int(exec_streams or 0), handles)
+        if not self._h:
+            raise Cm3dError("cm3d_pipe_create failed")
+        self.exec_streams = int(L.cm3d_pipe_exec_streams(self._h))
+        # With batches executing side by side the projection launch leaves part of the chip to the other batches' kernels (two workgroups
+        # per CU instead of three, one with four streams executing: cm3d_project_workgroups_per_cu -- process-wide, results unaffected):
+        # +1-2 % frames/s at three, +4 % at four, while one batch at a time runs fastest with the launch filling the chip.  It follows the
+        # streams that execute, not the slots.  CM3D_PIPE_WG_PER_CU overrides (0: never ask).
+        want = int(os.environ.get("CM3D_PIPE_WG_PER_CU", "1" if self.exec_streams >= 4 else "2"))
+        if self.exec_streams >= 2 and want > 0:
+            L.cm3d_project_workgroups_per_cu(want)
+        elif self.exec_streams == 1:
+            L.cm3d_project_workgroups_per_cu(0)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self.lib.cm3d_pipe_destroy(h)
 
     @property
     def depth(self):
         return len(self.engines)
 
+    def last_stream(self, slot):
+        """Index into `streams` of the stream the slot's last pass went to (-1 before the first)."""
+        return int(self.lib.cm3d_pipe_last_stream(self._h, slot))
+
+    def _pin_if_captured(self):
+        if not self._pinned and any(e.graph_captured for e in self.engines):
+            self.lib.cm3d_pipe_pin(self._h)
+            self._pinned = True
+
+    def _acquire(self, slot):
+        """The stream of the slot's next pass, ordered behind the slot's previous one."""
+        idx = self.lib.cm3d_pipe_acquire(self._h, slot)
+        if idx < 0:
+            check(idx, "cm3d_pipe_acquire")
+        return idx
+
+    def _wait(self, slot):
+        check(self.lib.cm3d_pipe_wait(self._h, slot), "cm3d_pipe_wait")
+        idx = self.last_stream(slot)
+        return self.streams[idx if idx >= 0 else slot]
+
     def submit(self, hb: HostBatch, masks="rle", stage_events=None):
-        """Uploads `hb` into the next slot and issues one pass over it on that slot's stream (asynchronous).
+        """Uploads `hb` into the next slot and issues one pass over it on the stream chosen for it (asynchronous).
         Returns the slot; `collect(slot)` must be called before the slot comes round again."""
         slot = self._next
         self._next = (slot + 1) % self.depth
         eng = self.engines[slot]
-        with torch.cuda.stream(self.streams[slot]):
-            eng.upload(hb)
-            self.uploaded[slot].record(self.streams[slot])
-            if masks == "dense":
-                eng.decode_masks_dense()
-            eng.run(masks=masks, stage_events=stage_events)
+        self._pin_if_captured()
+        st = self.streams[self._acquire(slot)]
+        try:
+            with torch.cuda.stream(st):
+                eng.upload(hb)
+                self.uploaded[slot].record(st)
+                if masks == "dense":
+                    eng.decode_masks_dense()
+                if eng.native_pass_ready(masks, stage_events=stage_events):
+                    check(self.lib.cm3d_lift_pass(eng.refresh_pass_descriptor(), st.cuda_stream), "cm3d_lift_pass")
+                    self.native_passes += 1
+                else:
+                    eng.run(masks=masks, stage_events=stage_events)
+        finally:
+            self.lib.cm3d_pipe_release(self._h, slot)
         self.masks[slot] = masks
         return slot
 
     def rerun(self, slot, masks=None, project_events=None):
         """Another pass over the batch resident in `slot` (benchmarks)."""
-        with torch.cuda.stream(self.streams[slot]):
-            self.engines[slot].run(masks=masks or self.masks[slot], project_events=project_events)
+        eng = self.engines[slot]
+        mode = masks or self.masks[slot]
+        self._pin_if_captured()
+        if eng.native_pass_ready(mode):
+            # (a pair of events around the projection kernel rides on the native pass: the library records them, as in `run`)
+            if project_events is None:
+                rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor())
+            else:
+                e0, e1 = eng._raw_events(project_events)
+                rc = self.lib.cm3d_pipe_submit_timed(self._h, slot, eng.refresh_pass_descriptor(), e0, e1)
+            if rc < 0:
+                check(rc, "cm3d_pipe_submit")
+            self.native_passes += 1
+            return
+        st = self.streams[self._acquire(slot)]
+        try:
+            with torch.cuda.stream(st):
+                eng.run(masks=mode, project_events=project_events)
+        finally:
+            self.lib.cm3d_pipe_release(self._h, slot)
+
+    def check_status(self, slot):
+        """Waits for the slot's last pass and checks its status word."""
+        with torch.cuda.stream(self._wait(slot)):
+            return self.engines[slot].check_status()
 
     def collect_records(self, slot, frame_ids):
-        """Waits for the slot's stream, checks the status word and returns the slot's kept-box records as a DEVICE tensor
+        """Waits for the slot's last pass, checks the status word and returns the slot's kept-box records as a DEVICE tensor
         (kept_box_records): what an entry point hands to the end-of-job gather -- nothing else is downloaded."""
-        self.streams[slot].synchronize()
+        st = self._wait(slot)
         eng = self.engines[slot]
         eng.check_status()
-        with torch.cuda.stream(self.streams[slot]):
+        with torch.cuda.stream(st):
             rec = kept_box_records(eng.b, frame_ids, self.dev)
-        self.streams[slot].synchronize()
+        st.synchronize()
         return rec
 
     def collect(self, slot, full=True):
-        """Waits for the slot's stream only and returns (host batch, numpy results); full=False: per-mask results only
+        """Waits for the slot's last pass only and returns (host batch, numpy results); full=False: per-mask results only
         (LiftEngine.download)."""
-        self.streams[slot].synchronize()
+        st = self._wait(slot)
         eng = self.engines[slot]
-        with torch.cuda.stream(self.streams[slot]):
+        with torch.cuda.stream(st):
             res = eng.download(full=full)
         return eng.b.hb, res
 

@@ -500,6 +500,72 @@ int cm3d_waymo_metrics_sweep(const double *cand_box, const float *cand_heading, 
                              int32_t n_alphas, int64_t *counts, int64_t *heading_sum, int32_t *status, void *workspace,
                              int64_t workspace_bytes, cm3d_stream_t stream);
 
+/* ---- One steady-state nuScenes pass in one call; passes of several batches on as many streams as the process has queues for ----
+ * Added within ABI v5: new symbols only, no existing call changes, so CM3D_ABI_VERSION stays.  Host code (csrc/pipeline.cpp):
+ * no kernel of its own.
+ *
+ * The descriptor holds what the six calls of a pass over resident run lengths take -- cm3d_rle_erode_pack_begin,
+ * cm3d_sweep_project_hits, cm3d_compact_hits, cm3d_medoid2, cm3d_lane_nn, cm3d_box_nms -- under the names their declarations above
+ * use.  `size` is sizeof(cm3d_lift_pass_desc): a caller built against another layout is refused (CM3D_ERR_ARG).  `points`, `intensity`
+ * and `colsum` may be NULL as in those calls; with `points` NULL the compaction re-derives the in-mask points from the raw rows.
+ * `centroid_g` is what the lane search and the boxes read (nuScenes: the same buffer as `centroid`). */
+typedef struct cm3d_lift_pass_desc {
+    int64_t size;
+    /* masks */
+    const uint32_t *rle_counts; const int32_t *rle_off; uint32_t *packed; int32_t *bbox; void *rle_ws; int64_t rle_ws_bytes;
+    /* per-pass state */
+    int32_t *status; int32_t *hit_count; uint32_t *removed_bits; int64_t removed_words;
+    /* sweeps + projection */
+    const float *raw; const float *intensity; const int32_t *sweep_row_off; const float *sweep_xf; const int32_t *frame_sweep_off;
+    float *points; int32_t *pt_off; const float *cams; const int32_t *mask_off; const int32_t *mask_cam; uint32_t *hit_words;
+    void *pg_ws; int64_t pg_ws_bytes;
+    /* compaction + medoid */
+    int32_t *hit_off; int32_t *tile_off; int32_t *hit_idx; float *hit_xyz; int32_t *tile_work; int32_t *medoid_pos; float *centroid;
+    float *colsum; void *ws; int64_t ws_bytes;
+    int32_t *md_feedback;        /* cm3d_medoid2's feedback word: page-locked host memory the device writes; read here for the hint */
+    /* lanes + boxes */
+    const float *centroid_g; const int32_t *mask_frame; const float *lane; const int32_t *lane_off; const int32_t *frame_lane;
+    const void *grid; int32_t *lane_idx; double *lane_dist; const int32_t *class_id; const double *score; const double *prior_wlh;
+    const int32_t *is_vehicle; const int32_t *nms_group; const double *nms_thr; const double *ego_xyz; double *box; int32_t *flags;
+    /* sizes */
+    int32_t n_masks, total_runs, W, H, raw_stride, n_sweeps, max_sweeps_per_frame, pt_cap, n_frames, max_pts_per_frame, n_cams, planes,
+            idx_cap, n_tables, n_lane_points, n_classes;
+    int32_t md_hint;             /* non-zero: ask for the one-pass medoid route when *md_feedback says the last batch held no long list */
+    float halfw, min_dist;
+} cm3d_lift_pass_desc;
+
+/* Exactly those six calls, in that order, on `stream`; returns the first error.  Launches, arguments and order are those of
+ * cm3d_amd.lifting.LiftEngine.run for run-length masks on the fused-sweeps path with the lane index built. */
+int cm3d_lift_pass(const cm3d_lift_pass_desc *desc, cm3d_stream_t stream);
+
+/* min(depth, 4, max(1, hw_queues - 1)): the streams that execute passes at the same time (csrc/pipe_sched.h).  hw_queues <= 0: the
+ * value of GPU_MAX_HW_QUEUES in the environment, 4 when it is not set. */
+int cm3d_pipe_exec_streams_for(int32_t depth, int32_t hw_queues);
+
+/* A pipeline of `depth` slots over the caller's streams (`streams[depth]`, kept alive by the caller).  exec_streams <= 0: the policy
+ * above; else that many (at most depth).  With fewer executing streams than slots, pass number k goes to streams[k % n], and a slot
+ * whose previous pass ran on another stream is ordered behind it by the slot's event (not waited for when it has already fired).
+ * With n >= depth slot s always runs on streams[s] and no event is ever waited for.  NULL on a bad argument or a runtime error. */
+void *cm3d_pipe_create(int32_t depth, int32_t exec_streams, const cm3d_stream_t *streams);
+void cm3d_pipe_destroy(void *pipe);
+int cm3d_pipe_exec_streams(const void *pipe);
+/* Picks the stream of the slot's next pass, orders it behind the slot's previous pass, enqueues cm3d_lift_pass there and records the
+ * slot's event.  Returns the stream's index (>= 0) or an error code (< 0). */
+int cm3d_pipe_submit(void *pipe, int32_t slot, const cm3d_lift_pass_desc *desc);
+/* The same with cm3d_sweep_project_hits' optional ev_start / ev_stop (hipEvent_t, NULL = none) recorded around the projection kernel:
+ * a pass that is timed this way is enqueued like every other, so that timing a pass does not change what the host does for it. */
+int cm3d_pipe_submit_timed(void *pipe, int32_t slot, const cm3d_lift_pass_desc *desc, void *ev_start, void *ev_stop);
+/* The same choice and ordering without the pass, for work the caller enqueues itself on streams[returned index]; the caller then
+ * calls cm3d_pipe_release, which records the slot's event behind that work. */
+int cm3d_pipe_acquire(void *pipe, int32_t slot);
+int cm3d_pipe_release(void *pipe, int32_t slot);
+/* Blocks the host until the slot's last pass (submit or acquire/release) has completed. */
+int cm3d_pipe_wait(void *pipe, int32_t slot);
+/* From now on slot s stays on streams[s] (something else, a captured graph, runs there).  Returns CM3D_OK. */
+int cm3d_pipe_pin(void *pipe);
+/* Index of the stream of the slot's last pass, -1 before the first. */
+int cm3d_pipe_last_stream(const void *pipe, int32_t slot);
+
 #ifdef __cplusplus
 }
 #endif
