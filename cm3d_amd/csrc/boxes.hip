@@ -369,6 +369,20 @@ static __device__ __forceinline__ void nms_phase(int nm, int lane_id, const doub
     }
 }
 
+// One lane of a wave reads a double of lane `src` (wave-uniform).
+static __device__ __forceinline__ double bn_readlane(double v, int src)
+{
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
+}
+
+// LDS of k_box_nms for frames of up to `cap` masks: nms_phase's arrays one behind the other; none for cap <= 64 (a wave's registers)
+static inline size_t bn_lds_bytes(int cap) { return cap <= 64 ? 0 : (size_t)((cap + 7) & ~7) * (3 * sizeof(double) + 2 * sizeof(int) + 3); }
+
+// WAYMO: centroids arrive in the global frame, boxes leave in the vehicle frame (pose_inv); else nuScenes: boxes live in the global
+// frame, the ego position is needed for the push-back direction.  (A template parameter: the pose's 24 registers were live on nuScenes.)
+// cap: no frame is taken to have more masks (the launch's LDS is sized by it); the masks of a frame beyond it get the record of a
+// mask without a medoid.
+template <bool WAYMO>
 __global__ __launch_bounds__(64) void k_box_nms(const float *__restrict__ centroid, const int32_t *__restrict__ medoid_pos,
                                                 const int32_t *__restrict__ mask_off, const int32_t *__restrict__ class_id,
                                                 const double *__restrict__ score, const float *__restrict__ lane,
@@ -377,24 +391,29 @@ __global__ __launch_bounds__(64) void k_box_nms(const float *__restrict__ centro
                                                 const double *__restrict__ prior_wlh, const int32_t *__restrict__ is_vehicle,
                                                 const int32_t *__restrict__ nms_group, const double *__restrict__ nms_thr,
                                                 int n_classes, const double *__restrict__ ego_xyz,
-                                                const float *__restrict__ pose_inv, double *__restrict__ box,
+                                                const float *__restrict__ pose_inv, int cap, double *__restrict__ box,
                                                 int32_t *__restrict__ flags)
 {
-    __shared__ double s_x[BN_MAX], s_y[BN_MAX], s_s[BN_MAX];
-    __shared__ int s_lab[BN_MAX], s_order[BN_MAX];
-    __shared__ unsigned char s_valid[BN_MAX], s_sup[BN_MAX], s_keep[BN_MAX];
+    extern __shared__ __align__(8) double s_bn[];
+    const int cap8 = (cap + 7) & ~7;
+    double *const s_x = s_bn, *const s_y = s_x + cap8, *const s_s = s_y + cap8;
+    int *const s_lab = reinterpret_cast<int *>(s_s + cap8), *const s_order = s_lab + cap8;
+    unsigned char *const s_valid = reinterpret_cast<unsigned char *>(s_order + cap8), *const s_sup = s_valid + cap8, *const s_keep = s_sup + cap8;
     const int f = blockIdx.x;
     const int m0 = mask_off[f];
-    const int nm = min(mask_off[f + 1] - m0, BN_MAX);
+    const int nm_all = min(mask_off[f + 1] - m0, BN_MAX);
+    const int nm = min(nm_all, cap);
     const int lane_id = threadIdx.x;
-    // nuScenes: boxes live in the global frame, the ego position is needed for the push-back direction.
-    // Waymo (pose_inv != null): centroids arrive in the global frame, boxes leave in the vehicle frame.
-    const bool waymo = pose_inv != nullptr;
-    const double ex0 = waymo ? 0.0 : ego_xyz[3 * f], ey0 = waymo ? 0.0 : ego_xyz[3 * f + 1];
-    double Pi[12];
-    if (waymo)
+    // up to 64 masks: lane k keeps mask k, the NMS runs on registers and ballots (no LDS in the launch when no frame has more)
+    const bool in_regs = nm <= 64;
+    const double ex0 = WAYMO ? 0.0 : ego_xyz[3 * f], ey0 = WAYMO ? 0.0 : ego_xyz[3 * f + 1];
+    double Pi[WAYMO ? 12 : 1];
+    if (WAYMO)
         for (int q = 0; q < 12; ++q) Pi[q] = (double)pose_inv[(size_t)f * 16 + q];   // rows 0..2 of the 4x4, float32 -> float64
     const int ltab = lane_off[frame_lane[f]];
+    double r_x = 0.0, r_y = 0.0, r_s = 0.0, r_thr = 0.0;
+    int r_lab = 0;
+    bool r_valid = false;
 
     for (int k = lane_id; k < nm; k += 64) {
         const int m = m0 + k;
@@ -409,10 +428,12 @@ __global__ __launch_bounds__(64) void k_box_nms(const float *__restrict__ centro
         const float yaw_m = lane[(size_t)(valid ? max(ltab + li, 0) : 0) * 3 + 2];        // (a mask without a medoid: the array's first point, unused)
         const int veh = is_vehicle[cls], grp_c = nms_group[cls];
         const double prior_l = prior_wlh[3 * cls + 0], prior_w = prior_wlh[3 * cls + 1];
+        // (the register NMS compares against the mask's own threshold: requested here, behind the trigonometry when it is needed)
+        if (in_regs && valid) r_thr = nms_thr[grp_c];
         double tx = 0.0, ty = 0.0, tz = 0.0, qw = 1.0, qz = 0.0, yaw_out = 0.0, ld = 0.0;
         if (valid) {
             double cx = (double)c_x, cy = (double)c_y, cz = (double)c_z;
-            if (waymo) {
+            if (WAYMO) {
                 // src/waymo/2d_to_3d.py:812-816: np.dot(inv(float32 pose), [centroid, 1]) in float64
                 const double gx = cx, gy = cy, gz = cz;
                 cx = Pi[0] * gx + Pi[1] * gy + Pi[2] * gz + Pi[3];
@@ -446,25 +467,69 @@ __global__ __launch_bounds__(64) void k_box_nms(const float *__restrict__ centro
                 if (o1 != o1 || o2 != o2) off = NAN;
                 tx = cx + off * cos(alpha);
                 ty = cy + off * sin(alpha);
-                if (waymo) {
+                if (WAYMO) {
                     // src/waymo/2d_to_3d.py:978-1001: align_mat = R_inv . Rz(global lane yaw); heading = as_euler('xyz')[2]
                     qw = atan2(Pi[4] * cs + Pi[5] * sn, Pi[0] * cs + Pi[1] * sn);
                     qz = 0.0;
                 }
-            } else if (waymo) {
+            } else if (WAYMO) {
                 qw = 0.0; qz = 0.0;          // heading of identity (:1003-1010)
             }
         }
         double *b = box + (size_t)m * CM3D_BOX_STRIDE;
         b[0] = tx; b[1] = ty; b[2] = tz; b[3] = qw; b[4] = qz; b[5] = yaw_out; b[6] = ld; b[7] = score_m; b[8] = (double)cls;
-        s_x[k] = tx; s_y[k] = ty; s_s[k] = score_m; s_lab[k] = grp_c;
-        s_valid[k] = valid; s_sup[k] = 0; s_keep[k] = 0;
+        if (in_regs) {
+            r_x = tx; r_y = ty; r_s = score_m; r_lab = grp_c; r_valid = valid;
+        } else {
+            s_x[k] = tx; s_y[k] = ty; s_s[k] = score_m; s_lab[k] = grp_c;
+            s_valid[k] = valid; s_sup[k] = 0; s_keep[k] = 0;
+        }
     }
-    nms_phase(nm, lane_id, nms_thr, s_x, s_y, s_s, s_lab, s_order, s_valid, s_sup, s_keep);
-    for (int k = lane_id; k < nm; k += 64) {
-        const int fl = (s_valid[k] ? 1 : 0) | (s_keep[k] ? 2 : 0);
-        flags[m0 + k] = fl;
-        box[(size_t)(m0 + k) * CM3D_BOX_STRIDE + 9] = (double)fl;
+    if (in_regs) {
+        // The same greedy pass as nms_phase, lane k = mask k: order = descending score, ties by descending index; the box of rank r, unless
+        // suppressed, is kept and suppresses every later box of its group within that box's own threshold.  Same comparisons on the same
+        // float64 values, so the same flags.
+        const uint64_t vmask = __ballot(r_valid);
+        int rank = 0;
+        for (int j = 0; j < nm; ++j) {                       // (uniform j: two readlanes, no LDS)
+            const double sj = bn_readlane(r_s, j);
+            if ((vmask >> j) & 1) rank += (sj > r_s || (sj == r_s && j > lane_id)) ? 1 : 0;
+        }
+        const int nv = (int)__popcll(vmask);
+        uint64_t sup = 0, keep = 0;
+        for (int r = 0; r < nv; ++r) {
+            const uint64_t sel = __ballot(r_valid && rank == r);
+            if (!sel) continue;                              // (NaN scores: ranks that nobody holds)
+            const int i = (int)__builtin_ctzll(sel);
+            if ((sup >> i) & 1) continue;
+            keep |= 1ull << i;
+            const double xi = bn_readlane(r_x, i), yi = bn_readlane(r_y, i);
+            const int li = __builtin_amdgcn_readlane(r_lab, i);
+            const double dx = xi - r_x, dy = yi - r_y;
+            const double dist = dx * dx + dy * dy;
+            sup |= __ballot(r_valid && rank > r && dist <= r_thr && r_lab == li);
+        }
+        if (lane_id < nm) {
+            const int fl = (r_valid ? 1 : 0) | ((keep >> lane_id) & 1 ? 2 : 0);
+            flags[m0 + lane_id] = fl;
+            box[(size_t)(m0 + lane_id) * CM3D_BOX_STRIDE + 9] = (double)fl;
+        }
+    } else {
+        nms_phase(nm, lane_id, nms_thr, s_x, s_y, s_s, s_lab, s_order, s_valid, s_sup, s_keep);
+        for (int k = lane_id; k < nm; k += 64) {
+            const int fl = (s_valid[k] ? 1 : 0) | (s_keep[k] ? 2 : 0);
+            flags[m0 + k] = fl;
+            box[(size_t)(m0 + k) * CM3D_BOX_STRIDE + 9] = (double)fl;
+        }
+    }
+    // masks beyond the launch's bound (the projection took none of their points: no medoid): the record of a mask without one
+    for (int k = nm + lane_id; k < nm_all; k += 64) {
+        const int m = m0 + k;
+        int cls = class_id[m];
+        if (cls < 0 || cls >= n_classes) cls = 0;
+        double *b = box + (size_t)m * CM3D_BOX_STRIDE;
+        b[0] = 0.0; b[1] = 0.0; b[2] = 0.0; b[3] = 1.0; b[4] = 0.0; b[5] = 0.0; b[6] = 0.0; b[7] = score[m]; b[8] = (double)cls; b[9] = 0.0;
+        flags[m] = 0;
     }
 }
 
@@ -496,6 +561,30 @@ extern "C" int cm3d_centroid_transform(const float *centroid_in, const int32_t *
     return CM3D_OK;
 }
 
+extern "C" int cm3d_box_nms_bounded(const float *centroid, const int32_t *medoid_pos, const int32_t *mask_off, int32_t n_frames,
+                                    int32_t n_masks, const int32_t *class_id, const double *score, const float *lane,
+                                    const int32_t *lane_off, const int32_t *frame_lane, const int32_t *lane_idx,
+                                    const double *lane_dist, const double *prior_wlh, const int32_t *is_vehicle,
+                                    const int32_t *nms_group, const double *nms_thr, int32_t n_classes, const double *ego_xyz,
+                                    const float *pose_inv, int32_t max_masks_per_frame, double *box, int32_t *flags, cm3d_stream_t stream)
+{
+    if (!centroid || !medoid_pos || !mask_off || !class_id || !score || !lane || !lane_off || !frame_lane || !lane_idx ||
+        !lane_dist || !prior_wlh || !is_vehicle || !nms_group || !nms_thr || (!ego_xyz && !pose_inv) || !box || !flags)
+        return CM3D_ERR_ARG;
+    if (n_frames <= 0 || n_masks <= 0 || n_classes <= 0 || max_masks_per_frame <= 0) return CM3D_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int cap = max_masks_per_frame < BN_MAX ? max_masks_per_frame : BN_MAX;
+    const size_t lds = bn_lds_bytes(cap);
+    if (pose_inv)
+        hipLaunchKernelGGL(k_box_nms<true>, dim3(n_frames), dim3(64), lds, st, centroid, medoid_pos, mask_off, class_id, score, lane,
+                           lane_off, frame_lane, lane_idx, lane_dist, prior_wlh, is_vehicle, nms_group, nms_thr, n_classes, ego_xyz, pose_inv, cap, box, flags);
+    else
+        hipLaunchKernelGGL(k_box_nms<false>, dim3(n_frames), dim3(64), lds, st, centroid, medoid_pos, mask_off, class_id, score, lane,
+                           lane_off, frame_lane, lane_idx, lane_dist, prior_wlh, is_vehicle, nms_group, nms_thr, n_classes, ego_xyz, pose_inv, cap, box, flags);
+    CM3D_CHECK_LAUNCH();
+    return CM3D_OK;
+}
+
 extern "C" int cm3d_box_nms(const float *centroid, const int32_t *medoid_pos, const int32_t *mask_off, int32_t n_frames,
                             int32_t n_masks, const int32_t *class_id, const double *score, const float *lane,
                             const int32_t *lane_off, const int32_t *frame_lane, const int32_t *lane_idx,
@@ -503,15 +592,9 @@ extern "C" int cm3d_box_nms(const float *centroid, const int32_t *medoid_pos, co
                             const int32_t *nms_group, const double *nms_thr, int32_t n_classes, const double *ego_xyz,
                             const float *pose_inv, double *box, int32_t *flags, cm3d_stream_t stream)
 {
-    if (!centroid || !medoid_pos || !mask_off || !class_id || !score || !lane || !lane_off || !frame_lane || !lane_idx ||
-        !lane_dist || !prior_wlh || !is_vehicle || !nms_group || !nms_thr || (!ego_xyz && !pose_inv) || !box || !flags)
-        return CM3D_ERR_ARG;
-    if (n_frames <= 0 || n_masks <= 0 || n_classes <= 0) return CM3D_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_box_nms, dim3(n_frames), dim3(64), 0, st, centroid, medoid_pos, mask_off, class_id, score, lane,
-                       lane_off, frame_lane, lane_idx, lane_dist, prior_wlh, is_vehicle, nms_group, nms_thr, n_classes, ego_xyz, pose_inv, box, flags);
-    CM3D_CHECK_LAUNCH();
-    return CM3D_OK;
+    return cm3d_box_nms_bounded(centroid, medoid_pos, mask_off, n_frames, n_masks, class_id, score, lane, lane_off, frame_lane, lane_idx,
+                                lane_dist, prior_wlh, is_vehicle, nms_group, nms_thr, n_classes, ego_xyz, pose_inv, CM3D_MAX_MASKS_PER_FRAME,
+                                box, flags, stream);
 }
 
 

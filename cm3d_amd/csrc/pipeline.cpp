@@ -38,9 +38,11 @@ static int lift_pass(const cm3d_lift_pass_desc *d, void *ev_start, void *ev_stop
     rc = cm3d_lane_nn(d->centroid_g, d->medoid_pos, d->mask_frame, d->n_masks, d->lane, d->lane_off, d->frame_lane, d->n_tables,
                       d->n_lane_points, d->grid, d->lane_idx, d->lane_dist, d->ws, d->ws_bytes, st);
     if (rc != CM3D_OK) return rc;
-    return cm3d_box_nms(d->centroid_g, d->medoid_pos, d->mask_off, d->n_frames, d->n_masks, d->class_id, d->score, d->lane, d->lane_off,
-                        d->frame_lane, d->lane_idx, d->lane_dist, d->prior_wlh, d->is_vehicle, d->nms_group, d->nms_thr, d->n_classes,
-                        d->ego_xyz, nullptr, d->box, d->flags, st);
+    // (`planes` words of mask bits per point: no frame of the batch has more than 32 * planes masks)
+    return cm3d_box_nms_bounded(d->centroid_g, d->medoid_pos, d->mask_off, d->n_frames, d->n_masks, d->class_id, d->score, d->lane,
+                                d->lane_off, d->frame_lane, d->lane_idx, d->lane_dist, d->prior_wlh, d->is_vehicle, d->nms_group, d->nms_thr,
+                                d->n_classes, d->ego_xyz, nullptr, d->planes > 0 && d->planes < CM3D_MAX_MASKS_PER_FRAME / 32 ? 32 * d->planes : CM3D_MAX_MASKS_PER_FRAME,
+                                d->box, d->flags, st);
 }
 
 extern "C" int cm3d_lift_pass(const cm3d_lift_pass_desc *d, cm3d_stream_t st) { return lift_pass(d, nullptr, nullptr, st); }

@@ -364,6 +364,16 @@ int cm3d_box_nms(const float *centroid, const int32_t *medoid_pos, const int32_t
                  const double *lane_dist, const double *prior_wlh, const int32_t *is_vehicle,
                  const int32_t *nms_group, const double *nms_thr, int32_t n_classes, const double *ego_xyz,
                  const float *pose_inv, double *box, int32_t *flags, cm3d_stream_t stream);
+/* The same for a caller that knows max_masks_per_frame, the most masks a frame of the batch has (added within ABI v5): the launch
+ * takes its LDS by that bound instead of by CM3D_MAX_MASKS_PER_FRAME -- none up to 64, where a frame's NMS runs in one wave's
+ * registers -- and finds room beside the kernels of other passes sooner.  A frame with more masks than the bound gets, for the masks
+ * beyond it, the record of a mask without points (flags 0).  cm3d_box_nms is this call with CM3D_MAX_MASKS_PER_FRAME. */
+int cm3d_box_nms_bounded(const float *centroid, const int32_t *medoid_pos, const int32_t *mask_off, int32_t n_frames,
+                         int32_t n_masks, const int32_t *class_id, const double *score, const float *lane,
+                         const int32_t *lane_off, const int32_t *frame_lane, const int32_t *lane_idx,
+                         const double *lane_dist, const double *prior_wlh, const int32_t *is_vehicle,
+                         const int32_t *nms_group, const double *nms_thr, int32_t n_classes, const double *ego_xyz,
+                         const float *pose_inv, int32_t max_masks_per_frame, double *box, int32_t *flags, cm3d_stream_t stream);
 
 /* a17 (Waymo): medoid in the vehicle frame -> global frame, float32 rotate then translate
  * (src/waymo/2d_to_3d.py:684-690).  pose_rt float[F][12]: [0..8] rotation row-major, [9..11] translation. */
