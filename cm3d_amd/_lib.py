@@ -26,6 +26,10 @@ WM_BOX_STRIDE = 8        # doubles per box of cm3d_waymo_metrics
 WM_BREAKDOWNS = 16
 WM_CUTOFFS = 101
 WM_SWEEP_MAX_ALPHAS = 1024   # alphas of one cm3d_waymo_metrics_sweep call
+NUSC_MAX_CAND = 1024     # candidates of one group of cm3d_nusc_match
+NUSC_MAX_GT = 256        # ground-truth boxes of one group
+NUSC_MAX_TH = 4
+NUSC_MAX_ALPHAS = 1024   # alphas of one cm3d_nusc_match call
 RAW_QUADS = 3            # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -78,6 +82,8 @@ SIGNATURES = {
     "cm3d_waymo_metrics": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _p, _p, _p, _p, _i64, _p]),
     "cm3d_waymo_metrics_sweep_workspace_bytes": (_i64, [_i64]),
     "cm3d_waymo_metrics_sweep": (_i32, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _p, _i32, _p, _p, _p, _p, _i64, _p]),
+    "cm3d_nusc_match_workspace_bytes": (_i64, [_i32, _i64, _i32]),
+    "cm3d_nusc_match": (_i32, [_p, _p, _p, _p, _p, _p, _p, _i32, _i64, _p, _i32, _p, _i32, _p, _p, _p, _p, _i64, _p]),
     "cm3d_lift_pass": (_i32, [_p, _p]),
     "cm3d_pipe_exec_streams_for": (_i32, [_i32, _i32]),
     "cm3d_pipe_create": (_p, [_i32, _i32, _p]),

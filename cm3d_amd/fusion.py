@@ -353,3 +353,97 @@ def waymo_grid_search_device(pred_objs, sam3d_objs, gt_objs, out_path, best_path
         with open(best_path, "wb") as f:
             f.write(wm.encode_objects(fuse_waymo(pb, ps, sb, ss, pm, sm, best_alpha)))
     return best_alpha, best_score, scores
+
+
+# ------------------------------------------------------------------ nuScenes: every alpha from one matcher call
+def nusc_candidates(pred_box_dict, pred_supp_dict, sam3d_box_dict, sam3d_supp_dict, pred_matches, sam3d_matches):
+    """Everything fuse can emit at some alpha, in the order it emits it into each sample's list, samples in the order fuse's
+    result dict first gets them (neither depends on alpha): (boxes, kind, p, s).  kind 0 an unmatched prediction (score p),
+    kind 1 an unmatched SAM3D box (score clip(s * alpha)), then per matched pair two neighbours of which every alpha takes one:
+    kind 2 the prediction's box (score p, taken unless s * alpha > p) and kind 3 the SAM3D box under the prediction's name and
+    attribute (score clip(s * alpha)).  The boxes are _box_dict's, with the score of the file where it is fixed (kinds 0, 2)."""
+    res = {}
+
+    def add(ts, b, supp, kd, p_score, s_score):
+        res.setdefault(ts, []).append((_box_dict(ts, b, supp[3], p_score if kd in (0, 2) else None, supp[0]), kd,
+                                       0.0 if p_score is None else p_score, 0.0 if s_score is None else s_score))
+    for ts in pred_box_dict:
+        matched = set(pred_matches[ts])
+        for i, b in enumerate(pred_box_dict[ts]):
+            if i not in matched:
+                add(ts, b, pred_supp_dict[ts][i], 0, pred_supp_dict[ts][i][1], None)
+    for ts in sam3d_box_dict:
+        matched = set(sam3d_matches.get(ts, []))
+        for i, b in enumerate(sam3d_box_dict[ts]):
+            if i not in matched:
+                add(ts, b, sam3d_supp_dict[ts][i], 1, None, sam3d_supp_dict[ts][i][1])
+    for ts in pred_matches:
+        for k, pid in enumerate(pred_matches[ts]):
+            sid = sam3d_matches[ts][k]
+            ps = pred_supp_dict[ts][pid]
+            add(ts, pred_box_dict[ts][pid], ps, 2, ps[1], sam3d_supp_dict[ts][sid][1])
+            add(ts, sam3d_box_dict[ts][sid], ps, 3, ps[1], sam3d_supp_dict[ts][sid][1])
+    flat = [c for ts in res for c in res[ts]]
+    return ([c[0] for c in flat], np.array([c[1] for c in flat], np.int32).reshape(len(flat)),
+            np.array([c[2] for c in flat], np.float64).reshape(len(flat)), np.array([c[3] for c in flat], np.float64).reshape(len(flat)))
+
+
+def grid_search_device(pred_objects, sam3d_objects, scorer, out_path, best_path, iou=0.2, verbose=True, matcher=None, output_dir=None):
+    """grid_search with every alpha scored from one matcher call (cm3d_nusc_match through scorer = nusc_eval.GridScorer, which
+    holds the ground truth) instead of a fused file, a reload of the ground truth and a Python matching loop per alpha: match
+    once, pack the candidate superset once, then write two files only -- the last alpha's to out_path and the best alpha's to
+    best_path, as the loop leaves them.  output_dir: also leave the last alpha's metrics files there, as the loop's evaluator
+    does.  Returns (best_alpha, best_score, scores).  A group of the candidate superset over the kernel's capacity falls back to
+    grid_search with nusc_eval.evaluate per alpha (an alpha's file holds one box of every pair, so it can fit where the superset
+    does not); an alpha whose own file is over capacity too -- more than 256 ground-truth boxes in a group, say -- is scored by
+    eval_detection's host loop."""
+    import sys
+
+    from . import _lib, nusc_eval
+    sam3d_box, sam3d_supp, sam3d_max, sam3d_min = parse_results(sam3d_objects["results"], zero_min_quirk=True)
+    pred_box, pred_supp, pred_max, pred_min = parse_results(pred_objects["results"])
+    pred_matches, sam3d_matches = match_samples(pred_box, sam3d_box, iou)
+    alphas = alpha_grid(pred_min, pred_max, sam3d_min, sam3d_max)
+    if not alphas:
+        return 0, -1, []
+
+    def evaluate(path, out_dir=None):
+        return nusc_eval.evaluate(scorer.tables, scorer.cfg, path, scorer.eval_set, out_dir, drivable_filtering=False, object_only=False,
+                                  verbose=False, matcher=matcher)["mean_ap"]
+    try:
+        scores = [float(v) for v in scorer.score(nusc_candidates(pred_box, pred_supp, sam3d_box, sam3d_supp, pred_matches, sam3d_matches),
+                                                 alphas, matcher)]
+    except _lib.Cm3dError as e:
+        if not getattr(e, "status", 0) & 1:
+            raise
+        print(f"grid_search_device: {e}; scoring alpha by alpha instead", file=sys.stderr)
+        scores = []
+
+        def evaluate_and_keep(path):
+            try:
+                scores.append(float(evaluate(path, output_dir)))
+            except _lib.Cm3dError as e2:         # this alpha's own file is over capacity too: the evaluator's host loop takes any size
+                if not getattr(e2, "status", 0) & 1:
+                    raise
+                from . import eval_detection as ev
+                scores.append(float(ev.DetectionEval(scorer.tables, scorer.cfg, path, scorer.eval_set, output_dir, drivable_filtering=False,
+                                                     object_only=False, verbose=False).main()["mean_ap"]))
+            return scores[-1]
+        return grid_search(pred_objects, sam3d_objects, evaluate_and_keep, out_path, best_path, iou, verbose) + (scores,)
+    best_alpha, best_score = 0, -1
+    for alpha, map_score in zip(alphas, scores):
+        if map_score > best_score:
+            best_score, best_alpha = map_score, alpha
+        if verbose:
+            print(f"Curr Score: {map_score},  Curr Alpha: {alpha}")
+            print(f"Best Score: {best_score}, Best Alpha: {best_alpha}")
+            print("-" * 80)
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        json.dump(fuse(pred_box, pred_supp, sam3d_box, sam3d_supp, pred_matches, sam3d_matches, alphas[-1])[0], f)
+    if best_score > -1:
+        with open(best_path, "w") as f:
+            json.dump(fuse(pred_box, pred_supp, sam3d_box, sam3d_supp, pred_matches, sam3d_matches, best_alpha)[0], f)
+    if output_dir:
+        evaluate(out_path, output_dir)
+    return best_alpha, best_score, scores

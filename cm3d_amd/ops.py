@@ -467,3 +467,61 @@ def waymo_metrics_sweep(packed_candidates, alphas, device_ms=None):
             raise err
         out_c[lo:lo + n], out_h[lo:lo + n] = counts.cpu().numpy(), hsum.cpu().numpy()
     return out_c, out_h
+
+
+NUSC_ALPHA_CHUNK = 256       # alphas per cm3d_nusc_match call: bounds the output (one byte per candidate and alpha, 4 T more with indices)
+
+
+def nusc_match(packed, alphas, want_idx=False, device_ms=None):
+    """The nuScenes greedy matching of every group of `packed` (nusc_eval.pack) at every alpha, NUSC_ALPHA_CHUNK alphas per
+    cm3d_nusc_match call.  Returns (tp_bits uint8[A][C]: bit t = TP at dist_th[t], bit 7 = active; match_idx int32[A][C][T] with
+    the group-local ground-truth index or -1 when want_idx, else None).  Raises Cm3dError (its `status` attribute holds the
+    status word) when a group is over capacity.  device_ms: a list that receives every call's device time in ms (events)."""
+    L = _lib.lib()
+    alphas = np.ascontiguousarray(alphas, np.float64).reshape(-1)
+    A = int(alphas.size)
+    co, go = np.asarray(packed["cand_off"], np.int64), np.asarray(packed["gt_off"], np.int64)
+    th = np.ascontiguousarray(packed["dist_th"], np.float64).reshape(-1)
+    n_groups, C, T = int(co.size - 1), int(co[-1]), int(th.size)
+    tp_bits = np.zeros((A, C), np.uint8)
+    match_idx = np.full((A, C, T), -1, np.int32) if want_idx else None
+    if n_groups == 0 or C == 0 or A == 0:
+        return tp_bits, match_idx
+    if C >= 2 ** 31 or int(go[-1]) >= 2 ** 31:
+        raise _lib.Cm3dError("cm3d_nusc_match: offsets are 32-bit")
+
+    def dev(a, dtype):
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape[0] == 0:
+            a = np.zeros((1,) + a.shape[1:], dtype)
+        return _t(a)
+    d_xy, d_kind = dev(packed["cand_xy"], np.float64), dev(packed["cand_kind"], np.int32)
+    d_p, d_s, d_gxy = dev(packed["cand_p"], np.float64), dev(packed["cand_s"], np.float64), dev(packed["gt_xy"], np.float64)
+    d_co, d_go, d_th = _t(co.astype(np.int32)), _t(go.astype(np.int32)), _t(th)
+    status = torch.zeros(1, dtype=torch.int32, device=_dev())
+    for lo in range(0, A, NUSC_ALPHA_CHUNK):
+        n = min(NUSC_ALPHA_CHUNK, A - lo)
+        d_al = _t(alphas[lo:lo + n])
+        bits = _e(n, C, dtype=torch.uint8)
+        idx = _e(n, C, T) if want_idx else None
+        ws = _ws(L.cm3d_nusc_match_workspace_bytes(n_groups, C, n))
+        if device_ms is not None:
+            ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev[0].record()
+        check(L.cm3d_nusc_match(d_xy.data_ptr(), d_kind.data_ptr(), d_p.data_ptr(), d_s.data_ptr(), d_co.data_ptr(), d_gxy.data_ptr(),
+                                d_go.data_ptr(), n_groups, C, d_al.data_ptr(), n, d_th.data_ptr(), T, bits.data_ptr(),
+                                idx.data_ptr() if want_idx else 0, status.data_ptr(), ws.data_ptr(), ws.numel(), _st()), "cm3d_nusc_match")
+        if device_ms is not None:
+            ev[1].record()
+            ev[1].synchronize()
+            device_ms.append(ev[0].elapsed_time(ev[1]))
+        st = int(status.item())
+        if st:
+            err = _lib.Cm3dError(f"cm3d_nusc_match: status {st} (bit0: a group with more than {_lib.NUSC_MAX_CAND} candidates or more than "
+                                 f"{_lib.NUSC_MAX_GT} ground-truth boxes)")
+            err.status = st
+            raise err
+        tp_bits[lo:lo + n] = bits.cpu().numpy()
+        if want_idx:
+            match_idx[lo:lo + n] = idx.cpu().numpy()
+    return tp_bits, match_idx

@@ -510,6 +510,44 @@ int cm3d_waymo_metrics_sweep(const double *cand_box, const float *cand_heading, 
                              int32_t n_alphas, int64_t *counts, int64_t *heading_sum, int32_t *status, void *workspace,
                              int64_t workspace_bytes, cm3d_stream_t stream);
 
+/* ---- nuScenes detection matching for every alpha of the SAM3D fusion grid search in one call --------
+ * Added within ABI v5: two new symbols, no existing call changes, so CM3D_ABI_VERSION stays.
+ * The greedy matching of the reference's eval_custom.py (accumulate_object_class :542-706, accumulate_with_recall :709-864) only
+ * ever pairs boxes of one sample, so the host (cm3d_amd/nusc_eval.pack) packs GROUPS -- one sample for the class-agnostic "object"
+ * scoring, one (sample, class) for the class-aware one; the call does not know which -- and this call decides every group.  Group
+ * g owns candidates [cand_off[g], cand_off[g+1]) in FILE ORDER and ground truth [gt_off[g], gt_off[g+1]).  A candidate's POSITION
+ * is its index in the candidate arrays.  For alpha a, with prod = s * a (one float64 multiply):
+ *   kind 0  unmatched prediction        always active, score p
+ *   kind 1  unmatched SAM3D box         always active, score clip(prod, 0, 1)
+ *   kind 2  a pair's prediction box     active iff !(prod > p), score p
+ *   kind 3  a pair's SAM3D box          active iff prod > p, score clip(prod, 0, 1)       (any other kind: never active)
+ * A plain result file is all kind 0 with one dummy alpha.  Per (group, alpha, threshold t), each threshold on its own: the active
+ * candidates are walked by descending score (float64; -0 equals +0), equal scores by DESCENDING position -- Python's
+ * sorted((score, index))[::-1] -- and each takes, among the group's ground-truth boxes nobody took before it, the one of smallest
+ * d2 = dx * dx + dy * dy (dx = cand_x - gt_x, float64, no contraction; the lowest ground-truth index on equal d2) if
+ * d2 < dist_th[t] * dist_th[t]; otherwise it is a false positive and takes nothing.  (The reference compares numpy's norm with
+ * dist_th[t]: the two can differ only for a distance within an ulp of the threshold or of another distance)
+ *  cand_xy double[n_cand][2]; cand_kind int32[n_cand]; cand_p, cand_s double[n_cand]   (the score a kind lacks is ignored)
+ *  cand_off, gt_off int32[n_groups+1], non-decreasing, cand_off[n_groups] <= n_cand; gt_xy double[gt_off[n_groups]][2]
+ *  alphas double[n_alphas], 1 <= n_alphas <= CM3D_NUSC_MAX_ALPHAS (the caller hands a longer grid over in several calls)
+ *  dist_th double[n_th], 1 <= n_th <= CM3D_NUSC_MAX_TH
+ *  tp_bits uint8[n_alphas][n_cand] OUT: bit t = true positive at threshold t, bit 7 = active at this alpha; 0 for an inactive
+ *        candidate.  Every candidate of every group is written; candidates outside all groups are left alone.
+ *  match_idx int32[n_alphas][n_cand][n_th] OUT or NULL: the group-local index of the box taken, -1 for none
+ *  status int32[1] (zero it before the call): bit0 a group with more than CM3D_NUSC_MAX_CAND candidates or more than
+ *        CM3D_NUSC_MAX_GT ground-truth boxes (or negative counts) -- such a group is skipped and nothing of it is written
+ *  workspace: cm3d_nusc_match_workspace_bytes(...), which is 0 today (keys and permutation live in LDS; NULL is accepted then).
+ *        No allocation inside the call; one launch, no atomics on the outputs: every run gives the same bytes. */
+#define CM3D_NUSC_MAX_CAND 1024
+#define CM3D_NUSC_MAX_GT 256
+#define CM3D_NUSC_MAX_TH 4
+#define CM3D_NUSC_MAX_ALPHAS 1024
+int64_t cm3d_nusc_match_workspace_bytes(int32_t n_groups, int64_t n_cand, int32_t n_alphas);
+int cm3d_nusc_match(const double *cand_xy, const int32_t *cand_kind, const double *cand_p, const double *cand_s,
+                    const int32_t *cand_off, const double *gt_xy, const int32_t *gt_off, int32_t n_groups, int64_t n_cand,
+                    const double *alphas, int32_t n_alphas, const double *dist_th, int32_t n_th, uint8_t *tp_bits,
+                    int32_t *match_idx, int32_t *status, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
+
 /* ---- One steady-state nuScenes pass in one call; passes of several batches on as many streams as the process has queues for ----
  * Added within ABI v5: new symbols only, no existing call changes, so CM3D_ABI_VERSION stays.  Host code (csrc/pipeline.cpp):
  * no kernel of its own.

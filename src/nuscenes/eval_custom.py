@@ -2,7 +2,8 @@
 """Entry point of the detection evaluation (reference src/nuscenes/eval_custom.py:1158-1214): same positional argument
 and flags; the tables are read by cm3d_amd.nusc_io.NuscTables instead of nuscenes-devkit, so `--eval_set` is either
 `all` (every scene of the tables, the default), a comma-separated list of scene names, or a JSON file holding such a list.
-Plot / render flags are accepted for command-line compatibility and ignored (no matplotlib dependency here)."""
+Plot / render flags are accepted for command-line compatibility and ignored (no matplotlib dependency here).
+`--metrics device` runs the matching on the GPU (cm3d_nusc_match through cm3d_amd.nusc_eval); the default `host` is the Python loop."""
 import argparse
 import json
 import os
@@ -27,6 +28,7 @@ def main(argv=None):
     parser.add_argument('--verbose', type=int, default=1)
     parser.add_argument('--drivable_filtering', type=int, default=0)
     parser.add_argument('--object_only', type=int, default=0)
+    parser.add_argument('--metrics', choices=['host', 'device'], default='host', help='where the matching runs')
     args = parser.parse_args(argv)
     if args.config_path == '':
         cfg = ev.config_factory('detection_cvpr_2019')
@@ -41,6 +43,10 @@ def main(argv=None):
     else:
         scenes = set(args.eval_set.split(','))
     tables = nusc_io.NuscTables(args.version, os.path.expanduser(args.dataroot))
+    if args.metrics == 'device':
+        from cm3d_amd import nusc_eval
+        return nusc_eval.evaluate(tables, cfg, os.path.expanduser(args.result_path), scenes, os.path.expanduser(args.output_dir),
+                                  bool(args.drivable_filtering), bool(args.object_only), bool(args.verbose))
     de = ev.DetectionEval(tables, cfg, os.path.expanduser(args.result_path), scenes, os.path.expanduser(args.output_dir),
                           bool(args.drivable_filtering), bool(args.object_only), bool(args.verbose))
     return de.main()

@@ -5,7 +5,10 @@ and ../../outputs/sam3d_results_nusc_val.json (the reference's module constants 
 ../../outputs/matched_pseudolabels_nusc_train_0322.json per alpha and the best alpha's file to
 ../../outputs/best_matched_pseudolabels_nusc_train_0322.json (:452,:486).  The per-sample box matching runs on the
 MI355X (cm3d_bev_match); each alpha is scored with this package's evaluation (cm3d_amd.eval_detection, all classes,
-no drivable filtering, :455-478).  Paths and the table version are overridable through CM3D_* variables."""
+no drivable filtering, :455-478).  Paths and the table version are overridable through CM3D_* variables.
+CM3D_NUSC_METRICS=native keeps the loop and scores each alpha's file with the matching on the GPU (cm3d_amd.nusc_eval.evaluate);
+CM3D_NUSC_METRICS=sweep scores every alpha from one cm3d_nusc_match call (fusion.grid_search_device) and writes the same two
+files and the last alpha's metrics files."""
 import json
 import os
 import sys
@@ -37,6 +40,21 @@ def main():
         de = ev.DetectionEval(tables, cfg, path, scenes, EVAL_OUTPUT_DIR, drivable_filtering=False, object_only=False, verbose=False)
         return de.main()["mean_ap"]
 
+    mode = os.environ.get("CM3D_NUSC_METRICS", "")
+    if mode not in ("", "native", "sweep"):
+        raise SystemExit(f"CM3D_NUSC_METRICS={mode}: expected native or sweep")
+    if mode == "sweep":
+        from cm3d_amd import nusc_eval
+        alpha, score, _ = fusion.grid_search_device(pred_objects, sam3d_objects, nusc_eval.GridScorer(tables, cfg, scenes), OUT_PATH, BEST_PATH,
+                                                    output_dir=EVAL_OUTPUT_DIR)
+        print(f"best alpha {alpha}, mAP {score}")
+        return 0
+    if mode == "native":
+        from cm3d_amd import nusc_eval
+
+        def evaluate(path):  # noqa: F811
+            return nusc_eval.evaluate(tables, cfg, path, scenes, EVAL_OUTPUT_DIR, drivable_filtering=False, object_only=False,
+                                      verbose=False)["mean_ap"]
     alpha, score = fusion.grid_search(pred_objects, sam3d_objects, evaluate, OUT_PATH, BEST_PATH)
     print(f"best alpha {alpha}, mAP {score}")
     return 0
