@@ -11,6 +11,10 @@
 // staged through LDS 256 at a time and read back as wave-wide broadcasts, 8 rows per step in packed
 // float32.  VALU-bound (about 14 issue slots per pair incl. the correctly rounded sqrt); nothing M x M ever
 // touches HBM.  The tiles are worked longest lists first (worklist.h).
+// Lists of 26 .. 256 points in the scaled form (all of them on real coordinates) do not pay for the correctly rounded root on every
+// pair: the light instantiation takes approximate sums with the bare v_sqrt_f32 and settles only the one or two columns that can be
+// the tile's minimum exactly, inside the tile's own wave, from the rows still in its LDS slice (md_inwave_tile).  The
+// results are bit for bit those of the exact loop, which every other tile still runs.
 #include "common.h"
 #include "worklist.h"
 #include <stdlib.h>
@@ -227,6 +231,15 @@ static __device__ __forceinline__ float md_rows(const float4 *s4, int cnt, float
                 for (int u = 0; u < U; ++u) d[u] = __builtin_elementwise_max(d[u], (f2)(0.0f)); // clamp_min_(0)
             }
         }
+        if (SAFE && SCALED && !DIRECT && APPROX) {
+            // first pass of the in-wave route (md_inwave_tile): the clamp has left every value in [0, 1], so the bare v_sqrt_f32 --
+            // within 1 ulp of the root, +0 for the +0 of a padding row -- is all there is: no compare, no select
+#pragma unroll
+            for (int u = 0; u < U; ++u) d[u] = (f2){__builtin_amdgcn_sqrtf(d[u].x), __builtin_amdgcn_sqrtf(d[u].y)};
+#pragma unroll
+            for (int u = 0; u < U; ++u) { s = s + d[u].x; s = s + d[u].y; }
+            continue;
+        }
         if (SAFE && !DIRECT && !APPROX) {
 #pragma unroll
             for (int u = 0; u < U; ++u) d[u] = md_sqrt_core2z(d[u]);
@@ -270,6 +283,26 @@ static __device__ __forceinline__ float md_rows(const float4 *s4, int cnt, float
                             : (__ballot(bad) ? (f2){sqrtf(d.x), sqrtf(d.y)} : md_sqrt_core2z((f2){d.x, two ? d.y : 1.0f}));
         s = s + r.x;
         if (two) s = s + r.y;
+    }
+    return s;
+}
+
+// The light instantiation's loop for a stage that is not `safe` -- a squared norm outside [1e-22, 2e29) or not finite, never on real
+// coordinates --: the reference's own operations one value at a time, sqrtf(), and clamp_min_(0) as torch does it: a NaN stays a NaN
+// (v_max_f32 makes it 0), so that a list with a non-finite point has the reference's non-finite sums and argmin's "NaN counts as
+// minimal, first wins" decides as it does there.  On finite values: the bits of md_rows<false>.  cnt: the true rows, no padding.
+static __device__ __forceinline__ float md_rows_plain(const float4 *s4, int cnt, float qx, float qy, float qz, float qn, float s)
+{
+    for (int ii = 0; ii < cnt; ii += 2) {
+        const float4 A = s4[ii], B = s4[ii + 1];
+        f2 acc = (f2){A.x, A.y} * qx;
+        acc = PK_FMA(((f2){A.z, A.w}), (f2)(qy), acc);
+        acc = PK_FMA(((f2){B.x, B.y}), (f2)(qz), acc);
+        acc = acc + (f2){B.z, B.w};
+        acc = acc + qn;
+        const float d0 = acc.x > 0.0f ? acc.x : (acc.x != acc.x ? acc.x : 0.0f), d1 = acc.y > 0.0f ? acc.y : (acc.y != acc.y ? acc.y : 0.0f);
+        s = s + sqrtf(d0);
+        if (ii + 1 < cnt) s = s + sqrtf(d1);
     }
     return s;
 }
@@ -419,6 +452,115 @@ static __device__ __forceinline__ void md_approx_tile(Fetch fetch, float *s_rows
     }
 }
 
+// ---------------------------------------------------------------------------
+// The in-wave two-pass route of the light instantiation.  The correctly rounded root is 44 of the 72 vector instructions
+// of an exact 8-row step, and argmin needs it only for the columns that can still be the minimum.  So a tile whose list fits one stage
+// (M <= MD_INW_MAX) in the scaled, safe form first takes APPROXIMATE sums A_j -- the very chain of the exact loop, the bare v_sqrt_f32
+// (within 1 ulp) in place of the correctly rounded root, added in row order: md_rows<false, true, true, true> --, then settles the few
+// columns that can be the tile's first minimum exactly, from the rows still staged in its LDS slice: no launch, no memory traffic.
+// The bound is the one derived above k_medoid_long, E_j = 1.01 (M + 2) 2^-23 A_j + M 2e-14, and it covers this form: the terms differ
+// from the exact ones by at most one ulp (same squared distance, bit for bit; both roots are floats within an ulp of the real root),
+// the sum is sequential (the bound holds for any order), and the scaled units are exact powers of two of the unscaled ones (what
+// underflow inside a scaled chain can take, 6e-15 per term, is inside the M 2e-14).  The filter is local to the tile: with j* the
+// tile's exact first minimum, A_j* - E_j* <= S_j* <= S_k <= A_k + E_k for every column k of the tile, so j* and every exact tie of it
+// pass  A_j - E_j <= min_k (A_k + E_k)  taken over the tile's own active columns.  In float32, pushed to the safe side: E is taken with
+// 1.05 for 1.01 and 2.1e-14 for 2e-14; the excess, 0.04 (M + 2) 2^-23 A >= 2.2 * 2^-24 A for M > 25 and 5 % of the absolute part, is more
+// than the roundings of the factor, of the fma and of A +- E can move (2^-24 (A + E) for the last, 2^-24 E for each of the others).
+// A non-finite A_j makes every column a candidate.  More than MD_INW_GC candidates (duplicated points; far from the origin, where the
+// expansion leaves many zeros): the caller runs the exact loop over the whole tile -- the approximate pass was spent, no result changes.
+// The candidates' exact sums are k_medoid_long's row-parallel form: the 64 lanes take 64 staged rows, compute the exact loop's chain and
+// root (md_exact_dist2s) against each candidate, the terms are transposed through the LDS of those 64 rows, which nobody reads again (row c of `t` = candidate c's 64
+// terms) and lane c adds candidate c's terms in ascending row order from 0 -- the very additions, in the very order, of the column
+// loop; rows past the end are +0.
+#ifndef MD_INW_MAX
+#define MD_INW_MAX MD_STAGE              // longest list of the route: one stage
+#endif
+#ifndef MD_INW_GC
+#define MD_INW_GC 2                      // candidates settled in the one walk over the rows
+#endif
+// (the transposition buffer of a round lies over the 64 rows of that round, which every lane has read by then: no LDS of its own)
+static_assert(MD_INW_MAX <= MD_STAGE && MD_INW_GC % 2 == 0 && MD_INW_GC * 64 * sizeof(float) <= 64 * sizeof(float4),
+              "a round's terms fit the storage of its 64 staged rows");
+
+// md_exact_dist2 in the scaled, safe form of md_rows<false, false, true, true>: clamp_min_(0) on the last addition, no domain test
+static __device__ __forceinline__ f2 md_exact_dist2s(float m2x, float m2y, float m2z, float n, float4 qa, float4 qb)
+{
+    f2 acc = (f2){m2x, m2x} * (f2){qa.x, qb.x};
+    acc = PK_FMA(((f2){m2y, m2y}), ((f2){qa.y, qb.y}), acc);
+    acc = PK_FMA(((f2){m2z, m2z}), ((f2){qa.z, qb.z}), acc);
+    acc = acc + (f2){n, n};
+    acc = md_pk_add_clamp01(acc, (f2){qa.w, qb.w});
+    return md_sqrt_core2z(acc);
+}
+
+// s_row: the tile's list, staged in the scaled form and padded to cnt rows; (qx, qy, qz, qn): this lane's column, scaled.
+// true: (bs, bj) hold the exact (sum in metres, column) of a candidate in lanes 0 .. C-1 and (inf, 0x7FFFFFFF) elsewhere.
+// false: too many candidates, nothing is settled.
+static __device__ __forceinline__ bool md_inwave_tile(float4 *s_row, int cnt, int M, int jt, bool act, float qx, float qy, float qz, float qn,
+                                                      float &bs, int &bj)
+{
+    const int lane = cm3d_lane();
+    const float a = md_rows<false, true, true, true>(s_row, cnt, qx, qy, qz, qn, 0.0f) * 65536.0f;        // metres
+    const float rel = 1.05f * (float)(M + 2) * 1.1920928955078125e-07f, abs_e = (float)M * 2.1e-14f;
+    const float e = fmaf(a, rel, abs_e);
+    const float thr = cm3d_wave_reduce_t(act ? a + e : INFINITY, [](float x, float y) { return fminf(x, y); });
+    const bool all = __ballot(act && !(a < INFINITY)) != 0;
+    const uint64_t cm = __ballot(act && (all || !(a - e > thr)));
+    const int C = (int)__popcll(cm);
+    if (C < 1 || C > MD_INW_GC) return false;
+    // the candidates' lanes, ascending, and their points out of those lanes' registers (uniform; unused slots repeat the first)
+    float4 q[MD_INW_GC];
+    int myj = 0x7FFFFFFF;
+    {
+        uint64_t rest = cm;
+        const int first = __builtin_ctzll(cm);
+#pragma unroll
+        for (int c = 0; c < MD_INW_GC; ++c) {
+            const int cl = rest ? __builtin_ctzll(rest) : first;
+            if (rest && lane == c) myj = jt * 64 + cl;
+            rest &= rest - 1;
+            q[c] = make_float4(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(qx), cl)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qy), cl)),
+                               __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qz), cl)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(qn), cl)));
+        }
+    }
+    float s = 0.0f;                                                   // lane c < C: the sum of candidate c, scaled units
+    for (int r0 = 0; r0 < M; r0 += 64) {
+        const bool valid = r0 + lane < M;
+        const int row = min(r0 + lane, cnt - 1);
+        const float *f = reinterpret_cast<const float *>(s_row) + (row >> 1) * 8 + (row & 1);     // md_stage's layout
+        const float m2x = f[0], m2y = f[2], m2z = f[4], n = f[6];
+        float *t = reinterpret_cast<float *>(s_row + r0);             // t[c * 64 + r], over rows r0 .. r0 + 63: they are in registers now
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");          // every lane has its row; the round before has read its t
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int c = 0; c < MD_INW_GC; c += 2) {
+            if (c < C) {                                              // (uniform)
+                const f2 d = md_exact_dist2s(m2x, m2y, m2z, n, q[c], q[c + 1]);
+                t[c * 64 + lane] = valid ? d.x : 0.0f;
+                t[(c + 1) * 64 + lane] = valid ? d.y : 0.0f;
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        if (lane < C) {
+            const float4 *tr = reinterpret_cast<const float4 *>(t + lane * 64);
+            const int n16 = (min(64, M - r0) + 15) >> 4;              // (uniform) sixteen terms per round trip; past the end: +0
+            for (int k0 = 0; k0 < n16; ++k0) {
+                float4 v[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) v[k] = tr[4 * k0 + k];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { s = s + v[k].x; s = s + v[k].y; s = s + v[k].z; s = s + v[k].w; }
+            }
+        }
+    }
+    bs = lane < C ? s * 65536.0f : INFINITY;
+    bj = myj;
+    return true;
+}
+
 // One wave = one tile = 64 columns of one mask; rows are staged 64 at a time through the wave's own
 // LDS slice and read back as broadcasts.  No workgroup barrier: waves of a block are independent.
 // Two instantiations, launched one behind the other over the same work list, of which exactly ONE does the work: WITH_LONG = true
@@ -479,6 +621,11 @@ __global__ __launch_bounds__(MD_THREADS, 4) void k_medoid_tiles(const float4 *__
         const bool col_safe = !__ballot(act && !md_col_safe(qn));
         const bool col_scal = !__ballot(act && !mda_point_ok(qx, qy, qz, qn));           // the column side of the scaled form (md_rows<.., SCALED>)
         const bool direct = M <= 25;
+        // the in-wave two-pass route (md_inwave_tile): light instantiation, nobody wants every column's exact sum, one stage
+        const bool inw_ok = !WITH_LONG && colsum_opt == nullptr && !direct && M <= MD_INW_MAX;
+        bool inw = false;                                                 // (uniform) the tile's candidates are settled in (bs_inw, bj_inw)
+        float bs_inw = INFINITY;
+        int bj_inw = 0x7FFFFFFF;
         const bool approx = WITH_LONG && md_two_pass(M);                  // long list (of a batch with the first pass: this instantiation): approximate sums, k_medoid_long later
         if (WITH_LONG && approx && MD_APPROX_MFMA) {
             md_approx_tile(fetch, reinterpret_cast<float *>(s_row), off, M, jt, approx_opt);
@@ -529,12 +676,16 @@ __global__ __launch_bounds__(MD_THREADS, 4) void k_medoid_tiles(const float4 *__
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             const bool safe = col_safe && !__ballot(!rows_safe);
-            if (scaled)         // s goes in and comes out in its own units: the powers of two are exact both ways
+            // (uniform; such a list has one stage)  approximate sums, exact ones for the few columns that can be the minimum
+            if (scaled && inw_ok && safe && md_inwave_tile(s_row, cnt, M, jt, act, qx * MDA_S, qy * MDA_S, qz * MDA_S, qn * MDA_S2, bs_inw, bj_inw))
+                inw = true;
+            else if (scaled)    // s goes in and comes out in its own units: the powers of two are exact both ways
                 s = md_rows<false, false, true, true>(s_row, cnt, qx * MDA_S, qy * MDA_S, qz * MDA_S, qn * MDA_S2, s * MDA_S) * 65536.0f;
             else
                 s = direct ? md_rows<true>(s_row, cnt, qx, qy, qz, qn, s)
                            : (approx ? md_rows<false, true>(s_row, cnt, qx, qy, qz, qn, s)
-                                     : (safe ? md_rows<false, false, true>(s_row, cnt, qx, qy, qz, qn, s) : md_rows<false>(s_row, cnt, qx, qy, qz, qn, s)));
+                                     : (safe ? md_rows<false, false, true>(s_row, cnt, qx, qy, qz, qn, s)
+                                             : (WITH_LONG ? md_rows<false>(s_row, cnt, qx, qy, qz, qn, s) : md_rows_plain(s_row, min(MD_STAGE, M - i0), qx, qy, qz, qn, s))));
         }
         if (approx) {
             if (act) approx_opt[off + j] = s;
@@ -542,8 +693,8 @@ __global__ __launch_bounds__(MD_THREADS, 4) void k_medoid_tiles(const float4 *__
         }
         if (act && colsum_opt) colsum_opt[off + j] = s;
         // first minimum over the tile's columns (torch.argmin: NaN counts as minimal, first wins)
-        float bs = act ? s : INFINITY;
-        int bj = act ? j : 0x7FFFFFFF;
+        float bs = inw ? bs_inw : (act ? s : INFINITY);
+        int bj = inw ? bj_inw : (act ? j : 0x7FFFFFFF);
         auto better = [](float s1, int j1, float s2, int j2) {   // is (s1,j1) ahead of (s2,j2)?
             const bool n1 = s1 != s1, n2 = s2 != s2;
             if (n1 != n2) return n1;
