@@ -90,7 +90,6 @@ SIGNATURES = {
     "cm3d_pipe_destroy": (None, [_p]),
     "cm3d_pipe_exec_streams": (_i32, [_p]),
     "cm3d_pipe_submit": (_i32, [_p, _i32, _p]),
-    "cm3d_pipe_submit_timed": (_i32, [_p, _i32, _p, _p, _p]),
     "cm3d_pipe_acquire": (_i32, [_p, _i32]),
     "cm3d_pipe_release": (_i32, [_p, _i32]),
     "cm3d_pipe_wait": (_i32, [_p, _i32]),
@@ -111,9 +110,13 @@ class LiftPassDesc(C.Structure):
         + [("ws_bytes", _i64), ("md_feedback", _p)]
         + [(n, _p) for n in ("centroid_g", "mask_frame", "lane", "lane_off", "frame_lane", "grid", "lane_idx", "lane_dist", "class_id", "score",
                              "prior_wlh", "is_vehicle", "nms_group", "nms_thr", "ego_xyz", "box", "flags")]
-        + [(n, _i32) for n in ("n_masks", "total_runs", "W", "H", "raw_stride", "n_sweeps", "max_sweeps_per_frame", "pt_cap", "n_frames",
-                               "max_pts_per_frame", "n_cams", "planes", "idx_cap", "n_tables", "n_lane_points", "n_classes", "md_hint")]
-        + [("halfw", _f32), ("min_dist", _f32)])
+        + [(n, _p) for n in ("mask_wh", "pose_rt", "pose_inv", "obb_yaw", "obb_status", "obb_ws")] + [("obb_ws_bytes", _i64)]
+        + [("dense", _p), ("lane_ready", _p), ("ev_project", _p * 2), ("ev_stage", _p * 5)]
+        + [(n, _i32) for n in ("n_masks", "total_runs", "W", "H", "raw_stride", "n_sweeps", "max_sweeps_per_frame", "max_rows_per_sweep",
+                               "pt_cap", "n_frames", "max_pts_per_frame", "n_cams", "planes", "idx_cap", "n_tables", "n_lane_points",
+                               "n_classes")]
+        + [("halfw", _f32), ("min_dist", _f32)]
+        + [(n, _i32) for n in ("md_hint", "fused", "separate_reset")])
 
 
 class Cm3dError(RuntimeError):

@@ -1,7 +1,7 @@
-// Host side of a pass: one call that enqueues the six launches of a steady-state nuScenes pass (cm3d_lift_pass), and the pipeline
-// object that decides which stream a slot's pass goes to (csrc/pipe_sched.h) and keeps two passes of one slot in order when they
-// land on different streams.  No kernel lives here: every launch goes through the entry points of include/cm3d_hip.h, with the
-// arguments and in the order cm3d_amd.lifting.LiftEngine.run hands them over.
+// Host side of a pass: one call that enqueues every launch of a pass over a resident batch (cm3d_lift_pass: the only statement of a
+// pass's order, include/cm3d_hip.h spells it out), and the pipeline object that decides which stream a slot's pass goes to
+// (csrc/pipe_sched.h) and keeps two passes of one slot in order when they land on different streams.  No kernel lives here: every
+// launch goes through the entry points of include/cm3d_hip.h.
 #include <hip/hip_runtime_api.h>
 
 #include <cstdlib>
@@ -10,17 +10,51 @@
 #include "../../include/cm3d_hip.h"
 #include "pipe_sched.h"
 
-static int lift_pass(const cm3d_lift_pass_desc *d, void *ev_start, void *ev_stop, cm3d_stream_t st)
+static int record(void *ev, cm3d_stream_t st)
+{
+    return !ev || hipEventRecord((hipEvent_t)ev, (hipStream_t)st) == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
+}
+
+static int lift_masks(const cm3d_lift_pass_desc *d, bool on_masks, cm3d_stream_t st)
+{
+    if (d->dense) return cm3d_erode_pack(d->dense, d->n_masks, d->W, d->H, d->packed, d->bbox, st);
+    if (d->mask_wh)
+        return on_masks ? cm3d_rle_erode_pack_sized_begin(d->rle_counts, d->rle_off, d->n_masks, d->total_runs, d->W, d->H, d->mask_wh,
+                                                          d->packed, d->bbox, d->rle_ws, d->rle_ws_bytes, d->status, d->hit_count,
+                                                          d->n_masks, d->removed_bits, d->removed_words, st)
+                        : cm3d_rle_erode_pack_sized(d->rle_counts, d->rle_off, d->n_masks, d->total_runs, d->W, d->H, d->mask_wh, d->packed,
+                                                    d->bbox, d->rle_ws, d->rle_ws_bytes, st);
+    return on_masks ? cm3d_rle_erode_pack_begin(d->rle_counts, d->rle_off, d->n_masks, d->total_runs, d->W, d->H, d->packed, d->bbox,
+                                                d->rle_ws, d->rle_ws_bytes, d->status, d->hit_count, d->n_masks, d->removed_bits,
+                                                d->removed_words, st)
+                    : cm3d_rle_erode_pack(d->rle_counts, d->rle_off, d->n_masks, d->total_runs, d->W, d->H, d->packed, d->bbox, d->rle_ws,
+                                          d->rle_ws_bytes, st);
+}
+
+extern "C" int cm3d_lift_pass(const cm3d_lift_pass_desc *d, cm3d_stream_t st)
 {
     if (!d || d->size != (int64_t)sizeof(cm3d_lift_pass_desc)) return CM3D_ERR_ARG;
-    int rc = cm3d_rle_erode_pack_begin(d->rle_counts, d->rle_off, d->n_masks, d->total_runs, d->W, d->H, d->packed, d->bbox, d->rle_ws,
-                                       d->rle_ws_bytes, d->status, d->hit_count, d->n_masks, d->removed_bits, d->removed_words, st);
-    if (rc != CM3D_OK) return rc;
-    rc = cm3d_sweep_project_hits(d->raw, d->raw_stride, d->intensity, d->sweep_row_off, d->n_sweeps, d->max_sweeps_per_frame, d->sweep_xf,
-                                 d->frame_sweep_off, d->halfw, d->points, d->pt_cap, d->pt_off, d->removed_bits, d->n_frames,
-                                 d->max_pts_per_frame, d->pt_cap, d->cams, d->n_cams, d->mask_off, d->mask_cam, d->bbox, d->packed, d->n_masks,
-                                 d->W, d->H, d->min_dist, d->planes, d->hit_words, d->hit_count, d->status, d->pg_ws, d->pg_ws_bytes,
-                                 ev_start, ev_stop, st);
+    if (!d->fused && !d->points) return CM3D_ERR_ARG;        // the separate launches hand the cloud from one to the other
+    int rc;
+    // (resident run lengths on the fused-sweeps path: the mask launch is the pass's first and carries the reset -- one launch and one
+    // launch boundary less per pass)
+    const bool on_masks = !d->dense && d->fused && !d->separate_reset;
+    if (!on_masks && (rc = cm3d_batch_begin(d->status, d->hit_count, d->n_masks, d->removed_bits, d->removed_words, st)) != CM3D_OK)
+        return rc;
+    if ((rc = record(d->ev_stage[0], st)) != CM3D_OK) return rc;
+    if (!d->fused && (rc = cm3d_sweep_prep(d->raw, d->raw_stride, d->intensity, d->sweep_row_off, d->n_sweeps, d->max_rows_per_sweep,
+                                           d->sweep_xf, d->frame_sweep_off, d->n_frames, d->halfw, d->points, d->pt_cap, d->pt_off,
+                                           d->removed_bits, d->status, st)) != CM3D_OK)
+        return rc;
+    if ((rc = lift_masks(d, on_masks, st)) != CM3D_OK) return rc;
+    rc = d->fused ? cm3d_sweep_project_hits(d->raw, d->raw_stride, d->intensity, d->sweep_row_off, d->n_sweeps, d->max_sweeps_per_frame,
+                                            d->sweep_xf, d->frame_sweep_off, d->halfw, d->points, d->pt_cap, d->pt_off, d->removed_bits,
+                                            d->n_frames, d->max_pts_per_frame, d->pt_cap, d->cams, d->n_cams, d->mask_off, d->mask_cam, d->bbox,
+                                            d->packed, d->n_masks, d->W, d->H, d->min_dist, d->planes, d->hit_words, d->hit_count, d->status,
+                                            d->pg_ws, d->pg_ws_bytes, d->ev_project[0], d->ev_project[1], st)
+                  : cm3d_project_hits(d->points, d->pt_off, d->n_frames, d->max_pts_per_frame, d->pt_cap, d->cams, d->n_cams, d->mask_off,
+                                      d->mask_cam, d->bbox, d->packed, d->n_masks, d->W, d->H, d->min_dist, d->planes, d->hit_words,
+                                      d->hit_count, d->status, d->pg_ws, d->pg_ws_bytes, d->ev_project[0], d->ev_project[1], st);
     if (rc != CM3D_OK) return rc;
     // coordinates of the in-mask points: from the cloud when it exists, else re-derived from the raw rows
     const bool from_raw = d->points == nullptr;
@@ -28,24 +62,32 @@ static int lift_pass(const cm3d_lift_pass_desc *d, void *ev_start, void *ev_stop
                            d->removed_bits, from_raw ? d->raw : nullptr, d->raw_stride, from_raw ? d->intensity : nullptr,
                            from_raw ? d->sweep_xf : nullptr, d->points, d->hit_off, d->tile_off, d->hit_idx, nullptr, d->hit_xyz, d->idx_cap,
                            d->tile_work, d->status, d->pg_ws, d->pg_ws_bytes, st);
-    if (rc != CM3D_OK) return rc;
+    if (rc != CM3D_OK || (rc = record(d->ev_stage[1], st)) != CM3D_OK) return rc;
     // the hint: whatever the device has written into the page-locked word by now (a stale value costs time on one pass, never a result)
     int32_t md_flags = 0;
     if (d->md_hint && d->md_feedback && *(const volatile int32_t *)d->md_feedback == 0) md_flags = 1;
     rc = cm3d_medoid2(d->hit_xyz, nullptr, nullptr, d->n_masks, d->hit_off, d->tile_off, nullptr, d->idx_cap, d->tile_work, d->medoid_pos,
                       d->centroid, d->colsum, d->ws, d->ws_bytes, md_flags, d->md_feedback, st);
-    if (rc != CM3D_OK) return rc;
+    if (rc != CM3D_OK || (rc = record(d->ev_stage[2], st)) != CM3D_OK) return rc;
+    if (d->lane_ready && hipStreamWaitEvent((hipStream_t)st, (hipEvent_t)d->lane_ready, 0) != hipSuccess) return CM3D_ERR_LAUNCH;
+    // (Waymo: the lane lookup happens in the global frame)
+    if (d->pose_rt && (rc = cm3d_centroid_transform(d->centroid, d->medoid_pos, d->mask_frame, d->n_masks, d->pose_rt, d->centroid_g,
+                                                    st)) != CM3D_OK) return rc;
     rc = cm3d_lane_nn(d->centroid_g, d->medoid_pos, d->mask_frame, d->n_masks, d->lane, d->lane_off, d->frame_lane, d->n_tables,
                       d->n_lane_points, d->grid, d->lane_idx, d->lane_dist, d->ws, d->ws_bytes, st);
-    if (rc != CM3D_OK) return rc;
+    if (rc != CM3D_OK || (rc = record(d->ev_stage[3], st)) != CM3D_OK) return rc;
     // (`planes` words of mask bits per point: no frame of the batch has more than 32 * planes masks)
-    return cm3d_box_nms_bounded(d->centroid_g, d->medoid_pos, d->mask_off, d->n_frames, d->n_masks, d->class_id, d->score, d->lane,
-                                d->lane_off, d->frame_lane, d->lane_idx, d->lane_dist, d->prior_wlh, d->is_vehicle, d->nms_group, d->nms_thr,
-                                d->n_classes, d->ego_xyz, nullptr, d->planes > 0 && d->planes < CM3D_MAX_MASKS_PER_FRAME / 32 ? 32 * d->planes : CM3D_MAX_MASKS_PER_FRAME,
-                                d->box, d->flags, st);
+    rc = cm3d_box_nms_bounded(d->centroid_g, d->medoid_pos, d->mask_off, d->n_frames, d->n_masks, d->class_id, d->score, d->lane,
+                              d->lane_off, d->frame_lane, d->lane_idx, d->lane_dist, d->prior_wlh, d->is_vehicle, d->nms_group, d->nms_thr,
+                              d->n_classes, d->ego_xyz, d->pose_inv,
+                              d->planes > 0 && d->planes < CM3D_MAX_MASKS_PER_FRAME / 32 ? 32 * d->planes : CM3D_MAX_MASKS_PER_FRAME,
+                              d->box, d->flags, st);
+    if (rc != CM3D_OK || (rc = record(d->ev_stage[4], st)) != CM3D_OK) return rc;
+    if (d->obb_yaw)
+        return cm3d_obb(d->hit_xyz, d->hit_off, d->n_masks, d->idx_cap, d->obb_yaw, d->obb_status, nullptr, nullptr, d->obb_ws,
+                        d->obb_ws_bytes, st);
+    return CM3D_OK;
 }
-
-extern "C" int cm3d_lift_pass(const cm3d_lift_pass_desc *d, cm3d_stream_t st) { return lift_pass(d, nullptr, nullptr, st); }
 
 extern "C" int cm3d_pipe_exec_streams_for(int32_t depth, int32_t hw_queues)
 {
@@ -123,16 +165,11 @@ extern "C" int cm3d_pipe_exec_streams(const void *pipe)
 
 extern "C" int cm3d_pipe_submit(void *pipe, int32_t slot, const cm3d_lift_pass_desc *desc)
 {
-    return cm3d_pipe_submit_timed(pipe, slot, desc, nullptr, nullptr);
-}
-
-extern "C" int cm3d_pipe_submit_timed(void *pipe, int32_t slot, const cm3d_lift_pass_desc *desc, void *ev_start, void *ev_stop)
-{
     Pipe *p = (Pipe *)pipe;
     if (!desc) return CM3D_ERR_ARG;
     const int s = pipe_take(p, slot);
     if (s < 0) return s;
-    const int rc = lift_pass(desc, ev_start, ev_stop, (cm3d_stream_t)p->streams[s]);
+    const int rc = cm3d_lift_pass(desc, (cm3d_stream_t)p->streams[s]);
     // (the event also behind a pass that stopped half-way: what it did enqueue is what the slot's next pass must wait for)
     const int rm = pipe_mark(p, slot);
     if (rc != CM3D_OK) return rc;

@@ -549,57 +549,69 @@ class LiftEngine:
         b.rle_counts = t(hb.rle_counts.view(np.int32))
         b.intensity = t(hb.intensity) if hb.intensity is not None else None
         b.raw = t(hb.raw)
-        # what a steady-state pass hands to the library, filled once (cm3d_lift_pass: LiftPipeline's native submitter)
-        b.native_ok = b.fused and b.pose_rt is None and b.pose_inv is None and b.mask_wh is None and not self.obb
-        b.desc = self._pass_descriptor(b) if b.native_ok else None
-        b.desc_ref = ctypes.byref(b.desc) if b.native_ok else None
+        # what a pass hands to the library (cm3d_lift_pass), filled once; `refresh_pass_descriptor` adds what changes from pass to pass
+        b.desc = self._batch_descriptor(b)
+        b.desc_ref = ctypes.byref(b.desc)
         self.b = b
         return b
 
-    def _pass_descriptor(self, b):
-        """cm3d_lift_pass_desc of the resident batch: the arguments of the six calls `run` makes for run-length masks on the fused-sweeps
-        path (stage_masks(reset=True), stage_sweep_project, stage_compact, stage_medoid, stage_lanes, stage_boxes), name for name."""
+    def _batch_descriptor(self, b):
+        """cm3d_lift_pass_desc of the resident batch: the arguments of the calls a pass makes, name for name (the fields that belong to
+        the batch; `refresh_pass_descriptor` sets the per-pass ones)."""
         d = _lib.LiftPassDesc()
         d.size = ctypes.sizeof(_lib.LiftPassDesc)
         for name in ("rle_counts", "rle_off", "packed", "bbox", "rle_ws", "status", "hit_count", "removed_bits", "raw", "intensity",
                      "sweep_row_off", "sweep_xf", "frame_sweep_off", "points", "pt_off", "cams", "mask_off", "mask_cam", "hit_words", "pg_ws",
                      "hit_off", "tile_off", "hit_idx", "hit_xyz", "tile_work", "medoid_pos", "centroid", "colsum", "ws", "centroid_g",
                      "mask_frame", "lane", "lane_off", "frame_lane", "grid", "lane_idx", "lane_dist", "class_id", "score", "ego_xyz", "box",
-                     "flags"):
+                     "flags", "mask_wh", "pose_rt", "pose_inv"):
             setattr(d, name, _ptr(getattr(b, name)) or None)
         for name in ("prior_wlh", "is_vehicle", "nms_group", "nms_thr"):
             setattr(d, name, _ptr(getattr(self, name)))
+        if self.obb:
+            d.obb_yaw, d.obb_status, d.obb_ws, d.obb_ws_bytes = _ptr(b.obb_yaw), _ptr(b.obb_status), _ptr(b.obb_ws), b.obb_ws_bytes
         d.md_feedback = self._md_fb.data_ptr()
         d.rle_ws_bytes, d.removed_words, d.pg_ws_bytes, d.ws_bytes = b.rle_ws_bytes, b.removed_words, b.pg_ws_bytes, b.ws_bytes
         d.n_masks, d.total_runs, d.W, d.H = b.M, b.hb.rle_counts.size, b.W, b.H
         d.raw_stride, d.n_sweeps, d.max_sweeps_per_frame, d.pt_cap = b.hb.raw_stride, b.S, b.max_sweeps, b.pt_cap
+        d.max_rows_per_sweep = b.hb.max_rows_per_sweep
         d.n_frames, d.max_pts_per_frame, d.n_cams, d.planes, d.idx_cap = b.F, b.max_pts, b.hb.n_cams, b.planes, b.idx_cap
         d.n_tables, d.n_lane_points, d.n_classes = b.n_tables, b.n_lane, len(self.classes.names)
-        d.md_hint, d.halfw, d.min_dist = int(self._md_hint), b.halfw, self.min_dist
+        d.halfw, d.min_dist = b.halfw, self.min_dist
         return d
 
-    def native_pass_ready(self, masks, project_events=None, stage_events=None):
-        """True when the next pass over the resident batch is the steady-state nuScenes pass cm3d_lift_pass makes: run-length masks, fused
-        sweeps, one mask size, no Waymo pose, no OBB, no per-stage timing events, and the lane index built and seen complete (a pass that has to build
-        it, or to wait for the build, goes through `run`)."""
+    def resident_masks(self, masks):
+        """What the descriptor's `dense` takes for a mask mode: the resident dense masks, or None for the run lengths."""
         b = self.b
-        if masks != "rle" or project_events is not None or stage_events is not None or b is None or not b.native_ok:
-            return False
-        ln = self._lane
-        if not ln["built"]:
-            return False
-        if not ln.get("done"):
-            if not ln["built_event"].query():
-                return False
-            ln["done"] = True                # the build has completed: nothing left to wait for (wait_lane_grid)
-        return os.environ.get("CM3D_FUSED_RESET", "1") != "0"
+        if masks == "rle":
+            return None
+        if masks != "dense":
+            raise ValueError(masks)
+        require_one_mask_size(b.hb)
+        if b.dense is None:
+            raise Cm3dError("dense masks requested but not resident: call decode_masks_dense() or pass dense_masks")
+        return b.dense.data_ptr()
 
-    def refresh_pass_descriptor(self):
-        """What may change between two passes over one resident batch: the hint switch and the lane index in use."""
-        d = self.b.desc
-        d.md_hint = int(self._md_hint)
-        d.grid = self.b.grid.data_ptr()
-        return self.b.desc_ref
+    def refresh_pass_descriptor(self, dense=None, project_events=None, stage_events=None):
+        """The descriptor of the next pass over the resident batch, for cm3d_lift_pass / cm3d_pipe_submit: sets what may change between
+        two passes over one batch -- the mask route (`dense`: resident_masks), the reset, the hint switch, the lane index in use and
+        whether its build has to be waited for, the events (project_events: a pair of torch.cuda.Event, stage_events: five) -- and
+        counts the pass.  The build of the lane index must have been started (start_lane_grid)."""
+        b = self.b
+        d = b.desc
+        d.dense = dense
+        d.fused = b.fused
+        d.separate_reset = os.environ.get("CM3D_FUSED_RESET", "1") == "0"        # the reset as a launch of its own
+        d.md_hint = self._md_hint
+        d.grid = b.grid.data_ptr()
+        ln = self._lane
+        if not ln.get("done") and ln["built_event"].query():
+            ln["done"] = True                # the build has completed: nothing left to wait for
+        d.lane_ready = None if ln.get("done") else ln["built_event"].cuda_event
+        d.ev_project[:] = self._raw_events(project_events, 2)
+        d.ev_stage[:] = self._raw_events(stage_events, 5)
+        ln["passes_since_build"] = ln.get("passes_since_build", 0) + 1
+        return b.desc_ref
 
     def decode_masks_dense(self):
         """a1: RLE -> dense uint8 (M,H,W) on the device (pycocotools.mask.decode, reference :425)."""
@@ -615,14 +627,18 @@ class LiftEngine:
     # -- the stages, in reference order
     def stage_begin(self, st, defer_reset=False):
         """Resets the per-pass state and starts the lane-grid build on the side stream.  defer_reset: the reset rides on the mask stage's
-        launch instead (stage_masks(..., reset=True): run() does that for resident run lengths on the fused-sweeps path, one launch less
+        launch instead (stage_masks(..., reset=True): a pass does that for resident run lengths on the fused-sweeps path, one launch less
         per pass)."""
         b = self.b
         if not defer_reset:
             check(self.lib.cm3d_batch_begin(_ptr(b.status), _ptr(b.hit_count), b.M, _ptr(b.removed_bits), b.removed_words, st),
                   "cm3d_batch_begin")
-        if self._lane["built"]:
-            return                           # same lane tables as the last build: the index is still valid
+        if not self._lane["built"]:
+            self.start_lane_grid()
+
+    def start_lane_grid(self):
+        """Builds the lane index on the side stream, behind what the current stream holds so far, and records its event.  (Not needed
+        while the lane tables are those of the last build: the index is still valid.)"""
         main = torch.cuda.current_stream(self.dev)
         self.side.wait_stream(main)          # the uploads of the tables have been issued before this point
         self.side.wait_event(self._lane["tables_uploaded"])     # (by another engine of the pipeline, on its stream, when the entry is shared)
@@ -685,23 +701,25 @@ class LiftEngine:
         """events: optional pair of torch.cuda.Event (enable_timing) that the library records around the projection
         kernel itself on the launch stream (bench.py's roofline timing)."""
         b = self.b
-        e0, e1 = self._raw_events(events)
+        e0, e1 = self._raw_events(events, 2)
         check(self.lib.cm3d_project_hits(_ptr(b.points), _ptr(b.pt_off), b.F, b.max_pts, b.pt_cap, _ptr(b.cams), b.hb.n_cams,
                                          _ptr(b.mask_off), _ptr(b.mask_cam), _ptr(b.bbox), _ptr(b.packed), b.M, b.W, b.H,
                                          self.min_dist, b.planes, _ptr(b.hit_words), _ptr(b.hit_count), _ptr(b.status),
                                          _ptr(b.pg_ws), b.pg_ws_bytes, e0, e1, st), "cm3d_project_hits")
 
     @staticmethod
-    def _raw_events(events):
-        """torch events -> the hipEvent_t handles the C-ABI takes (created by a first record on the current stream)."""
+    def _raw_events(events, n):
+        """n torch events -> the hipEvent_t handles the C-ABI takes (created by a first record on the current stream); None: n times none."""
         if events is None:
-            return 0, 0
+            return [None] * n
         out = []
         for ev in events:
             if ev.cuda_event == 0 or ev.cuda_event is None:
                 ev.record()
             out.append(int(ev.cuda_event))
-        return out[0], out[1]
+        if len(out) != n:
+            raise ValueError(f"{n} events expected")
+        return out
 
     def can_fuse_sweeps(self):
         return self.b.fused
@@ -710,7 +728,7 @@ class LiftEngine:
         """Sweep preparation folded into the projection kernel (cm3d_sweep_project_hits): same outputs as
         stage_sweeps + stage_project, the cloud crosses HBM once less.  Needs the masks of the batch (stage_masks) first."""
         b = self.b
-        e0, e1 = self._raw_events(events)
+        e0, e1 = self._raw_events(events, 2)
         check(self.lib.cm3d_sweep_project_hits(_ptr(b.raw), b.hb.raw_stride, _ptr(b.intensity), _ptr(b.sweep_row_off), b.S, b.max_sweeps, _ptr(b.sweep_xf),
                                                _ptr(b.frame_sweep_off), b.halfw, _ptr(b.points), b.pt_cap, _ptr(b.pt_off),
                                                _ptr(b.removed_bits), b.F, b.max_pts, b.pt_cap, _ptr(b.cams),
@@ -759,11 +777,13 @@ class LiftEngine:
 
     def stage_boxes(self, st):
         b = self.b
-        check(self.lib.cm3d_box_nms(_ptr(b.centroid_g), _ptr(b.medoid_pos), _ptr(b.mask_off), b.F, b.M, _ptr(b.class_id),
-                                    _ptr(b.score), _ptr(b.lane), _ptr(b.lane_off), _ptr(b.frame_lane), _ptr(b.lane_idx),
-                                    _ptr(b.lane_dist), _ptr(self.prior_wlh), _ptr(self.is_vehicle), _ptr(self.nms_group),
-                                    _ptr(self.nms_thr), len(self.classes.names), _ptr(b.ego_xyz), _ptr(b.pose_inv), _ptr(b.box),
-                                    _ptr(b.flags), st), "cm3d_box_nms")
+        # (`planes` words of mask bits per point: no frame of the batch has more than 32 * planes masks -- the bound cm3d_lift_pass hands over)
+        check(self.lib.cm3d_box_nms_bounded(_ptr(b.centroid_g), _ptr(b.medoid_pos), _ptr(b.mask_off), b.F, b.M, _ptr(b.class_id),
+                                            _ptr(b.score), _ptr(b.lane), _ptr(b.lane_off), _ptr(b.frame_lane), _ptr(b.lane_idx),
+                                            _ptr(b.lane_dist), _ptr(self.prior_wlh), _ptr(self.is_vehicle), _ptr(self.nms_group),
+                                            _ptr(self.nms_thr), len(self.classes.names), _ptr(b.ego_xyz), _ptr(b.pose_inv),
+                                            min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), _ptr(b.box), _ptr(b.flags), st),
+              "cm3d_box_nms_bounded")
 
     def stage_obb(self, st):
         """a18 (KITTI): yaw of the oriented box of every mask's in-mask points (cm3d_obb), on hit_xyz / hit_off of the compaction."""
@@ -778,37 +798,15 @@ class LiftEngine:
         torch.cuda.Event recorded around the projection launch on the launch stream (bench.py's roofline timing).
         stage_events: optional list; gets five timing events appended -- before the point/mask stages, behind the compaction,
         the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them."""
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-
-        def mark():
-            if stage_events is not None:
-                e = torch.cuda.Event(enable_timing=True)
-                e.record()
-                stage_events.append(e)
-        # (resident run lengths on the fused-sweeps path: the mask launch is the pass's first and carries the reset -- one launch and one
-        # launch boundary less per pass; CM3D_FUSED_RESET=0: the reset as a launch of its own)
-        fused_reset = masks == "rle" and self.can_fuse_sweeps() and os.environ.get("CM3D_FUSED_RESET", "1") != "0"
-        self.stage_begin(st, defer_reset=fused_reset)
-        mark()
-        if not self.can_fuse_sweeps():
-            self.stage_sweeps(st)
-        self.stage_masks(st, masks, reset=fused_reset)
-        if not self.can_fuse_sweeps():
-            self.stage_project(st, project_events)
-        else:
-            self.stage_sweep_project(st, project_events)
-        self.stage_compact(st)
-        mark()
-        self.stage_medoid(st)
-        mark()
-        self.wait_lane_grid()
-        self.stage_lanes(st)
-        mark()
-        self.stage_boxes(st)
-        mark()
-        if self.obb:
-            self.stage_obb(st)
-        self._lane["passes_since_build"] = self._lane.get("passes_since_build", 0) + 1
+        dense = self.resident_masks(masks)               # raises before anything is enqueued
+        if not self._lane["built"]:
+            self.start_lane_grid()
+        marks = None
+        if stage_events is not None:
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+            stage_events.extend(marks)
+        check(self.lib.cm3d_lift_pass(self.refresh_pass_descriptor(dense, project_events, marks),
+                                      torch.cuda.current_stream(self.dev).cuda_stream), "cm3d_lift_pass")
 
     def capture_graph(self, masks="rle"):
         """Captures one pass over the resident batch into a HIP graph and returns it (`g.replay()` re-runs the pass
@@ -928,8 +926,9 @@ class LiftPipeline:
     variable read, never set; 4 queues when it is unset.  With that many streams or more than slots, slot s runs on `streams[s]` as
     it always did.  With fewer, pass number k runs on `streams[k % n]`, the slots take turns, and a slot's event keeps two passes of
     one slot in order when they land on different streams ("Passes rotate over as many streams as the process has queues
-    for").  `exec_streams` overrides the policy (tests).  A steady-state nuScenes pass is enqueued by one library call (cm3d_lift_pass);
-    every other pass is `LiftEngine.run` on the chosen stream.
+    for").  `exec_streams` overrides the policy (tests).  Every pass is enqueued by one library call (cm3d_lift_pass): `submit` and a
+    `rerun` that has to start the build of the lane index go through `LiftEngine.run` on the chosen stream, every other `rerun` hands the
+    slot's descriptor to cm3d_pipe_submit, which picks the stream itself.
 
     Rule for callers that use `streams[slot]` or `engines[slot]` directly (an upload, a pass stage by stage, a graph capture): the device
     must be idle before and after -- `torch.cuda.synchronize()` on both sides --, because the slot's last pass need not have run on
@@ -1010,13 +1009,10 @@ class LiftPipeline:
                 self.uploaded[slot].record(st)
                 if masks == "dense":
                     eng.decode_masks_dense()
-                if eng.native_pass_ready(masks, stage_events=stage_events):
-                    check(self.lib.cm3d_lift_pass(eng.refresh_pass_descriptor(), st.cuda_stream), "cm3d_lift_pass")
-                    self.native_passes += 1
-                else:
-                    eng.run(masks=masks, stage_events=stage_events)
+                eng.run(masks=masks, stage_events=stage_events)
         finally:
             self.lib.cm3d_pipe_release(self._h, slot)
+        self.native_passes += 1
         self.masks[slot] = masks
         return slot
 
@@ -1025,23 +1021,20 @@ class LiftPipeline:
         eng = self.engines[slot]
         mode = masks or self.masks[slot]
         self._pin_if_captured()
-        if eng.native_pass_ready(mode):
-            # (a pair of events around the projection kernel rides on the native pass: the library records them, as in `run`)
-            if project_events is None:
-                rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor())
-            else:
-                e0, e1 = eng._raw_events(project_events)
-                rc = self.lib.cm3d_pipe_submit_timed(self._h, slot, eng.refresh_pass_descriptor(), e0, e1)
+        if eng._lane["built"]:
+            # (no stream context, no Python between the launches: what bench.py's headline times.  A pair of events around the
+            # projection kernel rides along, so that a timed pass costs the host what an untimed one does)
+            rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor(eng.resident_masks(mode), project_events))
             if rc < 0:
                 check(rc, "cm3d_pipe_submit")
-            self.native_passes += 1
-            return
-        st = self.streams[self._acquire(slot)]
-        try:
-            with torch.cuda.stream(st):
-                eng.run(masks=mode, project_events=project_events)
-        finally:
-            self.lib.cm3d_pipe_release(self._h, slot)
+        else:                                # the pass has to start the build of the lane index first, and that is Python's to do
+            st = self.streams[self._acquire(slot)]
+            try:
+                with torch.cuda.stream(st):
+                    eng.run(masks=mode, project_events=project_events)
+            finally:
+                self.lib.cm3d_pipe_release(self._h, slot)
+        self.native_passes += 1
 
     def check_status(self, slot):
         """Waits for the slot's last pass and checks its status word."""

@@ -548,15 +548,14 @@ int cm3d_nusc_match(const double *cand_xy, const int32_t *cand_kind, const doubl
                     const double *alphas, int32_t n_alphas, const double *dist_th, int32_t n_th, uint8_t *tp_bits,
                     int32_t *match_idx, int32_t *status, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
 
-/* ---- One steady-state nuScenes pass in one call; passes of several batches on as many streams as the process has queues for ----
+/* ---- One pass over a resident batch in one call; passes of several batches on as many streams as the process has queues for ----
  * Added within ABI v5: new symbols only, no existing call changes, so CM3D_ABI_VERSION stays.  Host code (csrc/pipeline.cpp):
  * no kernel of its own.
  *
- * The descriptor holds what the six calls of a pass over resident run lengths take -- cm3d_rle_erode_pack_begin,
- * cm3d_sweep_project_hits, cm3d_compact_hits, cm3d_medoid2, cm3d_lane_nn, cm3d_box_nms -- under the names their declarations above
- * use.  `size` is sizeof(cm3d_lift_pass_desc): a caller built against another layout is refused (CM3D_ERR_ARG).  `points`, `intensity`
- * and `colsum` may be NULL as in those calls; with `points` NULL the compaction re-derives the in-mask points from the raw rows.
- * `centroid_g` is what the lane search and the boxes read (nuScenes: the same buffer as `centroid`). */
+ * The descriptor holds what the calls of a pass take, under the names their declarations above use.  `size` is
+ * sizeof(cm3d_lift_pass_desc): a caller built against another layout is refused (CM3D_ERR_ARG).  `points`, `intensity` and `colsum`
+ * may be NULL as in those calls; with `points` NULL the compaction re-derives the in-mask points from the raw rows.  `centroid_g` is
+ * what the lane search and the boxes read (without `pose_rt`: the same buffer as `centroid`). */
 typedef struct cm3d_lift_pass_desc {
     int64_t size;
     /* masks */
@@ -572,18 +571,50 @@ typedef struct cm3d_lift_pass_desc {
     float *colsum; void *ws; int64_t ws_bytes;
     int32_t *md_feedback;        /* cm3d_medoid2's feedback word: page-locked host memory the device writes; read here for the hint */
     /* lanes + boxes */
-    const float *centroid_g; const int32_t *mask_frame; const float *lane; const int32_t *lane_off; const int32_t *frame_lane;
+    float *centroid_g; const int32_t *mask_frame; const float *lane; const int32_t *lane_off; const int32_t *frame_lane;
     const void *grid; int32_t *lane_idx; double *lane_dist; const int32_t *class_id; const double *score; const double *prior_wlh;
     const int32_t *is_vehicle; const int32_t *nms_group; const double *nms_thr; const double *ego_xyz; double *box; int32_t *flags;
+    /* what only some batches have */
+    const int32_t *mask_wh;      /* NULL: one mask size; else the cm3d_rle_erode_pack_sized launches */
+    const float *pose_rt;        /* NULL: nuScenes; else cm3d_centroid_transform (centroid -> centroid_g) in front of the lane search */
+    const float *pose_inv;       /* cm3d_box_nms_bounded's (NULL: nuScenes) */
+    double *obb_yaw; int32_t *obb_status; void *obb_ws; int64_t obb_ws_bytes;        /* obb_yaw NULL: no cm3d_obb */
+    /* set anew for every pass */
+    const uint8_t *dense;        /* non-NULL: cm3d_erode_pack of these dense masks instead of the run lengths */
+    void *lane_ready;            /* hipEvent_t the stream waits for in front of the lane search (the build of `grid`); NULL: nothing */
+    void *ev_project[2];         /* optional hipEvent_t: cm3d_(sweep_)project_hits' ev_start, ev_stop */
+    void *ev_stage[5];           /* optional hipEvent_t, recorded in front of the point/mask stages, behind the compaction, the medoid,
+                                    the lane search and the boxes */
     /* sizes */
-    int32_t n_masks, total_runs, W, H, raw_stride, n_sweeps, max_sweeps_per_frame, pt_cap, n_frames, max_pts_per_frame, n_cams, planes,
-            idx_cap, n_tables, n_lane_points, n_classes;
-    int32_t md_hint;             /* non-zero: ask for the one-pass medoid route when *md_feedback says the last batch held no long list */
+    int32_t n_masks, total_runs, W, H, raw_stride, n_sweeps, max_sweeps_per_frame, max_rows_per_sweep, pt_cap, n_frames,
+            max_pts_per_frame, n_cams, planes, idx_cap, n_tables, n_lane_points, n_classes;
     float halfw, min_dist;
+    /* set anew for every pass */
+    int32_t md_hint;             /* non-zero: ask for the one-pass medoid route when *md_feedback says the last batch held no long list */
+    int32_t fused;               /* 0: cm3d_sweep_prep and cm3d_project_hits (needs `points`); else cm3d_sweep_project_hits */
+    int32_t separate_reset;      /* non-zero: cm3d_batch_begin as a launch of its own even where the mask launch could carry the reset */
 } cm3d_lift_pass_desc;
 
-/* Exactly those six calls, in that order, on `stream`; returns the first error.  Launches, arguments and order are those of
- * cm3d_amd.lifting.LiftEngine.run for run-length masks on the fused-sweeps path with the lane index built. */
+/* Every pass over a resident batch: enqueues on `stream`, stopping at and returning the first error (a failed event call:
+ * CM3D_ERR_LAUNCH); NULL events are skipped.  CM3D_ERR_ARG and no call for another `size`, or for !fused without `points`.  This is the only statement of a pass's order -- cm3d_amd.lifting.LiftEngine.run and
+ * cm3d_pipe_submit both end here:
+ *
+ *   the reset rides on the mask launch when !dense && fused && !separate_reset; else   cm3d_batch_begin
+ *   record ev_stage[0]
+ *   if (!fused)           cm3d_sweep_prep
+ *   masks                 dense ? cm3d_erode_pack : cm3d_rle_erode_pack[_sized][_begin]      (_sized: mask_wh; _begin: carries the reset)
+ *   projection            fused ? cm3d_sweep_project_hits : cm3d_project_hits               (ev_project handed through)
+ *   cm3d_compact_hits                                                                       (raw rows only when points == NULL)
+ *   record ev_stage[1]
+ *   cm3d_medoid2                                                                            (flags bit 0 from md_hint and *md_feedback)
+ *   record ev_stage[2]
+ *   if (lane_ready)       hipStreamWaitEvent
+ *   if (pose_rt)          cm3d_centroid_transform
+ *   cm3d_lane_nn
+ *   record ev_stage[3]
+ *   cm3d_box_nms_bounded                                                                    (pose_inv; bound 32 * planes: no frame has more)
+ *   record ev_stage[4]
+ *   if (obb_yaw)          cm3d_obb */
 int cm3d_lift_pass(const cm3d_lift_pass_desc *desc, cm3d_stream_t stream);
 
 /* min(depth, 4, max(1, hw_queues - 1)): the streams that execute passes at the same time (csrc/pipe_sched.h).  hw_queues <= 0: the
@@ -600,9 +631,6 @@ int cm3d_pipe_exec_streams(const void *pipe);
 /* Picks the stream of the slot's next pass, orders it behind the slot's previous pass, enqueues cm3d_lift_pass there and records the
  * slot's event.  Returns the stream's index (>= 0) or an error code (< 0). */
 int cm3d_pipe_submit(void *pipe, int32_t slot, const cm3d_lift_pass_desc *desc);
-/* The same with cm3d_sweep_project_hits' optional ev_start / ev_stop (hipEvent_t, NULL = none) recorded around the projection kernel:
- * a pass that is timed this way is enqueued like every other, so that timing a pass does not change what the host does for it. */
-int cm3d_pipe_submit_timed(void *pipe, int32_t slot, const cm3d_lift_pass_desc *desc, void *ev_start, void *ev_stop);
 /* The same choice and ordering without the pass, for work the caller enqueues itself on streams[returned index]; the caller then
  * calls cm3d_pipe_release, which records the slot's event behind that work. */
 int cm3d_pipe_acquire(void *pipe, int32_t slot);

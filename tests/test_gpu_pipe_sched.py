@@ -1,5 +1,6 @@
-"""LiftPipeline on fewer executing streams than slots (cm3d_pipe_*, csrc/pipe_sched.h) and the native pass submitter (cm3d_lift_pass):
-whatever stream a pass lands on and whoever enqueues it, every slot's download is byte for byte that of a lone LiftEngine.run."""
+"""LiftPipeline on fewer executing streams than slots (cm3d_pipe_*, csrc/pipe_sched.h) and the pass submitter (cm3d_lift_pass):
+whatever stream a pass lands on, every slot's download is byte for byte that of a lone LiftEngine.run, and LiftEngine.run's that of
+the same pass made stage by stage."""
 import functools
 
 import numpy as np
@@ -103,14 +104,128 @@ def test_slot_reuse_with_uploads():
         _same(pipe.collect(slot)[1], want[i], f"batch {i} in slot {slot}")
 
 
+def _waymo_batch():
+    from cm3d_amd import lifting
+    cfg = syn.config("tiny", n_cams=5)
+    frames = [syn.make_waymo_frame(cfg, i) for i in range(3)]
+    centre = np.asarray(frames[0].pose).reshape(4, 4)[:2, 3]
+    classes = lifting.ClassTable.waymo()
+    hb = lifting.pack_frames(frames, [syn.make_lane_table(centre, 30000, seed=4, extent=400.0)], [0] * 3, classes)
+    assert hb.pose_rt is not None
+    return hb, classes
+
+
+def _mixed_batch():
+    from cm3d_amd import lifting
+    from tests import mixed_size_cases as X
+    mixed = X.mixed_tiny_frames(3)
+    hb = lifting.pack_frames(mixed, [syn.make_lane_table(mixed[0].ego_xyz[:2], 3000, seed=5)], [0] * 3)
+    assert hb.mask_wh is not None
+    return hb
+
+
+def _stage_by_stage(eng, masks):
+    """The pass `run` makes, as the stage methods: the launches bench.py's per-stage figures time."""
+    import torch
+    st = torch.cuda.current_stream().cuda_stream
+    fused = eng.can_fuse_sweeps()
+    eng.stage_begin(st)
+    if not fused:
+        eng.stage_sweeps(st)
+    eng.stage_masks(st, masks)
+    if fused:
+        eng.stage_sweep_project(st)
+    else:
+        eng.stage_project(st)
+    eng.stage_compact(st)
+    eng.stage_medoid(st)
+    eng.wait_lane_grid()
+    eng.stage_lanes(st)
+    eng.stage_boxes(st)
+    if eng.obb:
+        eng.stage_obb(st)
+
+
+@pytest.mark.parametrize("case", ["plain", "separate_reset", "dense", "sweeps17", "mixed_sizes", "waymo", "obb", "stage_events",
+                                  "project_events"])
+def test_run_equals_the_pass_stage_by_stage(case, monkeypatch):
+    """LiftEngine.run (one cm3d_lift_pass) against the stage methods on one engine, sentinels written in between, for every branch of the
+    pass: the reset on the mask launch or as a launch of its own (CM3D_FUSED_RESET=0), dense masks, a frame of 17 sweeps (separate sweep
+    and projection launches), mixed mask sizes, Waymo poses, the OBB fit, and the two kinds of timing events."""
+    import torch
+    from cm3d_amd import lifting
+    kw, masks, run_kw = {}, "rle", {}
+    hb = _four()[0][1]                                   # three frames
+    if case == "separate_reset":
+        monkeypatch.setenv("CM3D_FUSED_RESET", "0")
+    elif case == "dense":
+        masks = "dense"
+    elif case == "sweeps17":
+        frames = [syn.make_frame(syn.config("tiny", n_sweeps=17, n_points=400), i) for i in range(2)]
+        hb = lifting.pack_frames(frames, [syn.make_lane_table(frames[0].ego_xyz[:2], 3000, seed=1)], [0] * 2)
+    elif case == "mixed_sizes":
+        hb = _mixed_batch()
+    elif case == "waymo":
+        hb, kw["classes"] = _waymo_batch()
+    elif case == "obb":
+        kw["obb"] = True
+    elif case == "stage_events":
+        run_kw["stage_events"] = []
+    elif case == "project_events":
+        run_kw["project_events"] = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+    eng = lifting.LiftEngine(**kw)
+    eng.fused_sweeps = True                              # (whatever CM3D_FUSED_SWEEPS says)
+    eng.upload(hb)
+    assert eng.can_fuse_sweeps() == (case != "sweeps17")
+    if masks == "dense":
+        eng.decode_masks_dense()
+    _stage_by_stage(eng, masks)
+    torch.cuda.synchronize()
+    want = eng.download()
+    assert want["hit_idx"].size > 20 and (want["flags"] == 3).any()
+    eng.b.hit_idx.fill_(-7); eng.b.box.fill_(0); eng.b.lane_idx.fill_(-7); eng.b.medoid_pos.fill_(-7)
+    if eng.obb:
+        eng.b.obb_yaw.fill_(0); eng.b.obb_status.fill_(-7)
+    torch.cuda.synchronize()
+    eng.run(masks=masks, **run_kw)
+    torch.cuda.synchronize()
+    _same(eng.download(), want, case)
+    # what the pass was told: the branch the case is about
+    d = eng.b.desc
+    assert bool(d.separate_reset) == (case == "separate_reset") and bool(d.dense) == (case == "dense") and bool(d.fused) == (case != "sweeps17")
+    assert bool(d.mask_wh) == (case == "mixed_sizes") and bool(d.pose_rt) == bool(d.pose_inv) == (case == "waymo")
+    assert bool(d.obb_yaw) == (case == "obb") and bool(d.points) == (case == "sweeps17")
+    assert [bool(e) for e in d.ev_stage] == [case == "stage_events"] * 5 and [bool(e) for e in d.ev_project] == [case == "project_events"] * 2
+    if case == "stage_events":
+        ev = run_kw["stage_events"]
+        assert len(ev) == 5 and all(a.elapsed_time(b) >= 0 for a, b in zip(ev, ev[1:]))
+    if case == "project_events":
+        assert run_kw["project_events"][0].elapsed_time(run_kw["project_events"][1]) > 0
+
+
+def test_run_refuses_before_it_enqueues():
+    from cm3d_amd import lifting
+    from cm3d_amd._lib import Cm3dError
+    eng = lifting.LiftEngine()
+    eng.upload(_four()[0][0])
+    ev = []
+    with pytest.raises(Cm3dError, match="dense masks requested but not resident"):
+        eng.run(masks="dense", stage_events=ev)
+    with pytest.raises(ValueError):
+        eng.run(masks="packed", stage_events=ev)
+    assert ev == [] and not eng._lane["built"]           # nothing was started, no event handed out
+    eng.upload(_mixed_batch())
+    with pytest.raises(ValueError, match="different image sizes"):
+        eng.run(masks="dense")
+
+
 def test_native_pass_equals_python_pass():
-    """cm3d_lift_pass against LiftEngine.run on one engine; through a pipeline the plain batch counts as a native pass (with or without a pair
-    of events around the projection kernel), and dense masks, per-stage timing events, a Waymo batch with poses, a mixed-mask-size batch and
-    the OBB fit each go through `run` -- with equal results."""
+    """cm3d_lift_pass called directly against LiftEngine.run on one engine; through a pipeline every pass counts as enqueued by cm3d_lift_pass
+    -- the plain batch (with or without a pair of events around the projection kernel), dense masks, per-stage timing events, a Waymo batch
+    with poses, a mixed-mask-size batch and the OBB fit -- with the results of a lone engine."""
     import torch
     from cm3d_amd import lifting
     from cm3d_amd._lib import check
-    from tests import mixed_size_cases as X
     hbs, want = _four()
     hb, ref = hbs[2], want[2]
     eng = lifting.LiftEngine()
@@ -118,55 +233,45 @@ def test_native_pass_equals_python_pass():
     eng.run(masks="rle")
     torch.cuda.synchronize()
     _same(eng.download(), ref, "python pass")
-    assert eng.native_pass_ready("rle") and not eng.native_pass_ready("dense")
     eng.b.hit_idx.fill_(-7); eng.b.box.fill_(0)
     check(eng.lib.cm3d_lift_pass(eng.refresh_pass_descriptor(), torch.cuda.current_stream().cuda_stream), "cm3d_lift_pass")
     torch.cuda.synchronize()
     _same(eng.download(), ref, "native pass")
 
-    def through(pipe, hb, want, native, masks="rle", submit_kw=None, rerun_kw=None, what=""):
+    def through(pipe, hb, want, masks="rle", submit_kw=None, rerun_kw=None, what=""):
         slot = pipe.submit(hb, masks, **(submit_kw or {}))
         _same(pipe.collect(slot)[1], want, what + ": first pass")
         n0 = pipe.native_passes
         pipe.engines[slot].b.hit_idx.fill_(-7); pipe.engines[slot].b.box.fill_(0)
         torch.cuda.synchronize()
         pipe.rerun(slot, **(rerun_kw or {}))
-        assert pipe.native_passes == n0 + (1 if native else 0), what
+        assert pipe.native_passes == n0 + 1, what
         _same(pipe.collect(slot)[1], want, what + ": second pass")
 
     pipe = lifting.LiftPipeline("cuda:0", depth=2, exec_streams=1)
-    through(pipe, hb, ref, True, what="plain")
+    through(pipe, hb, ref, what="plain")
     n0 = pipe.native_passes
-    slot = pipe.submit(hb, "rle")                    # the lane tables are cached and their index complete: the upload's pass is native too
+    slot = pipe.submit(hb, "rle")                    # the upload's pass too
     assert pipe.native_passes == n0 + 1
     _same(pipe.collect(slot)[1], ref, "plain, submit")
-    through(pipe, hb, _lone(hb, "dense"), False, masks="dense", what="dense masks")
+    through(pipe, hb, _lone(hb, "dense"), masks="dense", what="dense masks")
     ev = []
     n0 = pipe.native_passes
     slot = pipe.submit(hb, "rle", stage_events=ev)
-    assert pipe.native_passes == n0 and len(ev) == 5
+    assert pipe.native_passes == n0 + 1 and len(ev) == 5
     _same(pipe.collect(slot)[1], ref, "stage_events")
     pe = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    # a pair of events around the projection kernel rides on the native pass (the library records it), so that a timed pass costs the host what
+    # a pair of events around the projection kernel rides in the descriptor (the library records it), so that a timed pass costs the host what
     # an untimed one does -- tests/test_gpu_bench_contract.py holds bench.py's timed region, whose every pass carries such a pair on a small run,
-    # to within 30 % of its untimed regions; on an engine alone (`run`) the same pair takes the Python path
-    through(pipe, hb, ref, True, rerun_kw=dict(project_events=pe), what="project_events, native")
+    # to within 30 % of its untimed regions
+    through(pipe, hb, ref, rerun_kw=dict(project_events=pe), what="project_events")
     torch.cuda.synchronize()
     assert pe[0].elapsed_time(pe[1]) > 0
-    assert not pipe.engines[0].native_pass_ready("rle", project_events=pe)
-    mixed = X.mixed_tiny_frames(3)
-    lanes = [syn.make_lane_table(mixed[0].ego_xyz[:2], 3000, seed=5)]
-    hb_m = lifting.pack_frames(mixed, lanes, [0] * 3)
-    assert hb_m.mask_wh is not None
-    through(pipe, hb_m, _lone(hb_m), False, what="mixed mask sizes")
-    through(lifting.LiftPipeline("cuda:0", depth=2, exec_streams=1, obb=True), hb, _lone(hb, obb=True), False, what="obb")
-    cfg = syn.config("tiny", n_cams=5)
-    frames = [syn.make_waymo_frame(cfg, i) for i in range(3)]
-    centre = np.asarray(frames[0].pose).reshape(4, 4)[:2, 3]
-    classes = lifting.ClassTable.waymo()
-    hb_w = lifting.pack_frames(frames, [syn.make_lane_table(centre, 30000, seed=4, extent=400.0)], [0] * 3, classes)
-    assert hb_w.pose_rt is not None
-    through(lifting.LiftPipeline("cuda:0", depth=2, exec_streams=1, classes=classes), hb_w, _lone(hb_w, classes=classes), False, what="waymo")
+    hb_m = _mixed_batch()
+    through(pipe, hb_m, _lone(hb_m), what="mixed mask sizes")
+    through(lifting.LiftPipeline("cuda:0", depth=2, exec_streams=1, obb=True), hb, _lone(hb, obb=True), what="obb")
+    hb_w, classes = _waymo_batch()
+    through(lifting.LiftPipeline("cuda:0", depth=2, exec_streams=1, classes=classes), hb_w, _lone(hb_w, classes=classes), what="waymo")
 
 
 def test_lane_rebuild_under_rotation():
@@ -184,7 +289,7 @@ def test_lane_rebuild_under_rotation():
     for k in range(9, 13):
         pipe.engines[k % 4].rebuild_lane_grid()
         pipe.rerun(k % 4)
-    assert pipe.native_passes == n0                      # a pass that builds the index is not the steady-state pass
+    assert pipe.native_passes == n0 + 4                  # a pass that builds the index is enqueued by cm3d_lift_pass like every other
     for slot in range(4):
         _same(pipe.collect(slot)[1], want[slot], f"slot {slot}")
 
