@@ -95,7 +95,13 @@ SIGNATURES = {
     "cm3d_pipe_wait": (_i32, [_p, _i32]),
     "cm3d_pipe_pin": (_i32, [_p]),
     "cm3d_pipe_last_stream": (_i32, [_p, _i32]),
+    "cm3d_points_in_polygons": (_i32, [_p, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p]),
+    "cm3d_stage2_filter": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, C.c_double, C.c_double,
+                                  _p, _p, _p]),
+    "cm3d_lift_pass_filtered": (_i32, [_p, _p, _p]),
 }
+
+POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order
 
 
 class LiftPassDesc(C.Structure):
@@ -117,6 +123,13 @@ class LiftPassDesc(C.Structure):
                                "n_classes")]
         + [("halfw", _f32), ("min_dist", _f32)]
         + [(n, _i32) for n in ("md_hint", "fused", "separate_reset")])
+
+
+class Stage2FilterDesc(C.Structure):
+    """cm3d_stage2_filter_desc of include/cm3d_hip.h, field for field."""
+    _fields_ = ([("size", _i64)] + [(n, _p) for n in POLY_INDEX_ARRAYS + ("needs_road", "medoid_pos_kept", "on_road")]
+                + [("ev", _p * 2), ("lane_max_dist", C.c_double), ("vehicle_lane_max_dist", C.c_double), ("n_poly_tables", _i32),
+                   ("reserved", _i32)])
 
 
 class Cm3dError(RuntimeError):

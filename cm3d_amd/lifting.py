@@ -19,8 +19,10 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import drivable
 from . import rle as rlemod
 from ._lib import Cm3dError, check
+from .drivable import Stage2Filters  # noqa: F401  (LiftEngine(filters=Stage2Filters(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -63,10 +65,13 @@ class ClassTable:
     nms_thr: np.ndarray        # (g,) float64, squared-distance threshold per NMS label
     nms_group: Optional[np.ndarray] = None   # (n,) int32 NMS label of each class (default: the class itself)
     out_names: Optional[List[str]] = None    # what the writer calls each class (Waymo: the Waymo type)
+    needs_road: Optional[np.ndarray] = None  # (n,) int32 classes the opt-in drivable filter tests (default: car, truck, bus; :775)
 
     def __post_init__(self):
         if self.nms_group is None:
             self.nms_group = np.arange(len(self.names), dtype=np.int32)
+        if self.needs_road is None:
+            self.needs_road = drivable.needs_road(self.names)
 
     @staticmethod
     def nuscenes(shape_priors=None):
@@ -131,6 +136,9 @@ class HostBatch:
                                               # src/waymo/2d_to_3d.py:520-521); None: every mask has the canvas size (width, height)
     lane_key: Optional[tuple] = None          # which lane tables these are, from a caller that knows (pipeline_nuscenes: the map locations)
     raw_shm: Optional[tuple] = None           # (segment name, shape): the sweeps a reader process left in shared memory instead of `raw`
+    polygons: Optional[list] = None           # drivable-area polygon tables, one per lane table (eval_detection.load_drivable_polygons); only
+                                              # an engine with Stage2Filters(drivable=True) reads them
+    polygon_key: Optional[tuple] = None       # which polygon tables these are, from a caller that knows (else a checksum: polygon_tables_key)
     _lane_crc: Optional[tuple] = field(default=None, init=False, repr=False, compare=False)
 
     def lane_tables_key(self):
@@ -140,6 +148,12 @@ class HostBatch:
         if self._lane_crc is None:
             self._lane_crc = (self.lane.shape, self.lane_off.tobytes(), zlib.crc32(np.ascontiguousarray(self.lane).view(np.uint8)))
         return self._lane_crc
+
+    def polygon_tables_key(self):
+        """What LiftEngine keys its cache of polygon indices by."""
+        if self.polygon_key is None:
+            self.polygon_key = drivable.tables_key(self.polygons)
+        return ("polygons",) + tuple(self.polygon_key)
 
     @property
     def n_frames(self):
@@ -408,12 +422,16 @@ class LiftEngine:
     All launches go to torch's current HIP stream and never synchronise."""
 
     def __init__(self, device="cuda:0", classes: Optional[ClassTable] = None, min_dist=MIN_DIST,
-                 hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False):
+                 hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
         obb: also fit KITTI's oriented box of every mask on the device (stage_obb, cm3d_obb: src/kitti/2d_to_3d.py:855-876, :1524);
-        download() then returns `obb_yaw` and `obb_status`.  Off: no OBB buffer, no OBB launch."""
+        download() then returns `obb_yaw` and `obb_status`.  Off: no OBB buffer, no OBB launch.
+        filters: the opt-in stage-2 filters (drivable.Stage2Filters; the reference ships them commented out, :755-785).  With any of them
+        on, `run` enqueues cm3d_lift_pass_filtered -- the plain pass, cm3d_stage2_filter, the box launch again on the kept medoid
+        positions -- and download(full=True) adds `on_road` and `medoid_pos_kept`; `drivable` needs batches with polygon tables
+        (HostBatch.polygons).  None, or all switches off: nothing changes, neither a buffer nor a launch."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -425,6 +443,7 @@ class LiftEngine:
         self.keep_colsum = keep_colsum
         self.keep_cloud = (os.environ.get("CM3D_KEEP_CLOUD", "0") == "1") if keep_cloud is None else bool(keep_cloud)
         self.obb = bool(obb)
+        self.filters = filters if filters is not None and filters.active else None
         _verify_matrix_pipe(self.lib, self.dev)
         self.b = None
         self._lane = None                                    # the lane tables on the device and their spatial index (upload)
@@ -441,6 +460,7 @@ class LiftEngine:
         self.is_vehicle = torch.from_numpy(self.classes.is_vehicle).to(d)
         self.nms_thr = torch.from_numpy(self.classes.nms_thr).to(d)
         self.nms_group = torch.from_numpy(np.ascontiguousarray(self.classes.nms_group, np.int32)).to(d)
+        self.needs_road = torch.from_numpy(np.ascontiguousarray(self.classes.needs_road, np.int32)).to(d) if self.filters else None
 
     # -- upload + allocation
     def upload(self, hb: HostBatch, dense_masks: Optional[torch.Tensor] = None):
@@ -542,6 +562,9 @@ class LiftEngine:
             if len(self._lane_cache) >= 8:                  # a handful of cities per job: keep the cache small
                 self._lane_cache.pop(next(iter(self._lane_cache)))
             self._lane_cache[key] = self._lane
+        if self.filters is not None:
+            b.medoid_pos_kept = e(M); b.on_road = e(M, dtype=torch.uint8)
+            b.polygon_index = self._polygon_index(hb, b.n_tables) if self.filters.drivable else None
         b.dense = dense_masks
         # The bulk data LAST: sweeps and run lengths come from page-locked staging buffers (cm3d_amd.reader) and copy
         # asynchronously; the small arrays above are pageable, their copies block the host until everything queued before them on
@@ -552,8 +575,39 @@ class LiftEngine:
         # what a pass hands to the library (cm3d_lift_pass), filled once; `refresh_pass_descriptor` adds what changes from pass to pass
         b.desc = self._batch_descriptor(b)
         b.desc_ref = ctypes.byref(b.desc)
+        if self.filters is not None:
+            b.filter_desc = self._filter_descriptor(b)
+            b.filter_desc_ref = ctypes.byref(b.filter_desc)
         self.b = b
         return b
+
+    def _polygon_index(self, hb, n_tables):
+        """The batch's polygon index on the device: built on the host once per set of polygon tables (drivable.build_index: static data,
+        a handful of cities per job) and kept beside the lane index, in the cache the engines of a LiftPipeline share."""
+        if hb.polygons is None or len(hb.polygons) != n_tables:
+            raise ValueError("the drivable filter needs HostBatch.polygons: one polygon table per lane table")
+        key = hb.polygon_tables_key()
+        hit = self._lane_cache.get(key)
+        if hit is None:
+            from . import ops
+            hit = ops.upload_polygon_index(drivable.build_index(hb.polygons), self.dev)
+            if len(self._lane_cache) >= 8:
+                self._lane_cache.pop(next(iter(self._lane_cache)))
+            self._lane_cache[key] = hit
+        return hit
+
+    def _filter_descriptor(self, b):
+        """cm3d_stage2_filter_desc of the resident batch (refresh_pass_descriptor's counterpart, run, sets its events)."""
+        f = _lib.Stage2FilterDesc()
+        f.size = ctypes.sizeof(_lib.Stage2FilterDesc)
+        if b.polygon_index is not None:
+            for name in _lib.POLY_INDEX_ARRAYS:
+                setattr(f, name, b.polygon_index[name].data_ptr())
+            f.n_poly_tables = b.polygon_index["n_tables"]
+        f.needs_road = _ptr(self.needs_road)
+        f.medoid_pos_kept, f.on_road = _ptr(b.medoid_pos_kept), _ptr(b.on_road)
+        f.lane_max_dist, f.vehicle_lane_max_dist = self.filters.lane_max_dist, self.filters.vehicle_lane_max_dist
+        return f
 
     def _batch_descriptor(self, b):
         """cm3d_lift_pass_desc of the resident batch: the arguments of the calls a pass makes, name for name (the fields that belong to
@@ -797,7 +851,8 @@ class LiftEngine:
         """One pass of the hot path over the resident batch (asynchronous).  project_events: optional pair of
         torch.cuda.Event recorded around the projection launch on the launch stream (bench.py's roofline timing).
         stage_events: optional list; gets five timing events appended -- before the point/mask stages, behind the compaction,
-        the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them."""
+        the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them.
+        An engine with filters appends two more, around the filter launch (the "drivable" bucket), and enqueues the filtered pass."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
             self.start_lane_grid()
@@ -805,8 +860,17 @@ class LiftEngine:
         if stage_events is not None:
             marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
             stage_events.extend(marks)
-        check(self.lib.cm3d_lift_pass(self.refresh_pass_descriptor(dense, project_events, marks),
-                                      torch.cuda.current_stream(self.dev).cuda_stream), "cm3d_lift_pass")
+        st = torch.cuda.current_stream(self.dev).cuda_stream
+        if self.filters is not None:
+            fmarks = None
+            if stage_events is not None:
+                fmarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                stage_events.extend(fmarks)
+            self.b.filter_desc.ev[:] = self._raw_events(fmarks, 2)
+            check(self.lib.cm3d_lift_pass_filtered(self.refresh_pass_descriptor(dense, project_events, marks), self.b.filter_desc_ref, st),
+                  "cm3d_lift_pass_filtered")
+            return
+        check(self.lib.cm3d_lift_pass(self.refresh_pass_descriptor(dense, project_events, marks), st), "cm3d_lift_pass")
 
     def capture_graph(self, masks="rle"):
         """Captures one pass over the resident batch into a HIP graph and returns it (`g.replay()` re-runs the pass
@@ -912,6 +976,8 @@ class LiftEngine:
             out["colsum"] = b.colsum[:n_idx].cpu().numpy()
         if self.obb:
             out.update(obb_yaw=b.obb_yaw.cpu().numpy(), obb_status=b.obb_status.cpu().numpy())
+        if self.filters is not None:
+            out.update(on_road=b.on_road.cpu().numpy(), medoid_pos_kept=b.medoid_pos_kept.cpu().numpy())
         return out
 
 
@@ -1021,13 +1087,13 @@ class LiftPipeline:
         eng = self.engines[slot]
         mode = masks or self.masks[slot]
         self._pin_if_captured()
-        if eng._lane["built"]:
+        if eng._lane["built"] and eng.filters is None:           # (cm3d_pipe_submit knows only the plain pass)
             # (no stream context, no Python between the launches: what bench.py's headline times.  A pair of events around the
             # projection kernel rides along, so that a timed pass costs the host what an untimed one does)
             rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor(eng.resident_masks(mode), project_events))
             if rc < 0:
                 check(rc, "cm3d_pipe_submit")
-        else:                                # the pass has to start the build of the lane index first, and that is Python's to do
+        else:                                # the pass has to start the build of the lane index first, or is the filtered one: Python's to do
             st = self.streams[self._acquire(slot)]
             try:
                 with torch.cuda.stream(st):

@@ -178,11 +178,19 @@ def _default_matcher():
     return ops.nusc_match
 
 
+def _device_on_road(polygons, xy):
+    """filter_eval_boxes' hook: point_in_polygons for all boxes in one cm3d_points_in_polygons call."""
+    from . import ops
+    return ops.points_in_polygons([polygons], xy).astype(bool)
+
+
 class NativeEval(ev.DetectionEval):
     """DetectionEval with `evaluate` running one matcher call for all groups and thresholds instead of the per-threshold Python
     loops; loading, filtering and `main` (summary, the two json files, the printed table) are the parent's."""
 
     def __init__(self, *args, matcher=None, **kwargs):
+        if matcher is None:                 # the device route: the drivable-area filter, too, is one GPU call per box set
+            kwargs.setdefault("on_road", _device_on_road)
         super().__init__(*args, **kwargs)
         self.matcher = matcher or _default_matcher()
         self.recall_actual = {}

@@ -9,6 +9,7 @@ src/nuscenes/2d_to_3d.py so that parity tests read like calls into the reference
     points_in_masks(points, cams, masks, cam_nums)       :553-620 for all masks of a frame
     erode(mask) / decode(rles)                           :526-527 / :425
     obb_yaws(point_lists)                                src/kitti/2d_to_3d.py:855-876 + :1524 for several lists
+    points_in_polygons(polygon_tables, xy, table)        eval_custom.py:514-519 for many points
 
 They are conveniences for tests and small jobs; the batched path is lifting.LiftEngine.
 """
@@ -243,6 +244,47 @@ def obb_selftest_yaw(R):
     d_R, yaw = _t(R), _e(n, dtype=torch.float64)
     check(L.cm3d_selftest_obb_yaw(d_R.data_ptr(), n, yaw.data_ptr(), _st()), "cm3d_selftest_obb_yaw")
     return yaw.cpu().numpy()
+
+
+# ----------------------------------------------------------------------------- drivable-area polygons
+def upload_polygon_index(ix, device=None):
+    """A polygon index (drivable.build_index) as device tensors, in the order cm3d_points_in_polygons takes them, plus `n_tables`.
+    (Empty arrays get one element: nothing reads it, and a device pointer is never null.)"""
+    d = device or _dev()
+    out = {k: torch.from_numpy(np.ascontiguousarray(ix[k] if ix[k].size else np.zeros((1,) + ix[k].shape[1:], ix[k].dtype))).to(d)
+           for k in _lib.POLY_INDEX_ARRAYS}
+    out["n_tables"] = int(ix["n_tables"])
+    return out
+
+
+def points_in_polygons(polygon_tables, xy, table_of_point=None, device_ms=None):
+    """eval_detection.point_in_polygons(polygon_tables[table_of_point[i]], *xy[i]) for every point in ONE cm3d_points_in_polygons
+    call (eval_custom.py:514-519 for all boxes at once).  polygon_tables: a list of tables as load_drivable_polygons returns them, or
+    an index already on the device (upload_polygon_index).  table_of_point None: every point against table 0.  Returns uint8 (n,).
+    device_ms: a list that receives the launch's device time in ms (events)."""
+    from . import drivable
+    L = _lib.lib()
+    xy = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+    n = xy.shape[0]
+    if n >= 2 ** 31:
+        raise _lib.Cm3dError("cm3d_points_in_polygons: offsets are 32-bit")
+    tp = np.zeros(n, np.int32) if table_of_point is None else np.ascontiguousarray(table_of_point, np.int32).reshape(-1)
+    if tp.size != n:
+        raise ValueError("points_in_polygons: one table per point")
+    dix = polygon_tables if isinstance(polygon_tables, dict) else upload_polygon_index(drivable.build_index(polygon_tables))
+    if n == 0 or dix["n_tables"] == 0:
+        return np.zeros(n, np.uint8)
+    d_xy, d_tp, inside = _t(xy), _t(tp), _e(n, dtype=torch.uint8)
+    if device_ms is not None:
+        ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev[0].record()
+    check(L.cm3d_points_in_polygons(d_xy.data_ptr(), d_tp.data_ptr(), n, *[dix[k].data_ptr() for k in _lib.POLY_INDEX_ARRAYS],
+                                    dix["n_tables"], inside.data_ptr(), _st()), "cm3d_points_in_polygons")
+    if device_ms is not None:
+        ev[1].record()
+        ev[1].synchronize()
+        device_ms.append(ev[0].elapsed_time(ev[1]))
+    return inside.cpu().numpy()
 
 
 # ----------------------------------------------------------------------------- a10

@@ -57,6 +57,25 @@ class BatchTask:
     through_shm: bool = False                      # a reader process: the sweeps (nearly all of the bytes) go through shared memory
     reader_threads: Optional[int] = None           # a reader process: threads of the native loader it creates, once, for itself
     reader: Optional["reader.Reader"] = None       # a caller in this process: the native loader to use
+    drivable: bool = False                         # --drivable-filter: the batches carry their maps' drivable-area polygons
+
+
+_POLYGONS = {}
+
+
+def drivable_polygons(dataroot, location):
+    """The drivable-area polygons of a map location (eval_detection.load_drivable_polygons), loaded once per process."""
+    key = (dataroot, location)
+    if key not in _POLYGONS:
+        from . import eval_detection
+        _POLYGONS[key] = eval_detection.load_drivable_polygons(dataroot, location)
+    return _POLYGONS[key]
+
+
+def _attach_polygons(hb, dataroot, locations):
+    """The polygon tables of a batch whose lane table k is that of locations[k] (the --drivable-filter route)."""
+    hb.polygons = [drivable_polygons(dataroot, loc) for loc in locations]
+    hb.polygon_key = (dataroot, tuple(locations))
 
 
 def _batch_manifest(tables, names, mask_dir, n_sweeps, ratio, missing_ok):
@@ -101,6 +120,8 @@ def prepare_scene_batch(task: BatchTask):
             return np.ndarray((int(n_floats),), np.float32, buffer=shm.buf)
         try:
             hb, _ = lifting.pack_manifest(man, lanes, frame_lane, classes, native, alloc=shm_alloc if task.through_shm else None)
+            if task.drivable and hb is not None:
+                _attach_polygons(hb, tables.dataroot, [tables.location(tables.scene_by_name(n)) for n in task.names])
             if task.through_shm and hb is not None:
                 hb.raw_shm, hb.raw = (segs[-1].name, hb.raw.shape), None
                 for shm in segs[:-1]:              # a repack after dropping mask-less frames allocated twice
@@ -123,6 +144,8 @@ def prepare_scene_batch(task: BatchTask):
     for (W, H) in sorted({(frames[i].width, frames[i].height) for i in live}):
         sel = [i for i in live if (frames[i].width, frames[i].height) == (W, H)]
         batches.append(lifting.pack_frames([frames[i] for i in sel], lanes, [frame_lane[i] for i in sel], classes))
+        if task.drivable:
+            _attach_polygons(batches[-1], tables.dataroot, [tables.location(tables.scene_by_name(n)) for n in task.names])
     if task.through_shm:
         for hb in batches:
             shm = shared_memory.SharedMemory(create=True, size=max(hb.raw.nbytes, 16))
@@ -195,13 +218,14 @@ def _token_batches(batches, index, host_s):
         host_s = 0.0
 
 
-def _lift_batches(prepared, device, classes, masks, timer, on_records=None):
+def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
     on_records(records of one batch as numpy, first output index, number of samples): called per finished batch whose samples are a
-    contiguous run of the output order, with (None, 0, 0) otherwise."""
-    pipe = lifting.LiftPipeline(device, depth=2, classes=classes)
+    contiguous run of the output order, with (None, 0, 0) otherwise.  filters: the opt-in stage-2 filters (lifting.Stage2Filters); the
+    time of their launch goes into the reference's "drivable" bucket."""
+    pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters)
     records, pending, segments = [], [], []                            # pending: (slot, frame ids, stage events) in flight, oldest first
 
     def spent(key, since):
@@ -219,9 +243,10 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None):
                     on_records(records[-1].cpu().numpy(), first, len(ids))
                 else:
                     on_records(None, 0, 0)
-            if len(evs) == 5:                                          # (complete: the slot's stream has been synchronised)
-                for key, a, b in (("points in mask", 0, 1), ("medoid", 1, 2), ("closest lane", 2, 3), ("nms", 3, 4)):
-                    timer[key] = timer.get(key, 0.0) + evs[a].elapsed_time(evs[b]) * 1e-3
+            if len(evs) in (5, 7):                                     # (complete: the slot's stream has been synchronised)
+                for key, a, b in (("points in mask", 0, 1), ("medoid", 1, 2), ("closest lane", 2, 3), ("nms", 3, 4), ("drivable", 5, 6)):
+                    if b < len(evs):
+                        timer[key] = timer.get(key, 0.0) + evs[a].elapsed_time(evs[b]) * 1e-3
 
     try:
         for hb, ids, host_s in prepared:
@@ -250,7 +275,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None):
 
 
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
-                scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1):
+                scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -261,7 +286,8 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
     if token_index is None:
         token_index = {t: i for i, t in enumerate(sample_tokens(tables, scene_names))}
     _WORKER_TABLES.setdefault((tables.version, tables.dataroot), tables)
-    tasks = [BatchTask(tables.version, tables.dataroot, mask_dir, list(scene_names[b0:b0 + scenes_per_batch]), n_sweeps, ratio, missing_ok, priors)
+    tasks = [BatchTask(tables.version, tables.dataroot, mask_dir, list(scene_names[b0:b0 + scenes_per_batch]), n_sweeps, ratio, missing_ok, priors,
+                       drivable=bool(filters is not None and filters.drivable))
              for b0 in range(0, len(scene_names), scenes_per_batch)]
 
     def prepared():                                    # (starts with the first batch asked for: the readers spawn once the engines exist)
@@ -282,7 +308,7 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
                 pool.terminate()
                 pool.join()
     with contextlib.closing(prepared()) as batches:
-        return _lift_batches(batches, device, classes, masks, timer)
+        return _lift_batches(batches, device, classes, masks, timer, filters=filters)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -327,7 +353,7 @@ def _native_batch_head(nt, names, mask_dir, n_sweeps, ratio, classes, missing_ok
     return man, counts, rle_off, fmo, wh, lanes, frame_lane, locs
 
 
-def _native_batch_tail(nt, head, sub=None, rd=None):
+def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
     """Second host stage: the batch's sweeps read straight into a page-locked buffer, and the HostBatch put together -- without
     a Python statement per frame.  Returns (HostBatch, rows of its frames in sample.json)."""
     man, counts, rle_off, fmo, wh, lanes, frame_lane, locs = head
@@ -348,6 +374,8 @@ def _native_batch_tail(nt, head, sub=None, rd=None):
         class_id=man.class_id, score=man.score, detections_per_frame=[np.diff(man.frame_mask_off)], lane_tables=lanes, frame_lane=frame_lane,
         ego_xyz=man.ego_xyz, width=int(wh[0, 0]), height=int(wh[0, 1]),
         lane_key=(nt.dataroot, tuple(locs)))              # which lane tables these are: LiftEngine keeps their spatial index across batches
+    if drivable:                                           # the same locations' polygons, cached like the lane tables
+        _attach_polygons(hb, nt.dataroot, locs)
     if sub is not None:
         sub["host sweep files"] = sub.get("host sweep files", 0.0) + t1 - t0
         sub["host assemble"] = sub.get("host assemble", 0.0) + time.perf_counter() - t1
@@ -355,7 +383,7 @@ def _native_batch_tail(nt, head, sub=None, rd=None):
 
 
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
-                       scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None):
+                       scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -385,7 +413,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
     def tails():
         for names, head, io_s in _ahead(heads(), depth=1):
             t0 = time.time()
-            got = None if head is None else _native_batch_tail(nt, head, timer, rd_sweeps)
+            got = None if head is None else _native_batch_tail(nt, head, timer, rd_sweeps, bool(filters is not None and filters.drivable))
             yield names, got, max(io_s, time.time() - t0)       # the two stages overlap: the longer one is the wall time
 
     def prepared():
@@ -398,7 +426,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 hb, rows = got
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
-        return _lift_batches(prepared(), device, classes, masks, timer, on_records)
+        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -422,7 +450,15 @@ def main(argv=None):
     ap.add_argument("--reader-threads", type=int, default=int(os.environ.get("CM3D_READER_THREADS", "0")),
                     help="threads of the native loader (libcm3d_reader.so) that reads sweeps and mask files; 0 = one per core, "
                          "-1 = the Python reader (pickle.load / np.fromfile per frame, like the reference)")
+    # the stage-2 filters the reference ships commented out (:755-785); off unless asked for
+    ap.add_argument("--drivable-filter", action="store_true",
+                    help="drop car / truck / bus boxes whose medoid is not on a drivable-area polygon of the map (maps/expansion/<location>.json)")
+    ap.add_argument("--lane-max-dist", type=float, default=None, metavar="M",
+                    help="drop boxes farther than M metres from the nearest lane point (the reference's commented value: 20)")
+    ap.add_argument("--vehicle-lane-max-dist", type=float, default=None, metavar="M",
+                    help="the same for the pushed (vehicle) classes (the reference's commented value: 4)")
     args = ap.parse_args(argv)
+    filters = lifting.Stage2Filters.from_args(args.drivable_filter, args.lane_max_dist, args.vehicle_lane_max_dist)
 
     total_start = time.time()
     rank, world, local_rank = cdist.init_from_env()
@@ -463,7 +499,7 @@ def main(argv=None):
         def python_batch(batch_names):
             tabs = tables_py()
             toks, batches, _ = prepare_scene_batch(BatchTask(args.version, args.dataroot, args.mask_dir, batch_names, args.n_sweeps, args.ratio,
-                                                             args.missing_ok, priors))
+                                                             args.missing_ok, priors, drivable=args.drivable_filter))
             sample_rows = {t: i for i, t in enumerate(tabs.t["sample"].keys())}
             for hb in batches:                                 # its frames named by their row in sample.json, like the native batches'
                 hb.tokens = [sample_rows[t] for t in hb.tokens]
@@ -495,7 +531,7 @@ def main(argv=None):
             write_q.put((rec_np, first, count))
         mine = lift_scenes_native(nt, names[lo:hi], args.mask_dir, classes, device, row_to_out, args.n_sweeps, args.ratio, args.masks, timer,
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
-                                  on_records=on_records if world == 1 else None)
+                                  on_records=on_records if world == 1 else None, filters=filters)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
@@ -503,7 +539,7 @@ def main(argv=None):
         tokens = sample_tokens(tables, names)                  # the whole job's samples, identical on every rank
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
-                           token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads)
+                           token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.

@@ -118,7 +118,14 @@ def main(argv=None):
     ap.add_argument("--scenes", default=os.environ.get("CM3D_SCENES", ""))
     ap.add_argument("--priors", default="cfg/shape_priors_chatgpt.json")
     ap.add_argument("--masks", default="rle", choices=["rle", "dense"])
+    # the lane thresholds the reference ships commented out (src/waymo/2d_to_3d.py:881-934); off unless asked for.  Waymo frames carry no
+    # drivable-area polygons, so there is no --drivable-filter here
+    ap.add_argument("--lane-max-dist", type=float, default=None, metavar="M",
+                    help="drop boxes farther than M metres from the nearest lane point (the reference's commented value: 20)")
+    ap.add_argument("--vehicle-lane-max-dist", type=float, default=None, metavar="M",
+                    help="the same for the pushed (vehicle) classes (the reference's commented value: 4)")
     args = ap.parse_args(argv)
+    filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
     rank, world, local_rank = cdist.init_from_env()
     if os.environ.get("CM3D_SINGLE_DEVICE"):      # rehearsal of the N>1 path on a one-GPU box (with CM3D_DIST_BACKEND=gloo)
@@ -128,7 +135,7 @@ def main(argv=None):
     scenes = [s for s in args.scenes.split(",") if s] or sorted(os.listdir(args.tfrecords if use_tf else args.frames_dir))
     pri = json.load(open(args.priors)) if os.path.exists(args.priors) else None
     classes = lifting.ClassTable.waymo(pri)
-    eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes)
+    eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters)
     lo, hi = cdist.shard_range(len(scenes), rank, world)
     mine, meta = [], {}
     for si in range(lo, hi):

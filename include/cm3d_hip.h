@@ -642,6 +642,76 @@ int cm3d_pipe_pin(void *pipe);
 /* Index of the stream of the slot's last pass, -1 before the first. */
 int cm3d_pipe_last_stream(const void *pipe, int32_t slot);
 
+/* ---- Points in drivable-area polygons, the stage-2 filters and the filtered pass (opt-in) ----
+ * Added within ABI v5: three new symbols, no existing call changes, so CM3D_ABI_VERSION stays.
+ * Replaces the per-box loop of eval_custom.py:496-526 and the filters the reference ships commented out at 2d_to_3d.py:755-785
+ * ("Object lane thresh", "Uncomment for drivable filtering", "Vehicle lane thresh"; src/waymo/2d_to_3d.py:881-934).
+ *
+ * The test, in float64 and without contraction (host statement: cm3d_amd.eval_detection.point_in_polygons): an edge (xs, ys) ->
+ * (xn, yn) of a ring is crossed iff (ys > y) != (yn > y) and x < ((xn - xs) * (y - ys)) / (yn - ys) + xs; a ring's parity is the
+ * parity of its crossed edges, counted PER RING; a ring of fewer than 3 nodes is ignored; a point is inside a polygon iff its exterior's
+ * parity is odd and no hole's is; the result is the OR over the table's polygons.  The answer is the brute-force answer for every input
+ * (points on vertices and edges included: the formula decides them).
+ *
+ * The polygon index is built on the host (cm3d_amd.drivable.build_index), once per set of tables; T tables back to back:
+ *  tab_y     double[T][3]  y-min and y-max over the table's nodes, slabs per unit of y (0 with a single slab)
+ *  tab_slab  int32[T][2]   the table's first slab and its number of slabs (0: a table without edges -- every point is outside)
+ *  slab_off  int32[slabs+1] entries of slab s at [slab_off[s], slab_off[s+1]).  A point of a table falls into slab
+ *                          first + min((int)((y - ymin) * per_y), n - 1); a point outside [y-min, y-max] is outside
+ *  ent_edge  int32[entries] the slab's edges: every edge whose closed y-interval touches the slab (and, conservatively, the slabs next
+ *                          to those), sorted by edge number, so that the edges of a ring are neighbours and the rings of a polygon too
+ *  ent_ring  int32[entries] the ring of each entry's edge
+ *  edge      double[E][4]  xs, ys, xn, yn
+ *  ring_info int32[R]      2 * polygon number + (1 for a hole); rings in polygon order, a polygon's exterior first
+ * Every count is below 2^31 (the host raises otherwise).  The kernels allocate nothing and write only inside[p] / medoid_pos_kept[m] /
+ * on_road[m]; a table number outside [0, n_tables) reads as "outside".  One wave per point.
+ *
+ *  xy double[n_points][2]; point_table int32[n_points] the table of each point; inside uint8[n_points] OUT 0 / 1 */
+int cm3d_points_in_polygons(const double *xy, const int32_t *point_table, int32_t n_points, const double *tab_y,
+                            const int32_t *tab_slab, const int32_t *slab_off, const int32_t *ent_edge, const int32_t *ent_ring,
+                            const double *edge, const int32_t *ring_info, int32_t n_tables, uint8_t *inside, cm3d_stream_t stream);
+
+/* The stage-2 filters on what a pass left in device memory.  Mask m's point is its medoid in the global frame,
+ * ((double)centroid_g[3m], (double)centroid_g[3m+1]) -- the reference's float(m_x), float(m_y), not the pushed centre --, its table
+ * frame_lane[mask_frame[m]]: the location index of the lane tables.  tab_y == NULL: no polygons, no road test (the other index
+ * arrays and needs_road are then ignored).
+ *   medoid_pos_kept[m] = medoid_pos[m], unless the mask has a centroid (medoid_pos[m] >= 0) and is dropped; then -1.  Dropped iff
+ *     lane_dist[m] > lane_max_dist                                              (any class, :755), or
+ *     is_vehicle[cls] && lane_dist[m] > vehicle_lane_max_dist                   (:782), or
+ *     polygons given && needs_road[cls] && the point is not inside               (:775; car, truck and bus)
+ *   strict > on float64, so a threshold of +inf is off.
+ *   on_road[m] = 1 iff polygons are given, the mask has a centroid and its point is inside (every class); else 0. */
+int cm3d_stage2_filter(const float *centroid_g, const int32_t *medoid_pos, const int32_t *mask_frame, const int32_t *frame_lane,
+                       const int32_t *class_id, const double *lane_dist, int32_t n_masks, int32_t n_frames, const double *tab_y,
+                       const int32_t *tab_slab, const int32_t *slab_off, const int32_t *ent_edge, const int32_t *ent_ring,
+                       const double *edge, const int32_t *ring_info, int32_t n_tables, const int32_t *needs_road,
+                       const int32_t *is_vehicle, int32_t n_classes, double lane_max_dist, double vehicle_lane_max_dist,
+                       int32_t *medoid_pos_kept, uint8_t *on_road, cm3d_stream_t stream);
+
+/* What the filtered pass needs beyond cm3d_lift_pass_desc.  `size` is sizeof(cm3d_stage2_filter_desc) (another value: CM3D_ERR_ARG).
+ * The index arrays and needs_road as in cm3d_stage2_filter (tab_y NULL: no road test); n_poly_tables = the batch's n_tables. */
+typedef struct cm3d_stage2_filter_desc {
+    int64_t size;
+    const double *tab_y; const int32_t *tab_slab; const int32_t *slab_off; const int32_t *ent_edge; const int32_t *ent_ring;
+    const double *edge; const int32_t *ring_info; const int32_t *needs_road;
+    int32_t *medoid_pos_kept; uint8_t *on_road;
+    void *ev[2];                 /* optional hipEvent_t, recorded in front of and behind the filter launch */
+    double lane_max_dist, vehicle_lane_max_dist;
+    int32_t n_poly_tables, reserved;
+} cm3d_stage2_filter_desc;
+
+/* The opt-in filtered pass (host code, csrc/pass_filter.cpp; cm3d_lift_pass and cm3d_pipe_submit know nothing of it).  Enqueues on
+ * `stream`, stopping at and returning the first error:
+ *
+ *   cm3d_lift_pass(desc)                  the plain pass, boxes of every mask included
+ *   record filter->ev[0]
+ *   cm3d_stage2_filter                    centroid_g, medoid_pos, lane_dist ... of desc -> medoid_pos_kept, on_road
+ *   record filter->ev[1]
+ *   cm3d_box_nms_bounded                  as in the plain pass, with medoid_pos_kept for medoid_pos: `box` and `flags` written anew
+ *
+ * k_box_nms treats a negative position as "no box", so a dropped mask neither gets a box nor suppresses one. */
+int cm3d_lift_pass_filtered(const cm3d_lift_pass_desc *desc, const cm3d_stage2_filter_desc *filter, cm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

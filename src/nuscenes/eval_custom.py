@@ -3,7 +3,8 @@
 and flags; the tables are read by cm3d_amd.nusc_io.NuscTables instead of nuscenes-devkit, so `--eval_set` is either
 `all` (every scene of the tables, the default), a comma-separated list of scene names, or a JSON file holding such a list.
 Plot / render flags are accepted for command-line compatibility and ignored (no matplotlib dependency here).
-`--metrics device` runs the matching on the GPU (cm3d_nusc_match through cm3d_amd.nusc_eval); the default `host` is the Python loop."""
+`--metrics device` runs the matching on the GPU (cm3d_nusc_match through cm3d_amd.nusc_eval); the default `host` is the Python loop.
+With `--drivable_filtering 1` the device route also answers the drivable-area filter on the GPU (cm3d_points_in_polygons), one call per box set."""
 import argparse
 import json
 import os
