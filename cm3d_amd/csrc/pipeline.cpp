@@ -1,5 +1,5 @@
 // Host side of a pass: one call that enqueues every launch of a pass over a resident batch (cm3d_lift_pass: the only statement of a
-// pass's order, include/cm3d_hip.h spells it out), and the pipeline object that decides which stream a slot's pass goes to
+// pass's order, include/cm3d_hip.h spells it out; its two halves, through the compaction and from the medoid on, are exported too), and the pipeline object that decides which stream a slot's pass goes to
 // (csrc/pipe_sched.h) and keeps two passes of one slot in order when they land on different streams.  No kernel lives here: every
 // launch goes through the entry points of include/cm3d_hip.h.
 #include <hip/hip_runtime_api.h>
@@ -31,10 +31,22 @@ static int lift_masks(const cm3d_lift_pass_desc *d, bool on_masks, cm3d_stream_t
                                           d->rle_ws_bytes, st);
 }
 
+static bool bad_desc(const cm3d_lift_pass_desc *d)
+{
+    if (!d || d->size != (int64_t)sizeof(cm3d_lift_pass_desc)) return true;
+    return !d->fused && !d->points;                          // the separate launches hand the cloud from one to the other
+}
+
 extern "C" int cm3d_lift_pass(const cm3d_lift_pass_desc *d, cm3d_stream_t st)
 {
-    if (!d || d->size != (int64_t)sizeof(cm3d_lift_pass_desc)) return CM3D_ERR_ARG;
-    if (!d->fused && !d->points) return CM3D_ERR_ARG;        // the separate launches hand the cloud from one to the other
+    if (bad_desc(d)) return CM3D_ERR_ARG;
+    const int rc = cm3d_lift_pass_head(d, st);
+    return rc != CM3D_OK ? rc : cm3d_lift_pass_tail(d, st);
+}
+
+extern "C" int cm3d_lift_pass_head(const cm3d_lift_pass_desc *d, cm3d_stream_t st)
+{
+    if (bad_desc(d)) return CM3D_ERR_ARG;
     int rc;
     // (resident run lengths on the fused-sweeps path: the mask launch is the pass's first and carries the reset -- one launch and one
     // launch boundary less per pass)
@@ -62,7 +74,13 @@ extern "C" int cm3d_lift_pass(const cm3d_lift_pass_desc *d, cm3d_stream_t st)
                            d->removed_bits, from_raw ? d->raw : nullptr, d->raw_stride, from_raw ? d->intensity : nullptr,
                            from_raw ? d->sweep_xf : nullptr, d->points, d->hit_off, d->tile_off, d->hit_idx, nullptr, d->hit_xyz, d->idx_cap,
                            d->tile_work, d->status, d->pg_ws, d->pg_ws_bytes, st);
-    if (rc != CM3D_OK || (rc = record(d->ev_stage[1], st)) != CM3D_OK) return rc;
+    return rc != CM3D_OK ? rc : record(d->ev_stage[1], st);
+}
+
+extern "C" int cm3d_lift_pass_tail(const cm3d_lift_pass_desc *d, cm3d_stream_t st)
+{
+    if (bad_desc(d)) return CM3D_ERR_ARG;
+    int rc;
     // the hint: whatever the device has written into the page-locked word by now (a stale value costs time on one pass, never a result)
     int32_t md_flags = 0;
     if (d->md_hint && d->md_feedback && *(const volatile int32_t *)d->md_feedback == 0) md_flags = 1;

@@ -178,8 +178,10 @@ def labels_of_frame(hb, res, f, classes, shape_priors, obb="host"):
         raise ValueError(obb)
     from .lifting import get_detection_name
     pred, pseudo = [], []
+    # (an engine with a depth clustering: the clustered lists are the lists -- the <= 3 points rule and the host fit read them)
+    off, xyz = ("cl_off", "cl_xyz") if "cl_off" in res else ("hit_off", "hit_xyz")
     for m in range(hb.mask_off[f], hb.mask_off[f + 1]):
-        o, e = res["hit_off"][m], res["hit_off"][m + 1]
+        o, e = res[off][m], res[off][m + 1]
         if e - o <= 3:                                   # :1479-1480
             continue
         st = int(res["obb_status"][m]) if obb == "device" else None
@@ -187,11 +189,11 @@ def labels_of_frame(hb, res, f, classes, shape_priors, obb="host"):
             yaw = 0.0
         elif st == OBB_FITTED:
             yaw = float(res["obb_yaw"][m])
-        elif st is not None and "hit_xyz" not in res:
+        elif st is not None and xyz not in res:
             raise RuntimeError(f"mask {m}: the device box fit gave status {st}; download the in-mask points (download(full=True)) "
                                "to fit it on the host, or run with --obb host")
         else:                                            # host mode, or a mask the device could not fit (status 4): the host fit
-            pts = res["hit_xyz"][o:e, :3]                # the in-mask points (:1479), laid out like hit_idx
+            pts = res[xyz][o:e, :3]                      # the in-mask points (:1479), laid out like hit_idx
             try:
                 yaw = obb_yaw(pts)
             except Exception:                            # :1481-1484: bare except -> identity box

@@ -23,6 +23,7 @@ from . import drivable
 from . import rle as rlemod
 from ._lib import Cm3dError, check
 from .drivable import Stage2Filters  # noqa: F401  (LiftEngine(filters=Stage2Filters(...)))
+from .cluster import DepthCluster  # noqa: F401  (LiftEngine(cluster=DepthCluster(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -422,7 +423,8 @@ class LiftEngine:
     All launches go to torch's current HIP stream and never synchronise."""
 
     def __init__(self, device="cuda:0", classes: Optional[ClassTable] = None, min_dist=MIN_DIST,
-                 hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None):
+                 hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
+                 cluster: Optional[DepthCluster] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -431,7 +433,13 @@ class LiftEngine:
         filters: the opt-in stage-2 filters (drivable.Stage2Filters; the reference ships them commented out, :755-785).  With any of them
         on, `run` enqueues cm3d_lift_pass_filtered -- the plain pass, cm3d_stage2_filter, the box launch again on the kept medoid
         positions -- and download(full=True) adds `on_road` and `medoid_pos_kept`; `drivable` needs batches with polygon tables
-        (HostBatch.polygons).  None, or all switches off: nothing changes, neither a buffer nor a launch."""
+        (HostBatch.polygons).  None, or all switches off: nothing changes, neither a buffer nor a launch.
+        cluster: the opt-in depth clustering of the in-mask lists (cluster.DepthCluster; the reference's clusters_hdbscan is dead code).
+        `run` then enqueues cm3d_lift_pass_clustered -- the pass through the compaction, cm3d_depth_cluster with the batch's `ego_xyz` as
+        the frames' origins, the rest of the pass on the clustered lists -- so that `medoid_pos` is a position in the clustered list
+        (`cl_off`), and the OBB fit sees those lists too; download() adds `cl_off`, `cl_status` (full=True: `cl_idx`, `cl_xyz`), while
+        `hit_off` / `hit_idx` / `hit_xyz` stay the raw lists.  With filters also on, the filter and the second box launch follow
+        through their own calls.  None: nothing changes, neither a buffer nor a launch."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -444,6 +452,7 @@ class LiftEngine:
         self.keep_cloud = (os.environ.get("CM3D_KEEP_CLOUD", "0") == "1") if keep_cloud is None else bool(keep_cloud)
         self.obb = bool(obb)
         self.filters = filters if filters is not None and filters.active else None
+        self.cluster = cluster if cluster is not None and cluster.active else None
         _verify_matrix_pipe(self.lib, self.dev)
         self.b = None
         self._lane = None                                    # the lane tables on the device and their spatial index (upload)
@@ -565,6 +574,11 @@ class LiftEngine:
         if self.filters is not None:
             b.medoid_pos_kept = e(M); b.on_road = e(M, dtype=torch.uint8)
             b.polygon_index = self._polygon_index(hb, b.n_tables) if self.filters.drivable else None
+        if self.cluster is not None:
+            b.cl_off = e(M + 1); b.cl_tile_off = e(M + 1); b.cl_status = e(M)
+            b.cl_idx = e(b.idx_cap); b.cl_xyz = e(b.idx_cap, 4, dtype=torch.float32)
+            b.cl_ws_bytes = int(L.cm3d_depth_cluster_workspace_bytes(M, b.idx_cap))
+            b.cl_ws = torch.empty(max(b.cl_ws_bytes, 16), dtype=torch.uint8, device=d)
         b.dense = dense_masks
         # The bulk data LAST: sweeps and run lengths come from page-locked staging buffers (cm3d_amd.reader) and copy
         # asynchronously; the small arrays above are pageable, their copies block the host until everything queued before them on
@@ -578,6 +592,9 @@ class LiftEngine:
         if self.filters is not None:
             b.filter_desc = self._filter_descriptor(b)
             b.filter_desc_ref = ctypes.byref(b.filter_desc)
+        if self.cluster is not None:
+            b.cluster_desc = self._cluster_descriptor(b)
+            b.cluster_desc_ref = ctypes.byref(b.cluster_desc)
         self.b = b
         return b
 
@@ -608,6 +625,18 @@ class LiftEngine:
         f.medoid_pos_kept, f.on_road = _ptr(b.medoid_pos_kept), _ptr(b.on_road)
         f.lane_max_dist, f.vehicle_lane_max_dist = self.filters.lane_max_dist, self.filters.vehicle_lane_max_dist
         return f
+
+    def _cluster_descriptor(self, b):
+        """cm3d_depth_cluster_desc of the resident batch (run sets its events).  The origin of frame f is ego_xyz[f]: the LIDAR_TOP ego
+        translation on nuScenes, zeros on Waymo (vehicle frame) and on KITTI (reference-camera frame)."""
+        c = _lib.DepthClusterDesc()
+        c.size = ctypes.sizeof(_lib.DepthClusterDesc)
+        c.origin = _ptr(b.ego_xyz)
+        for name in ("cl_off", "cl_tile_off", "cl_idx", "cl_xyz", "cl_status"):
+            setattr(c, name, _ptr(getattr(b, name)))
+        c.ws, c.ws_bytes = _ptr(b.cl_ws), b.cl_ws_bytes
+        c.eps, c.min_points, c.pick = self.cluster.eps, self.cluster.min_points, self.cluster.pick_index
+        return c
 
     def _batch_descriptor(self, b):
         """cm3d_lift_pass_desc of the resident batch: the arguments of the calls a pass makes, name for name (the fields that belong to
@@ -845,6 +874,34 @@ class LiftEngine:
         check(self.lib.cm3d_obb(_ptr(b.hit_xyz), _ptr(b.hit_off), b.M, b.idx_cap, _ptr(b.obb_yaw), _ptr(b.obb_status), 0, 0,
                                 _ptr(b.obb_ws), b.obb_ws_bytes, st), "cm3d_obb")
 
+    def stage_cluster(self, st):
+        """The depth clustering alone, on the raw lists the last pass left resident (cm3d_depth_cluster: what the clustered pass
+        enqueues between the compaction and the medoid)."""
+        b, c = self.b, self.b.cluster_desc
+        check(self.lib.cm3d_depth_cluster(_ptr(b.hit_xyz), _ptr(b.hit_idx), _ptr(b.hit_off), _ptr(b.mask_frame), b.M, b.idx_cap, c.origin, b.F,
+                                          c.eps, c.min_points, c.pick, c.cl_off, c.cl_tile_off, c.cl_idx, c.cl_xyz, c.cl_status, c.ws,
+                                          c.ws_bytes, st), "cm3d_depth_cluster")
+
+    def stage_filter(self, st, events=None):
+        """The stage-2 filter on the resident results and the box launch again on the kept medoid positions (what
+        cm3d_lift_pass_filtered enqueues behind the plain pass), for the pass that is not the plain one.  events: optional pair of
+        torch.cuda.Event recorded around the filter launch."""
+        b, f = self.b, self.b.filter_desc
+        if events is not None:
+            events[0].record(torch.cuda.current_stream(self.dev))
+        check(self.lib.cm3d_stage2_filter(_ptr(b.centroid_g), _ptr(b.medoid_pos), _ptr(b.mask_frame), _ptr(b.frame_lane), _ptr(b.class_id),
+                                          _ptr(b.lane_dist), b.M, b.F, f.tab_y, f.tab_slab, f.slab_off, f.ent_edge, f.ent_ring, f.edge,
+                                          f.ring_info, f.n_poly_tables, f.needs_road, _ptr(self.is_vehicle), len(self.classes.names),
+                                          f.lane_max_dist, f.vehicle_lane_max_dist, f.medoid_pos_kept, f.on_road, st), "cm3d_stage2_filter")
+        if events is not None:
+            events[1].record(torch.cuda.current_stream(self.dev))
+        check(self.lib.cm3d_box_nms_bounded(_ptr(b.centroid_g), _ptr(b.medoid_pos_kept), _ptr(b.mask_off), b.F, b.M, _ptr(b.class_id),
+                                            _ptr(b.score), _ptr(b.lane), _ptr(b.lane_off), _ptr(b.frame_lane), _ptr(b.lane_idx),
+                                            _ptr(b.lane_dist), _ptr(self.prior_wlh), _ptr(self.is_vehicle), _ptr(self.nms_group),
+                                            _ptr(self.nms_thr), len(self.classes.names), _ptr(b.ego_xyz), _ptr(b.pose_inv),
+                                            min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), _ptr(b.box), _ptr(b.flags), st),
+              "cm3d_box_nms_bounded")
+
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
     def run(self, masks="dense", project_events=None, stage_events=None):
@@ -852,7 +909,9 @@ class LiftEngine:
         torch.cuda.Event recorded around the projection launch on the launch stream (bench.py's roofline timing).
         stage_events: optional list; gets five timing events appended -- before the point/mask stages, behind the compaction,
         the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them.
-        An engine with filters appends two more, around the filter launch (the "drivable" bucket), and enqueues the filtered pass."""
+        An engine with filters appends two more, around the filter launch (the "drivable" bucket), and enqueues the filtered pass.
+        An engine with a depth clustering appends two more after those, around the clustering's launches (the "cluster" bucket; they
+        lie between the second and the third of the five), and enqueues the clustered pass."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
             self.start_lane_grid()
@@ -861,11 +920,21 @@ class LiftEngine:
             marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
             stage_events.extend(marks)
         st = torch.cuda.current_stream(self.dev).cuda_stream
-        if self.filters is not None:
-            fmarks = None
+        fmarks = cmarks = None
+        if self.filters is not None and stage_events is not None:
+            fmarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            stage_events.extend(fmarks)
+        if self.cluster is not None:
             if stage_events is not None:
-                fmarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-                stage_events.extend(fmarks)
+                cmarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                stage_events.extend(cmarks)
+            self.b.cluster_desc.ev[:] = self._raw_events(cmarks, 2)
+            check(self.lib.cm3d_lift_pass_clustered(self.refresh_pass_descriptor(dense, project_events, marks), self.b.cluster_desc_ref, st),
+                  "cm3d_lift_pass_clustered")
+            if self.filters is not None:             # the filter and the boxes again, on what the clustered pass left: the existing calls
+                self.stage_filter(st, fmarks)
+            return
+        if self.filters is not None:
             self.b.filter_desc.ev[:] = self._raw_events(fmarks, 2)
             check(self.lib.cm3d_lift_pass_filtered(self.refresh_pass_descriptor(dense, project_events, marks), self.b.filter_desc_ref, st),
                   "cm3d_lift_pass_filtered")
@@ -954,6 +1023,8 @@ class LiftEngine:
                        centroid_global=b.centroid_g.cpu().numpy(), box=b.box.cpu().numpy(), flags=b.flags.cpu().numpy())
             if self.obb:
                 out.update(obb_yaw=b.obb_yaw.cpu().numpy(), obb_status=b.obb_status.cpu().numpy())
+            if self.cluster is not None:
+                out.update(cl_off=b.cl_off.cpu().numpy(), cl_status=b.cl_status.cpu().numpy())
             return out
         n_rows, n_idx = int(s[1]), int(s[2])
         pt_off_rows = b.pt_off.cpu().numpy()
@@ -978,6 +1049,11 @@ class LiftEngine:
             out.update(obb_yaw=b.obb_yaw.cpu().numpy(), obb_status=b.obb_status.cpu().numpy())
         if self.filters is not None:
             out.update(on_road=b.on_road.cpu().numpy(), medoid_pos_kept=b.medoid_pos_kept.cpu().numpy())
+        if self.cluster is not None:
+            cl_off = b.cl_off.cpu().numpy()
+            n_cl = int(cl_off[-1])
+            out.update(cl_off=cl_off, cl_status=b.cl_status.cpu().numpy(), cl_idx=b.cl_idx[:n_cl].cpu().numpy(),
+                       cl_xyz=b.cl_xyz[:n_cl].cpu().numpy())
         return out
 
 
@@ -1087,13 +1163,13 @@ class LiftPipeline:
         eng = self.engines[slot]
         mode = masks or self.masks[slot]
         self._pin_if_captured()
-        if eng._lane["built"] and eng.filters is None:           # (cm3d_pipe_submit knows only the plain pass)
+        if eng._lane["built"] and eng.filters is None and eng.cluster is None:           # (cm3d_pipe_submit knows only the plain pass)
             # (no stream context, no Python between the launches: what bench.py's headline times.  A pair of events around the
             # projection kernel rides along, so that a timed pass costs the host what an untimed one does)
             rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor(eng.resident_masks(mode), project_events))
             if rc < 0:
                 check(rc, "cm3d_pipe_submit")
-        else:                                # the pass has to start the build of the lane index first, or is the filtered one: Python's to do
+        else:                                # the pass has to start the build of the lane index first, or is the filtered or clustered one: Python's to do
             st = self.streams[self._acquire(slot)]
             try:
                 with torch.cuda.stream(st):

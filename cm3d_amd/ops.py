@@ -10,6 +10,7 @@ src/nuscenes/2d_to_3d.py so that parity tests read like calls into the reference
     erode(mask) / decode(rles)                           :526-527 / :425
     obb_yaws(point_lists)                                src/kitti/2d_to_3d.py:855-876 + :1524 for several lists
     points_in_polygons(polygon_tables, xy, table)        eval_custom.py:514-519 for many points
+    depth_cluster(point_lists, origins, eps, ...)        the opt-in depth clustering of several lists (cluster.depth_cluster_host)
 
 They are conveniences for tests and small jobs; the batched path is lifting.LiftEngine.
 """
@@ -206,6 +207,54 @@ def get_medoids(point_lists, via_rows=False, want_colsum=False):
         cs = colsum.cpu().numpy()
         return out, [cs[hit_off[k]:hit_off[k + 1]] for k in range(n)]
     return out
+
+
+# ----------------------------------------------------------------------------- depth clustering (opt-in)
+def depth_cluster_arrays(point_lists, origins, mask_frame, eps, min_points=20, pick="largest", hit_idx=None, with_idx=True):
+    """cm3d_depth_cluster on lists laid out back to back (one "mask" each).  point_lists: arrays (n_k, 3) or (n_k, 4) of float32;
+    origins (F, 3) float64; mask_frame: the frame of every list; hit_idx: the index entries that travel with the positions (default:
+    each list's own positions 0 .. n_k - 1); with_idx=False: the call without hit_idx / cl_idx.  Returns a dict of numpy arrays:
+    cl_off, cl_tile_off, cl_status, cl_xyz (cl_off[-1], 4), cl_idx (or None), and hit_off."""
+    from .cluster import pick_code
+    L = _lib.lib()
+    Ms = [int(np.asarray(p).shape[0]) for p in point_lists]
+    n, tot = len(Ms), int(sum(Ms))
+    cap = max(tot, 1)
+    P4 = np.zeros((cap, 4), np.float32)
+    o = 0
+    for p, m in zip(point_lists, Ms):
+        if m:
+            p = np.asarray(p, np.float32).reshape(m, -1)
+            P4[o:o + m, :p.shape[1]] = p
+        o += m
+    hit_off = np.concatenate([[0], np.cumsum(Ms)]).astype(np.int32)
+    if hit_idx is None:
+        hit_idx = np.concatenate([np.arange(m, dtype=np.int32) for m in Ms]) if tot else np.zeros(0, np.int32)
+    idx = np.zeros(cap, np.int32)
+    idx[:tot] = np.asarray(hit_idx, np.int32)
+    org = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+    d_xyz, d_idx, d_off, d_mf, d_org = _t(P4), _t(idx), _t(hit_off), _t(mask_frame, np.int32), _t(org)
+    cl_off, cl_tile, cl_st = _e(n + 1), _e(n + 1), _e(n)
+    cl_idx, cl_xyz = _e(cap), _e(cap, 4, dtype=torch.float32)
+    ws = _ws(L.cm3d_depth_cluster_workspace_bytes(n, cap))
+    check(L.cm3d_depth_cluster(d_xyz.data_ptr(), d_idx.data_ptr() if with_idx else 0, d_off.data_ptr(), d_mf.data_ptr(), n, cap,
+                               d_org.data_ptr(), org.shape[0], float(eps), int(min_points), pick_code(pick), cl_off.data_ptr(),
+                               cl_tile.data_ptr(), cl_idx.data_ptr() if with_idx else 0, cl_xyz.data_ptr(), cl_st.data_ptr(), ws.data_ptr(),
+                               ws.numel(), _st()), "cm3d_depth_cluster")
+    off = cl_off.cpu().numpy()
+    k = int(off[-1])
+    return dict(hit_off=hit_off, cl_off=off, cl_tile_off=cl_tile.cpu().numpy(), cl_status=cl_st.cpu().numpy(),
+                cl_xyz=cl_xyz.cpu().numpy()[:k], cl_idx=cl_idx.cpu().numpy()[:k] if with_idx else None)
+
+
+def depth_cluster(point_lists, origins, eps, min_points=20, pick="largest"):
+    """The depth clustering of each list in ONE call of cm3d_depth_cluster (host statement: cluster.depth_cluster_host).  point_lists:
+    arrays (n_k, 3) of float32; origins: (3,) for all lists or (n, 3), one per list.  Returns (kept, status): the kept positions of
+    each list, ascending, and cl_status (n,)."""
+    n = len(point_lists)
+    org = np.array(np.broadcast_to(np.asarray(origins, np.float64).reshape(-1, 3), (n, 3))) if n else np.zeros((1, 3))
+    r = depth_cluster_arrays(point_lists, org, np.arange(n, dtype=np.int32), eps, min_points, pick)
+    return [r["cl_idx"][r["cl_off"][k]:r["cl_off"][k + 1]] for k in range(n)], r["cl_status"]
 
 
 # ----------------------------------------------------------------------------- a18 (KITTI)

@@ -11,6 +11,7 @@ import time
 
 import torch
 
+from . import cluster as clmod
 from . import kitti as kt
 from . import lifting
 
@@ -29,6 +30,7 @@ def main(argv=None):
                     help="where the yaw of the oriented box is fitted (:855-876, :1524): host = scipy/numpy per mask on the downloaded "
                          "in-mask points (the restatement the default output is pinned to); device = cm3d_obb in the pass, only the "
                          "per-mask results come back (eigenvector signs canonical, see include/cm3d_hip.h)")
+    clmod.add_arguments(ap)
     args = ap.parse_args(argv)
     t0 = time.time()
     pri = json.load(open(args.priors)) if os.path.exists(args.priors) else dict(lifting.SHAPE_PRIORS_CHATGPT)
@@ -39,7 +41,7 @@ def main(argv=None):
     os.makedirs(pseudo_dir, exist_ok=True)
     nums = sorted(int(os.path.basename(p).split("_")[0]) for p in glob.glob(os.path.join(args.mask_dir, "*_masks.pkl")))
     device_obb = args.obb == "device"
-    eng = lifting.LiftEngine("cuda:0", classes=classes, obb=device_obb)
+    eng = lifting.LiftEngine("cuda:0", classes=classes, obb=device_obb, cluster=clmod.from_namespace(args))
     lane = [[0.0, 0.0, 0.0]]                   # stage 1 of KITTI uses no lanes; the engine still wants a table
     n_lines = 0
     for b0 in range(0, len(nums), args.batch):

@@ -25,6 +25,7 @@ import time
 import numpy as np
 import torch
 
+from . import cluster as clmod
 from . import dist as cdist
 from . import lifting
 from . import waymo as wm
@@ -124,6 +125,7 @@ def main(argv=None):
                     help="drop boxes farther than M metres from the nearest lane point (the reference's commented value: 20)")
     ap.add_argument("--vehicle-lane-max-dist", type=float, default=None, metavar="M",
                     help="the same for the pushed (vehicle) classes (the reference's commented value: 4)")
+    clmod.add_arguments(ap)
     args = ap.parse_args(argv)
     filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
@@ -135,7 +137,7 @@ def main(argv=None):
     scenes = [s for s in args.scenes.split(",") if s] or sorted(os.listdir(args.tfrecords if use_tf else args.frames_dir))
     pri = json.load(open(args.priors)) if os.path.exists(args.priors) else None
     classes = lifting.ClassTable.waymo(pri)
-    eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters)
+    eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args))
     lo, hi = cdist.shard_range(len(scenes), rank, world)
     mine, meta = [], {}
     for si in range(lo, hi):

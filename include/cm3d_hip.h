@@ -52,6 +52,8 @@ extern "C" {
 #define CM3D_WM_BREAKDOWNS 16    /* breakdowns of cm3d_waymo_metrics: (type - 1) * 4 + shard */
 #define CM3D_WM_CUTOFFS 101      /* score cutoffs of cm3d_waymo_metrics: float32(c * 0.01) */
 #define CM3D_WM_SWEEP_MAX_ALPHAS 1024 /* alphas of one cm3d_waymo_metrics_sweep call (added within ABI v5) */
+#define CM3D_DEPTH_CLUSTER_LDS_POINTS 4096 /* longest list cm3d_depth_cluster sorts in LDS (added within ABI v5): 12 bytes per point,
+                                              48 KiB per workgroup, three workgroups in a CU's 160 KiB */
 
 /* status word written by kernels (int32[4] in device memory, zero it per batch):
  *  [0] bit0: point capacity overflow (cm3d_sweep_prep), bit1: hit-index capacity
@@ -616,6 +618,10 @@ typedef struct cm3d_lift_pass_desc {
  *   record ev_stage[4]
  *   if (obb_yaw)          cm3d_obb */
 int cm3d_lift_pass(const cm3d_lift_pass_desc *desc, cm3d_stream_t stream);
+/* The two halves of that sequence, each with cm3d_lift_pass's argument checks: cm3d_lift_pass_head is everything through
+ * `record ev_stage[1]`, cm3d_lift_pass_tail is cm3d_medoid2 onward.  cm3d_lift_pass is head, then tail. */
+int cm3d_lift_pass_head(const cm3d_lift_pass_desc *desc, cm3d_stream_t stream);
+int cm3d_lift_pass_tail(const cm3d_lift_pass_desc *desc, cm3d_stream_t stream);
 
 /* min(depth, 4, max(1, hw_queues - 1)): the streams that execute passes at the same time (csrc/pipe_sched.h).  hw_queues <= 0: the
  * value of GPU_MAX_HW_QUEUES in the environment, 4 when it is not set. */
@@ -711,6 +717,64 @@ typedef struct cm3d_stage2_filter_desc {
  *
  * k_box_nms treats a negative position as "no box", so a dropped mask neither gets a box nor suppresses one. */
 int cm3d_lift_pass_filtered(const cm3d_lift_pass_desc *desc, const cm3d_stage2_filter_desc *filter, cm3d_stream_t stream);
+
+/* ---- Depth clustering of every mask's in-mask list, and the clustered pass (opt-in) ----
+ * Added within ABI v5: new symbols only, no existing call changes, so CM3D_ABI_VERSION stays.
+ * Stands where the reference's clusters_hdbscan stood (src/kitti/2d_to_3d.py:159-174, src/waymo/2d_to_3d.py:102-117; its only call
+ * site is commented out): background points inside a mask -- seen through windows, leaked in at the mask's edge -- are dropped before
+ * the medoid and the box fit see the list.  It is a 1-D gap clustering on the range from the sensor rig, exact and independent of the
+ * order of processing; host statement: cm3d_amd.cluster.depth_cluster_host.
+ *
+ * Per mask m: its list is positions hit_off[m] .. hit_off[m+1] of hit_xyz (and hit_idx), its origin o = origin[mask_frame[m]].
+ *   key      float64, no contraction: dx = (double)x - ox, dy, dz alike; r = sqrt((dx*dx + dy*dy) + dz*dz)
+ *   clusters the positions sorted by (r, position); a boundary lies between sorted neighbours iff r[k+1] - r[k] > eps (strict,
+ *            float64) -- the connected components of |ri - rj| <= eps
+ *   choice   a cluster qualifies iff it has >= min_points points.  pick 0 (largest): the qualifying cluster of most points, the
+ *            nearer one (smaller first range) on a tie; pick 1 (nearest): the first qualifying cluster in range order
+ *   result   cl_status[m] = 0: the chosen cluster's points, in the list's own (ascending) order; 1: no cluster qualifies, the list is
+ *            kept whole (the reference's `return None`, :168-171); 2: empty list, empty result.  A non-empty list never becomes empty.
+ *  hit_xyz    float[idx_cap][4]; hit_idx int32[idx_cap] or NULL; hit_off int32[n_masks+1]; mask_frame int32[n_masks]
+ *  origin     double[n_frames][3] (a frame number outside [0, n_frames) reads as the origin 0, 0, 0)
+ *  eps > 0 (+inf: one cluster), min_points >= 1, pick 0 or 1: anything else, NaN included, is CM3D_ERR_ARG and no launch
+ *  cl_off      int32[n_masks+1] OUT exclusive scan of the kept counts
+ *  cl_tile_off int32[n_masks+1] OUT exclusive scan of ceil(kept count / CM3D_MEDOID_TILE)
+ *  cl_idx      int32[idx_cap] OUT (NULL exactly when hit_idx is), cl_xyz float[idx_cap][4] OUT: the kept entries, laid out by cl_off
+ *  cl_status   int32[n_masks] OUT
+ *  workspace: cm3d_depth_cluster_workspace_bytes(n_masks, idx_cap) = 13 idx_cap + 4 n_masks bytes, 8-byte aligned (sort keys and
+ *             positions of the lists too long for LDS, placed by the offsets; one keep byte per position; the kept counts)
+ * Three launches, no synchronisation, no allocation: one workgroup per mask sorts (in LDS up to CM3D_DEPTH_CLUSTER_LDS_POINTS points,
+ * in the workspace beyond: every length gives the statement's answer), finds the clusters and marks the kept positions; one
+ * workgroup scans the counts; one workgroup per mask compacts.  An offset outside [0, idx_cap] is clamped into it and a list end below
+ * its start is an empty list: no position >= idx_cap is read or written whatever hit_off holds. */
+int64_t cm3d_depth_cluster_workspace_bytes(int32_t n_masks, int32_t idx_cap);
+int cm3d_depth_cluster(const float *hit_xyz, const int32_t *hit_idx, const int32_t *hit_off, const int32_t *mask_frame, int32_t n_masks,
+                       int32_t idx_cap, const double *origin, int32_t n_frames, double eps, int32_t min_points, int32_t pick,
+                       int32_t *cl_off, int32_t *cl_tile_off, int32_t *cl_idx, float *cl_xyz, int32_t *cl_status, void *workspace,
+                       int64_t workspace_bytes, cm3d_stream_t stream);
+
+/* What the clustered pass needs beyond cm3d_lift_pass_desc.  `size` is sizeof(cm3d_depth_cluster_desc) (another value: CM3D_ERR_ARG);
+ * the other fields as in cm3d_depth_cluster (origin: double[desc->n_frames][3]). */
+typedef struct cm3d_depth_cluster_desc {
+    int64_t size;
+    const double *origin;
+    int32_t *cl_off; int32_t *cl_tile_off; int32_t *cl_idx; float *cl_xyz; int32_t *cl_status;
+    void *ws; int64_t ws_bytes;
+    void *ev[2];                 /* optional hipEvent_t, recorded in front of and behind the clustering's launches */
+    double eps;
+    int32_t min_points, pick;
+} cm3d_depth_cluster_desc;
+
+/* The opt-in clustered pass (host code, csrc/pass_cluster.cpp; cm3d_lift_pass and cm3d_pipe_submit know nothing of it).  Enqueues on
+ * `stream`, stopping at and returning the first error; a wrong `size` or a null output: CM3D_ERR_ARG and no call:
+ *
+ *   cm3d_lift_pass_head(desc)             through the compaction: hit_off, tile_off, hit_idx, hit_xyz
+ *   record cluster->ev[0]
+ *   cm3d_depth_cluster                    desc's lists -> cl_off, cl_tile_off, cl_idx, cl_xyz, cl_status
+ *   record cluster->ev[1]
+ *   cm3d_lift_pass_tail(desc')            desc' = desc with hit_off, tile_off, hit_idx, hit_xyz = the cl_* arrays and tile_work = NULL
+ *
+ * so the medoid, colsum and cm3d_obb see the clustered lists and medoid_pos is a position in them; the raw lists stay what they were. */
+int cm3d_lift_pass_clustered(const cm3d_lift_pass_desc *desc, const cm3d_depth_cluster_desc *cluster, cm3d_stream_t stream);
 
 #ifdef __cplusplus
 }
