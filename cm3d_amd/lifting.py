@@ -24,6 +24,7 @@ from . import rle as rlemod
 from ._lib import Cm3dError, check
 from .drivable import Stage2Filters  # noqa: F401  (LiftEngine(filters=Stage2Filters(...)))
 from .cluster import DepthCluster  # noqa: F401  (LiftEngine(cluster=DepthCluster(...)))
+from .nms import RotatedNms  # noqa: F401  (LiftEngine(nms=RotatedNms(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -424,7 +425,7 @@ class LiftEngine:
 
     def __init__(self, device="cuda:0", classes: Optional[ClassTable] = None, min_dist=MIN_DIST,
                  hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
-                 cluster: Optional[DepthCluster] = None):
+                 cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -439,7 +440,11 @@ class LiftEngine:
         the frames' origins, the rest of the pass on the clustered lists -- so that `medoid_pos` is a position in the clustered list
         (`cl_off`), and the OBB fit sees those lists too; download() adds `cl_off`, `cl_status` (full=True: `cl_idx`, `cl_xyz`), while
         `hit_off` / `hit_idx` / `hit_xyz` stay the raw lists.  With filters also on, the filter and the second box launch follow
-        through their own calls.  None: nothing changes, neither a buffer nor a launch."""
+        through their own calls.  None: nothing changes, neither a buffer nor a launch.
+        nms: the opt-in rotated-box NMS (nms.RotatedNms; the reference's rotated-rectangle nms is dead code).  `run` then enqueues
+        cm3d_box_rotated_nms as the last launch of whichever pass it is: bit 1 of `flags` and column 9 of `box` are decided again by the
+        bird's-eye-view overlap of the boxes the pass wrote, everything else stays what the pass wrote.  None: nothing changes, neither
+        a buffer nor a launch."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -453,6 +458,7 @@ class LiftEngine:
         self.obb = bool(obb)
         self.filters = filters if filters is not None and filters.active else None
         self.cluster = cluster if cluster is not None and cluster.active else None
+        self.nms = nms if nms is not None and nms.active else None
         _verify_matrix_pipe(self.lib, self.dev)
         self.b = None
         self._lane = None                                    # the lane tables on the device and their spatial index (upload)
@@ -470,6 +476,7 @@ class LiftEngine:
         self.nms_thr = torch.from_numpy(self.classes.nms_thr).to(d)
         self.nms_group = torch.from_numpy(np.ascontiguousarray(self.classes.nms_group, np.int32)).to(d)
         self.needs_road = torch.from_numpy(np.ascontiguousarray(self.classes.needs_road, np.int32)).to(d) if self.filters else None
+        self.rot_thr = torch.from_numpy(self.nms.thr_by_group(self.classes)).to(d) if self.nms else None
 
     # -- upload + allocation
     def upload(self, hb: HostBatch, dense_masks: Optional[torch.Tensor] = None):
@@ -902,6 +909,14 @@ class LiftEngine:
                                             min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), _ptr(b.box), _ptr(b.flags), st),
               "cm3d_box_nms_bounded")
 
+    def stage_rotated_nms(self, st):
+        """The opt-in rotated-box NMS on the box rows and flags the pass's (last) box launch wrote (cm3d_box_rotated_nms)."""
+        b = self.b
+        check(self.lib.cm3d_box_rotated_nms(_ptr(b.box), _ptr(b.flags), _ptr(b.mask_off), b.F, b.M, _ptr(b.class_id), _ptr(self.prior_wlh),
+                                            _ptr(self.nms_group), len(self.classes.names), _ptr(self.rot_thr), self.rot_thr.numel(),
+                                            self.nms.measure_index, int(self.nms.class_agnostic), int(b.pose_inv is not None),
+                                            min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), st), "cm3d_box_rotated_nms")
+
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
     def run(self, masks="dense", project_events=None, stage_events=None):
@@ -911,7 +926,8 @@ class LiftEngine:
         the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them.
         An engine with filters appends two more, around the filter launch (the "drivable" bucket), and enqueues the filtered pass.
         An engine with a depth clustering appends two more after those, around the clustering's launches (the "cluster" bucket; they
-        lie between the second and the third of the five), and enqueues the clustered pass."""
+        lie between the second and the third of the five), and enqueues the clustered pass.
+        An engine with a rotated-box NMS enqueues its launch last, behind the fifth event; no allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
             self.start_lane_grid()
@@ -933,13 +949,14 @@ class LiftEngine:
                   "cm3d_lift_pass_clustered")
             if self.filters is not None:             # the filter and the boxes again, on what the clustered pass left: the existing calls
                 self.stage_filter(st, fmarks)
-            return
-        if self.filters is not None:
+        elif self.filters is not None:
             self.b.filter_desc.ev[:] = self._raw_events(fmarks, 2)
             check(self.lib.cm3d_lift_pass_filtered(self.refresh_pass_descriptor(dense, project_events, marks), self.b.filter_desc_ref, st),
                   "cm3d_lift_pass_filtered")
-            return
-        check(self.lib.cm3d_lift_pass(self.refresh_pass_descriptor(dense, project_events, marks), st), "cm3d_lift_pass")
+        else:
+            check(self.lib.cm3d_lift_pass(self.refresh_pass_descriptor(dense, project_events, marks), st), "cm3d_lift_pass")
+        if self.nms is not None:                     # behind the pass's last box launch, whichever pass it was
+            self.stage_rotated_nms(st)
 
     def capture_graph(self, masks="rle"):
         """Captures one pass over the resident batch into a HIP graph and returns it (`g.replay()` re-runs the pass
@@ -1163,13 +1180,13 @@ class LiftPipeline:
         eng = self.engines[slot]
         mode = masks or self.masks[slot]
         self._pin_if_captured()
-        if eng._lane["built"] and eng.filters is None and eng.cluster is None:           # (cm3d_pipe_submit knows only the plain pass)
+        if eng._lane["built"] and eng.filters is None and eng.cluster is None and eng.nms is None:     # (cm3d_pipe_submit knows only the plain pass)
             # (no stream context, no Python between the launches: what bench.py's headline times.  A pair of events around the
             # projection kernel rides along, so that a timed pass costs the host what an untimed one does)
             rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor(eng.resident_masks(mode), project_events))
             if rc < 0:
                 check(rc, "cm3d_pipe_submit")
-        else:                                # the pass has to start the build of the lane index first, or is the filtered or clustered one: Python's to do
+        else:                                # the pass has to start the build of the lane index first, or is not the plain one (filters, clustering, rotated NMS): Python's to do
             st = self.streams[self._acquire(slot)]
             try:
                 with torch.cuda.stream(st):

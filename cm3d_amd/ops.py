@@ -6,6 +6,7 @@ src/nuscenes/2d_to_3d.py so that parity tests read like calls into the reference
     lane_yaws_distances_and_coords(centroids, lane_pts)  :277-302
     push_centroid(centroid, extents, yaw, poserecord)    :164-198 (+ the rotation of :788-806)
     circle_nms(dets, det_labels, threshs_by_label)       :309-332
+    rotated_nms(rec, score, group, frame_off, thr, ...)  the opt-in NMS on the boxes' bird's-eye-view overlap (nms.rotated_nms_host)
     points_in_masks(points, cams, masks, cam_nums)       :553-620 for all masks of a frame
     erode(mask) / decode(rles)                           :526-527 / :425
     obb_yaws(point_lists)                                src/kitti/2d_to_3d.py:855-876 + :1524 for several lists
@@ -408,6 +409,25 @@ def circle_nms(dets, det_labels, threshs_by_label):
     check(L.cm3d_circle_nms(x.data_ptr(), y.data_ptr(), sc.data_ptr(), lab.data_ptr(), off.data_ptr(), 1, thr.data_ptr(),
                             len(names), keep.data_ptr(), _st()), "cm3d_circle_nms")
     return np.flatnonzero(keep.cpu().numpy()).tolist()
+
+
+def rotated_nms(rec, score, group, frame_off, thr, measure="iou", class_agnostic=False):
+    """The opt-in rotated-box NMS on records (cm3d_rotated_nms; nms.rotated_nms_host states it): rec (n, 6) cx, cy, length, width,
+    c, s; score (n,); group (n,) NMS group of each box; frame_off (F + 1,); thr: one float or one per group.  Returns keep (n,) int32."""
+    from . import nms as nmsmod
+    L = _lib.lib()
+    rec = np.asarray(rec, np.float64).reshape(-1, 6)
+    n = rec.shape[0]
+    off = np.asarray(frame_off, np.int32).reshape(-1)
+    thr = np.atleast_1d(np.asarray(thr, np.float64))
+    if n == 0 or off.size < 2:
+        return np.zeros(n, np.int32)
+    d_rec, d_sc, d_grp = _t(rec), _t(np.asarray(score, np.float64).reshape(n)), _t(np.asarray(group, np.int32).reshape(n))
+    d_off, d_thr = _t(off), _t(thr)
+    keep = _e(n)
+    check(L.cm3d_rotated_nms(d_rec.data_ptr(), d_sc.data_ptr(), d_grp.data_ptr(), d_off.data_ptr(), off.size - 1, d_thr.data_ptr(),
+                             thr.size, nmsmod.measure_code(measure), int(bool(class_agnostic)), keep.data_ptr(), _st()), "cm3d_rotated_nms")
+    return keep.cpu().numpy()
 
 
 # ----------------------------------------------------------------------------- f4: SAM3D fusion matching

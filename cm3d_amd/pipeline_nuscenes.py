@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from . import cluster as clmod
+from . import nms as nmsmod
 from . import dist as cdist
 from . import lifting, nusc_io
 
@@ -219,15 +220,16 @@ def _token_batches(batches, index, host_s):
         host_s = 0.0
 
 
-def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None):
+def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
     on_records(records of one batch as numpy, first output index, number of samples): called per finished batch whose samples are a
     contiguous run of the output order, with (None, 0, 0) otherwise.  filters: the opt-in stage-2 filters (lifting.Stage2Filters); the
     time of their launch goes into the reference's "drivable" bucket.  cluster: the opt-in depth clustering (cluster.DepthCluster); its
-    launches lie between the compaction's event and the medoid's, and their time goes into a "cluster" bucket instead of "medoid"."""
-    pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster)
+    launches lie between the compaction's event and the medoid's, and their time goes into a "cluster" bucket instead of "medoid".
+    nms: the opt-in rotated-box NMS (nms.RotatedNms); its launch lies behind the last event."""
+    pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms)
     n_evs = 5 + (2 if filters is not None and filters.active else 0) + (2 if cluster is not None else 0)
     records, pending, segments = [], [], []                            # pending: (slot, frame ids, stage events) in flight, oldest first
 
@@ -285,7 +287,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
 
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                 scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None,
-                cluster=None):
+                cluster=None, nms=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -318,7 +320,7 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
                 pool.terminate()
                 pool.join()
     with contextlib.closing(prepared()) as batches:
-        return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster)
+        return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -393,7 +395,7 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
 
 
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
-                       scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None):
+                       scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -436,7 +438,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 hb, rows = got
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
-        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster)
+        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -468,8 +470,10 @@ def main(argv=None):
     ap.add_argument("--vehicle-lane-max-dist", type=float, default=None, metavar="M",
                     help="the same for the pushed (vehicle) classes (the reference's commented value: 4)")
     clmod.add_arguments(ap)
+    nmsmod.add_arguments(ap)
     args = ap.parse_args(argv)
     cluster = clmod.from_namespace(args)
+    nms = nmsmod.from_args(args)
     filters = lifting.Stage2Filters.from_args(args.drivable_filter, args.lane_max_dist, args.vehicle_lane_max_dist)
 
     total_start = time.time()
@@ -543,7 +547,7 @@ def main(argv=None):
             write_q.put((rec_np, first, count))
         mine = lift_scenes_native(nt, names[lo:hi], args.mask_dir, classes, device, row_to_out, args.n_sweeps, args.ratio, args.masks, timer,
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
-                                  on_records=on_records if world == 1 else None, filters=filters, cluster=cluster)
+                                  on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
@@ -551,7 +555,7 @@ def main(argv=None):
         tokens = sample_tokens(tables, names)                  # the whole job's samples, identical on every rank
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
-                           token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster)
+                           token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.

@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import cluster as clmod
+from . import nms as nmsmod
 from . import dist as cdist
 from . import lifting
 from . import waymo as wm
@@ -126,6 +127,7 @@ def main(argv=None):
     ap.add_argument("--vehicle-lane-max-dist", type=float, default=None, metavar="M",
                     help="the same for the pushed (vehicle) classes (the reference's commented value: 4)")
     clmod.add_arguments(ap)
+    nmsmod.add_arguments(ap)
     args = ap.parse_args(argv)
     filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
@@ -137,7 +139,8 @@ def main(argv=None):
     scenes = [s for s in args.scenes.split(",") if s] or sorted(os.listdir(args.tfrecords if use_tf else args.frames_dir))
     pri = json.load(open(args.priors)) if os.path.exists(args.priors) else None
     classes = lifting.ClassTable.waymo(pri)
-    eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args))
+    eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args),
+                             nms=nmsmod.from_args(args))
     lo, hi = cdist.shard_range(len(scenes), rank, world)
     mine, meta = [], {}
     for si in range(lo, hi):

@@ -388,6 +388,38 @@ int cm3d_circle_nms(const double *x, const double *y, const double *score, const
                     const int32_t *frame_off, int32_t n_frames, const double *nms_thr, int32_t n_classes,
                     int32_t *keep, cm3d_stream_t stream);
 
+/* ---- opt-in: greedy NMS on the bird's-eye-view overlap of the rotated boxes (added within ABI v5) ----------------
+ * In place of circle_nms's centre distance: the rotated-rectangle nms(rrects, scores, ...) the reference carries as dead code
+ * (src/kitti/2d_to_3d.py:359-599; strict > at :596, nms_threshold 0.4 at :531-534), with the float64 clip of cm3d_bev_match as the
+ * overlap instead of its rasterised polygons.  cm3d_amd/nms.py (rotated_nms_host) states the rule to the bit:
+ *  order: descending score, ties by descending index; the box of rank r, unless suppressed, is kept and suppresses every
+ *  later-ranked, not yet suppressed box j with (class_agnostic || group[j] == group[i]) and measure(i, j) > thr[group[j]].
+ *  measure 0 "iou":   the bird's-eye-view IoU of cm3d_bev_match (0 when either area is not positive, at most 1);
+ *  measure 1 "cover": intersection area / (length_j * width_j), at most 1: the share of the lower-scored box the kept one covers
+ *        (the reference's ratio).  In both the kept box is the one the clip's coordinates are relative to.
+ *  A box whose float64 area is not positive or whose centre is not finite neither suppresses nor is suppressed.  Scores are finite.
+ *  rec   double[n][6]  cx, cy, length, width, cos(heading), sin(heading) -- the record of cm3d_bev_match
+ *  group int32[n] NMS group of each box (outside [0, n_groups): 0); thr double[n_groups]
+ *  frame_off int32[F+1]: boxes [frame_off[f], frame_off[f+1]) form one frame (an empty frame is legal); the boxes of a frame beyond
+ *        its CM3D_MAX_MASKS_PER_FRAME-th get keep 0
+ *  keep  int32[n] OUT, written whole: 1 for the survivors */
+int cm3d_rotated_nms(const double *rec, const double *score, const int32_t *group, const int32_t *frame_off, int32_t n_frames,
+                     const double *thr, int32_t n_groups, int32_t measure, int32_t class_agnostic, int32_t *keep,
+                     cm3d_stream_t stream);
+/* The same behind the box launch of a pass (cm3d_box_nms / cm3d_box_nms_bounded), on the `box` rows and `flags` it wrote: only boxes with
+ * flags & 1 take part; bit 1 of `flags` and column 9 of `box` are rewritten for EVERY mask of the batch (nothing of the circle NMS's
+ * decision remains), nothing else is touched.  The record of a box is built from stored values only: cx, cy = box[0], box[1];
+ * class = box[8] (what the box launch stored of class_id, which is only checked here); length = prior_wlh[3 * class + 1],
+ * width = prior_wlh[3 * class + 0] (the [w, l, h] table: length along the heading); nuScenes (waymo == 0): the axis of the rotation
+ * [qw, 0, 0, qz], c = qw * qw - qz * qz, s = 2 * qw * qz, every product and the difference rounded on their own (a box of a class
+ * that is not rotated is the axis-aligned rectangle its record describes); Waymo (waymo != 0): c, s = cos, sin of box[3] in
+ * float64.  group = nms_group[class], score = box[7].  max_masks_per_frame as in cm3d_box_nms_bounded: the launch's LDS is sized
+ * by it (none up to 64), and the masks of a frame beyond it -- which that launch gave flags 0 -- take no part. */
+int cm3d_box_rotated_nms(double *box, int32_t *flags, const int32_t *mask_off, int32_t n_frames, int32_t n_masks,
+                         const int32_t *class_id, const double *prior_wlh, const int32_t *nms_group, int32_t n_classes,
+                         const double *thr, int32_t n_groups, int32_t measure, int32_t class_agnostic, int32_t waymo,
+                         int32_t max_masks_per_frame, cm3d_stream_t stream);
+
 /* ---- f4: box matching of the SAM3D fusion step ------------------------------------
  * Replaces `match(pred_boxes, sam3d_boxes, 0.2, Type.TYPE_2D)` of src/nuscenes/linear_matching.py:53-121,
  * called per sample at :231-259 (src/waymo/linear_matching.py:251-283 alike): waymo_open_dataset's
