@@ -200,7 +200,7 @@ def _host_clustered(hb, A, c):
 
 
 @pytest.mark.parametrize("pick", cluster.PICKS)
-def test_clustered_pass(batch, pick):
+def test_clustered_pass(oracle, batch, pick):
     import torch
     from cm3d_amd import lifting, ops
     frames, lanes, hb, A = batch
@@ -221,8 +221,9 @@ def test_clustered_pass(batch, pick):
     # the medoid of the clustered lists
     off = exp["cl_off"]
     lists = [exp["cl_xyz"][off[m]:off[m + 1], :3] for m in range(hb.n_masks)]
-    med = np.array(ops.get_medoids(lists), np.int32)
+    med = np.array([oracle.medoid(exp["cl_xyz"], np.arange(off[m], off[m + 1], dtype=np.int32)) for m in range(hb.n_masks)], np.int32)      # (-1: empty)
     assert np.array_equal(B["medoid_pos"], med)
+    assert np.array_equal(np.array(ops.get_medoids(lists), np.int32), med)           # the stand-alone call agrees
     cen = np.array([lists[m][med[m]] if med[m] >= 0 else np.zeros(3, np.float32) for m in range(hb.n_masks)], np.float32)
     assert B["centroid"].tobytes() == cen.tobytes()
     assert (B["medoid_pos"] >= 0).tolist() == (A["medoid_pos"] >= 0).tolist()       # the set of masks with a box does not change
@@ -291,7 +292,7 @@ def test_filters_and_clustering_together(batch):
     assert np.array_equal(both["box"][kept >= 0, 0:9], only["box"][kept >= 0, 0:9])
 
 
-def test_kitti_entry_point_with_depth_clustering(tmp_path):
+def test_kitti_entry_point_with_depth_clustering(tmp_path, oracle):
     """src/kitti/2d_to_3d.py --depth-cluster 1 --obb device on one small frame: the labels' yaw is cm3d_obb of the clustered lists,
     their centre the clustered lists' medoid."""
     from cm3d_amd import kitti as kt, lifting, ops, synthetic as syn
@@ -322,7 +323,8 @@ def test_kitti_entry_point_with_depth_clustering(tmp_path):
     off = exp["cl_off"]
     lists = [exp["cl_xyz"][off[m]:off[m + 1], :3] for m in range(hb.n_masks)]
     yaw, st, _ = ops.obb_yaws(lists)
-    med = ops.get_medoids(lists)
+    med = [oracle.medoid(exp["cl_xyz"], np.arange(off[m], off[m + 1], dtype=np.int32)) for m in range(hb.n_masks)]
+    assert list(ops.get_medoids(lists)) == med
     cen = np.array([lists[m][med[m]] if med[m] >= 0 else np.zeros(3, np.float32) for m in range(hb.n_masks)], np.float32)
     res = dict(cl_off=off, cl_xyz=exp["cl_xyz"], hit_off=A["hit_off"], centroid=cen, obb_yaw=yaw, obb_status=st)
     pred, pseudo = kt.labels_of_frame(hb, res, 0, classes, pri, obb="device")

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests import drivable_cases as dc
+from tests.optin_pass_cases import expected_filtered         # the host restatement of the filtered pass (moved there: the composed expectation uses it)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -123,40 +124,9 @@ def build_scenario(run_plain):
     return frames, lanes, frame_lane, tables, hb, res, pairs
 
 
-def expected_filtered(orc, hb, plain, lanes, frame_lane, frames, tables, filters):
-    """The host restatement: on_road by the host test on the plain pass's medoids, medoid_pos_kept by the rule, box / flags by the
-    oracle's stage 2 with med = -1 for the dropped masks (tests/helpers.oracle_batch's record layout)."""
-    from cm3d_amd import drivable
-    from cm3d_amd.lifting import ClassTable
-    cls = ClassTable.nuscenes()
-    has = plain["medoid_pos"] >= 0
-    cg = plain["centroid"]
-    on_road = None
-    if filters.drivable:
-        on_road = drivable.points_on_road(tables, cg[:, :2].astype(np.float64), np.asarray(frame_lane)[hb.mask_frame]) * has.astype(np.uint8)
-    kept = drivable.filter_rule(plain["medoid_pos"], hb.class_id, plain["lane_dist"], on_road, cls.is_vehicle, cls.needs_road,
-                                filters.lane_max_dist, filters.vehicle_lane_max_dist)
-    box, flags = [], []
-    for fi, fr in enumerate(frames):
-        m0, m1 = int(hb.mask_off[fi]), int(hb.mask_off[fi + 1])
-        s2 = orc.stage2_frame(cg[m0:m1], kept[m0:m1], hb.class_id[m0:m1], hb.score[m0:m1], lanes[frame_lane[fi]], fr.ego_xyz)
-        b = np.zeros((m1 - m0, 10))
-        b[:, 0:3] = np.where(s2["valid"][:, None], s2["translation"], 0.0)
-        b[:, 3] = np.where(s2["valid"], s2["rotation"][:, 0], 1.0)
-        b[:, 4] = np.where(s2["valid"], s2["rotation"][:, 3], 0.0)
-        b[:, 5] = s2["yaw"]
-        b[:, 6] = np.where(s2["valid"], s2["lane_dist"], 0.0)
-        b[:, 7], b[:, 8] = hb.score[m0:m1], hb.class_id[m0:m1]
-        b[:, 9] = s2["valid"].astype(np.int32) | (s2["keep"].astype(np.int32) << 1)
-        box.append(b)
-        flags.append(b[:, 9].astype(np.int32))
-    return dict(on_road=on_road if on_road is not None else np.zeros(hb.n_masks, np.uint8), medoid_pos_kept=kept,
-                box=np.concatenate(box, 0), flags=np.concatenate(flags))
-
-
 def check_scenario(hb, plain, pairs, exp):
-    """The scenario holds what the test is about (also run on the host against the oracle alone, tests/test_drivable_host.py's
-    sibling check below)."""
+    """The scenario holds what the test is about (also run on the host against the oracle alone:
+    tests/test_optin_pass_cases_host.py)."""
     from cm3d_amd.lifting import ClassTable
     names = ClassTable.nuscenes().names
     n_per = np.diff(hb.mask_off)

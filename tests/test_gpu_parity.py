@@ -45,7 +45,8 @@ def _expected_hit_xyz(hb, exp):
     return exp["points"][base + exp["hit_idx"]]
 
 
-def _compare(hb, got, exp):
+def _compare_raw(hb, got, exp):
+    """What a pass produces in front of the medoid: the cloud's offsets (and the cloud), the masks' bounds, the raw in-mask lists."""
     assert np.array_equal(got["pt_off"], exp["pt_off"])
     if "points" in got:
         assert np.array_equal(got["points"].view(np.uint32), exp["points"].view(np.uint32)), "sweep prep not bit-exact"
@@ -53,16 +54,24 @@ def _compare(hb, got, exp):
     assert np.array_equal(got["hit_off"], exp["hit_off"])
     assert np.array_equal(got["hit_idx"], exp["hit_idx"]), "point-to-mask index lists differ"
     assert np.array_equal(got["hit_xyz"].view(np.uint32), _expected_hit_xyz(hb, exp).view(np.uint32)), "in-mask coordinates not bit-exact"
+
+
+def _compare_box(got, exp):
+    assert np.allclose(got["box"], exp["box"], rtol=0, atol=BOX_TOL)
+    # what we actually see: ~1e-9, up to 1.2e-6 where push_centroid's 1/sin, 1/cos amplify the one-ulp difference between the
+    # device's and the host's float32 cos/sin of the lane yaw (1000-shape campaign)
+    assert np.abs(got["box"] - exp["box"]).max() < 1e-5
+
+
+def _compare(hb, got, exp):
+    _compare_raw(hb, got, exp)
     assert np.array_equal(got["medoid_pos"], exp["medoid_pos"])
     assert np.array_equal(got["centroid"].view(np.uint32), exp["centroid"].view(np.uint32))
     assert np.array_equal(got["lane_idx"], exp["lane_idx"])
     valid = exp["medoid_pos"] >= 0
     assert np.array_equal(got["lane_dist"][valid], exp["lane_dist"][valid])
     assert np.array_equal(got["flags"], exp["flags"])
-    assert np.allclose(got["box"], exp["box"], rtol=0, atol=BOX_TOL)
-    # what we actually see: ~1e-9, up to 1.2e-6 where push_centroid's 1/sin, 1/cos amplify the one-ulp difference between the
-    # device's and the host's float32 cos/sin of the lane yaw (1000-shape campaign)
-    assert np.abs(got["box"] - exp["box"]).max() < 1e-5
+    _compare_box(got, exp)
 
 
 @pytest.mark.parametrize("masks", ["dense", "rle"])
