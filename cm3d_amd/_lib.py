@@ -31,7 +31,8 @@ NUSC_MAX_GT = 256        # ground-truth boxes of one group
 NUSC_MAX_TH = 4
 NUSC_MAX_ALPHAS = 1024   # alphas of one cm3d_nusc_match call
 DEPTH_CLUSTER_LDS_POINTS = 4096   # longest list cm3d_depth_cluster sorts in LDS
-RAW_QUADS = 3            # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
+BEV_FIT_CHUNK = 512      # points of a list cm3d_bev_fit stages in LDS at a time
+RAW_QUADS = 3           # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -107,6 +108,10 @@ SIGNATURES = {
     "cm3d_depth_cluster_workspace_bytes": (_i64, [_i32, _i32]),
     "cm3d_depth_cluster": (_i32, [_p, _p, _p, _p, _i32, _i32, _p, _i32, C.c_double, _i32, _i32, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "cm3d_lift_pass_clustered": (_i32, [_p, _p, _p]),
+    "cm3d_bev_fit": (_i32, [_p, _p, _i32, _i32, _p, _i32, C.c_double, _i32, C.c_double, _p, _p, _p, _p]),
+    "cm3d_yaw_select": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _p, C.c_double, _p, _p, _p, _p, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
+    "cm3d_yaw_fit_boxes": (_i32, [_p, _p, _p]),
+    "cm3d_lift_pass_yaw_fitted": (_i32, [_p, _p, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order
@@ -144,6 +149,14 @@ class DepthClusterDesc(C.Structure):
     """cm3d_depth_cluster_desc of include/cm3d_hip.h, field for field."""
     _fields_ = ([("size", _i64)] + [(n, _p) for n in ("origin", "cl_off", "cl_tile_off", "cl_idx", "cl_xyz", "cl_status", "ws")]
                 + [("ws_bytes", _i64), ("ev", _p * 2), ("eps", C.c_double), ("min_points", _i32), ("pick", _i32)])
+
+
+class YawFitDesc(C.Structure):
+    """cm3d_yaw_fit_desc of include/cm3d_hip.h, field for field."""
+    _fields_ = ([("size", _i64)] + [(n, _p) for n in ("angle_cs", "hit_xyz", "hit_off", "medoid_pos", "fit_k", "fit_rect", "fit_status",
+                                                      "yaw_tab", "yaw_idx", "yaw_src", "tab_off", "tab_frame")]
+                + [("ev", _p * 2), ("d0", C.c_double), ("min_length", C.c_double), ("lane_min_dist", C.c_double), ("K", _i32),
+                   ("min_points", _i32)])
 
 
 class Cm3dError(RuntimeError):

@@ -24,6 +24,7 @@ from . import rle as rlemod
 from ._lib import Cm3dError, check
 from .drivable import Stage2Filters  # noqa: F401  (LiftEngine(filters=Stage2Filters(...)))
 from .cluster import DepthCluster  # noqa: F401  (LiftEngine(cluster=DepthCluster(...)))
+from .bevfit import YawFit, angle_table  # noqa: F401  (LiftEngine(yaw=YawFit(...)))
 from .nms import RotatedNms  # noqa: F401  (LiftEngine(nms=RotatedNms(...)))
 
 # ---- tables of the reference --------------------------------------------------
@@ -425,7 +426,7 @@ class LiftEngine:
 
     def __init__(self, device="cuda:0", classes: Optional[ClassTable] = None, min_dist=MIN_DIST,
                  hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
-                 cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None):
+                 cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -444,7 +445,12 @@ class LiftEngine:
         nms: the opt-in rotated-box NMS (nms.RotatedNms; the reference's rotated-rectangle nms is dead code).  `run` then enqueues
         cm3d_box_rotated_nms as the last launch of whichever pass it is: bit 1 of `flags` and column 9 of `box` are decided again by the
         bird's-eye-view overlap of the boxes the pass wrote, everything else stays what the pass wrote.  None: nothing changes, neither
-        a buffer nor a launch."""
+        a buffer nor a launch.
+        yaw: the opt-in yaw fit (bevfit.YawFit; nuScenes and Waymo batches -- KITTI's yaw comes from cm3d_obb).  `run` then enqueues
+        cm3d_lift_pass_yaw_fitted -- the plain pass, cm3d_bev_fit on the in-mask lists, cm3d_yaw_select, the box launch again with the
+        chosen yaws where the lane tables stood -- or, behind a clustered or filtered pass, cm3d_yaw_fit_boxes on the `cl_*` lists and
+        on `medoid_pos_kept`; the rotated NMS stays last.  download() adds `yaw_src`, `fit_status`, `fit_k` and `fit_rect`, and
+        column 5 of `box` holds the yaw that was used.  None: nothing changes, neither a buffer nor a launch."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -459,6 +465,7 @@ class LiftEngine:
         self.filters = filters if filters is not None and filters.active else None
         self.cluster = cluster if cluster is not None and cluster.active else None
         self.nms = nms if nms is not None and nms.active else None
+        self.yaw = yaw if yaw is not None and yaw.active else None
         _verify_matrix_pipe(self.lib, self.dev)
         self.b = None
         self._lane = None                                    # the lane tables on the device and their spatial index (upload)
@@ -477,6 +484,7 @@ class LiftEngine:
         self.nms_group = torch.from_numpy(np.ascontiguousarray(self.classes.nms_group, np.int32)).to(d)
         self.needs_road = torch.from_numpy(np.ascontiguousarray(self.classes.needs_road, np.int32)).to(d) if self.filters else None
         self.rot_thr = torch.from_numpy(self.nms.thr_by_group(self.classes)).to(d) if self.nms else None
+        self.angle_cs = torch.from_numpy(angle_table(self.yaw.angles)).to(d) if self.yaw else None
 
     # -- upload + allocation
     def upload(self, hb: HostBatch, dense_masks: Optional[torch.Tensor] = None):
@@ -586,6 +594,10 @@ class LiftEngine:
             b.cl_idx = e(b.idx_cap); b.cl_xyz = e(b.idx_cap, 4, dtype=torch.float32)
             b.cl_ws_bytes = int(L.cm3d_depth_cluster_workspace_bytes(M, b.idx_cap))
             b.cl_ws = torch.empty(max(b.cl_ws_bytes, 16), dtype=torch.uint8, device=d)
+        if self.yaw is not None:
+            b.fit_k = e(M); b.fit_status = e(M); b.fit_rect = e(M, _lib.MATCH_BOX_STRIDE, dtype=torch.float64)
+            b.yaw_tab = e(M, 3, dtype=torch.float32); b.yaw_idx = e(M); b.yaw_src = e(M)
+            b.yaw_tab_off = t(np.array([0, M], np.int32)); b.yaw_tab_frame = torch.zeros(F, dtype=torch.int32, device=d)
         b.dense = dense_masks
         # The bulk data LAST: sweeps and run lengths come from page-locked staging buffers (cm3d_amd.reader) and copy
         # asynchronously; the small arrays above are pageable, their copies block the host until everything queued before them on
@@ -602,6 +614,9 @@ class LiftEngine:
         if self.cluster is not None:
             b.cluster_desc = self._cluster_descriptor(b)
             b.cluster_desc_ref = ctypes.byref(b.cluster_desc)
+        if self.yaw is not None:
+            b.yaw_desc = self._yaw_descriptor(b)
+            b.yaw_desc_ref = ctypes.byref(b.yaw_desc)
         self.b = b
         return b
 
@@ -644,6 +659,23 @@ class LiftEngine:
         c.ws, c.ws_bytes = _ptr(b.cl_ws), b.cl_ws_bytes
         c.eps, c.min_points, c.pick = self.cluster.eps, self.cluster.min_points, self.cluster.pick_index
         return c
+
+    def _yaw_descriptor(self, b):
+        """cm3d_yaw_fit_desc of the resident batch (run sets its events).  The lists that are fitted are the clustered ones when the
+        engine clusters, the positions that decide about a box the kept ones when it filters."""
+        y = _lib.YawFitDesc()
+        y.size = ctypes.sizeof(_lib.YawFitDesc)
+        y.angle_cs = _ptr(self.angle_cs)
+        if self.cluster is not None:
+            y.hit_xyz, y.hit_off = _ptr(b.cl_xyz), _ptr(b.cl_off)
+        if self.filters is not None:
+            y.medoid_pos = _ptr(b.medoid_pos_kept)
+        for name in ("fit_k", "fit_rect", "fit_status", "yaw_tab", "yaw_idx", "yaw_src"):
+            setattr(y, name, _ptr(getattr(b, name)))
+        y.tab_off, y.tab_frame = _ptr(b.yaw_tab_off), _ptr(b.yaw_tab_frame)
+        y.K, y.min_points = self.yaw.angles, self.yaw.min_points
+        y.d0, y.min_length, y.lane_min_dist = self.yaw.d0, self.yaw.min_length, self.yaw.lane_min_dist
+        return y
 
     def _batch_descriptor(self, b):
         """cm3d_lift_pass_desc of the resident batch: the arguments of the calls a pass makes, name for name (the fields that belong to
@@ -909,6 +941,17 @@ class LiftEngine:
                                             min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), _ptr(b.box), _ptr(b.flags), st),
               "cm3d_box_nms_bounded")
 
+    def stage_yaw_fit(self, st):
+        """The yaw fit's three launches alone, on what the last pass left resident (cm3d_yaw_fit_boxes: cm3d_bev_fit, cm3d_yaw_select,
+        the box launch with the chosen yaws)."""
+        check(self.lib.cm3d_yaw_fit_boxes(self.b.desc_ref, self.b.yaw_desc_ref, st), "cm3d_yaw_fit_boxes")
+
+    def stage_bev_fit(self, st):
+        """cm3d_bev_fit alone, on the lists the yaw-fitted pass fits."""
+        b, y = self.b, self.b.yaw_desc
+        check(self.lib.cm3d_bev_fit(y.hit_xyz or _ptr(b.hit_xyz), y.hit_off or _ptr(b.hit_off), b.M, b.idx_cap, y.angle_cs, y.K, y.d0,
+                                    y.min_points, y.min_length, y.fit_k, y.fit_rect, y.fit_status, st), "cm3d_bev_fit")
+
     def stage_rotated_nms(self, st):
         """The opt-in rotated-box NMS on the box rows and flags the pass's (last) box launch wrote (cm3d_box_rotated_nms)."""
         b = self.b
@@ -927,6 +970,8 @@ class LiftEngine:
         An engine with filters appends two more, around the filter launch (the "drivable" bucket), and enqueues the filtered pass.
         An engine with a depth clustering appends two more after those, around the clustering's launches (the "cluster" bucket; they
         lie between the second and the third of the five), and enqueues the clustered pass.
+        An engine with a yaw fit appends two more after those, around the fit's two launches (the "yawfit" bucket; behind the fifth
+        event), and enqueues the yaw-fitted pass -- or, behind a clustered or filtered pass, the fit's three launches.
         An engine with a rotated-box NMS enqueues its launch last, behind the fifth event; no allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
@@ -936,10 +981,14 @@ class LiftEngine:
             marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
             stage_events.extend(marks)
         st = torch.cuda.current_stream(self.dev).cuda_stream
-        fmarks = cmarks = None
+        fmarks = cmarks = ymarks = None
         if self.filters is not None and stage_events is not None:
             fmarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
             stage_events.extend(fmarks)
+        if self.yaw is not None:
+            if stage_events is not None:
+                ymarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            self.b.yaw_desc.ev[:] = self._raw_events(ymarks, 2)
         if self.cluster is not None:
             if stage_events is not None:
                 cmarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -953,8 +1002,16 @@ class LiftEngine:
             self.b.filter_desc.ev[:] = self._raw_events(fmarks, 2)
             check(self.lib.cm3d_lift_pass_filtered(self.refresh_pass_descriptor(dense, project_events, marks), self.b.filter_desc_ref, st),
                   "cm3d_lift_pass_filtered")
+        elif self.yaw is not None:
+            check(self.lib.cm3d_lift_pass_yaw_fitted(self.refresh_pass_descriptor(dense, project_events, marks), self.b.yaw_desc_ref, st),
+                  "cm3d_lift_pass_yaw_fitted")
         else:
             check(self.lib.cm3d_lift_pass(self.refresh_pass_descriptor(dense, project_events, marks), st), "cm3d_lift_pass")
+        if self.yaw is not None:
+            if self.cluster is not None or self.filters is not None:      # behind the pass that is not the plain one: the three launches alone
+                self.stage_yaw_fit(st)
+            if ymarks is not None:
+                stage_events.extend(ymarks)
         if self.nms is not None:                     # behind the pass's last box launch, whichever pass it was
             self.stage_rotated_nms(st)
 
@@ -1042,6 +1099,8 @@ class LiftEngine:
                 out.update(obb_yaw=b.obb_yaw.cpu().numpy(), obb_status=b.obb_status.cpu().numpy())
             if self.cluster is not None:
                 out.update(cl_off=b.cl_off.cpu().numpy(), cl_status=b.cl_status.cpu().numpy())
+            if self.yaw is not None:
+                out.update(self._yaw_results())
             return out
         n_rows, n_idx = int(s[1]), int(s[2])
         pt_off_rows = b.pt_off.cpu().numpy()
@@ -1071,7 +1130,14 @@ class LiftEngine:
             n_cl = int(cl_off[-1])
             out.update(cl_off=cl_off, cl_status=b.cl_status.cpu().numpy(), cl_idx=b.cl_idx[:n_cl].cpu().numpy(),
                        cl_xyz=b.cl_xyz[:n_cl].cpu().numpy())
+        if self.yaw is not None:
+            out.update(self._yaw_results())
         return out
+
+    def _yaw_results(self):
+        b = self.b
+        return dict(yaw_src=b.yaw_src.cpu().numpy(), fit_status=b.fit_status.cpu().numpy(), fit_k=b.fit_k.cpu().numpy(),
+                    fit_rect=b.fit_rect.cpu().numpy())
 
 
 class LiftPipeline:
@@ -1180,7 +1246,7 @@ class LiftPipeline:
         eng = self.engines[slot]
         mode = masks or self.masks[slot]
         self._pin_if_captured()
-        if eng._lane["built"] and eng.filters is None and eng.cluster is None and eng.nms is None:     # (cm3d_pipe_submit knows only the plain pass)
+        if eng._lane["built"] and eng.filters is None and eng.cluster is None and eng.nms is None and eng.yaw is None:     # (cm3d_pipe_submit knows only the plain pass)
             # (no stream context, no Python between the launches: what bench.py's headline times.  A pair of events around the
             # projection kernel rides along, so that a timed pass costs the host what an untimed one does)
             rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor(eng.resident_masks(mode), project_events))

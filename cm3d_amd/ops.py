@@ -12,6 +12,7 @@ src/nuscenes/2d_to_3d.py so that parity tests read like calls into the reference
     obb_yaws(point_lists)                                src/kitti/2d_to_3d.py:855-876 + :1524 for several lists
     points_in_polygons(polygon_tables, xy, table)        eval_custom.py:514-519 for many points
     depth_cluster(point_lists, origins, eps, ...)        the opt-in depth clustering of several lists (cluster.depth_cluster_host)
+    bev_fit(xyz, off, ...) / yaw_select(...)             the opt-in yaw fit of several lists and the choice of each mask's yaw (bevfit.*_host)
 
 They are conveniences for tests and small jobs; the batched path is lifting.LiftEngine.
 """
@@ -256,6 +257,50 @@ def depth_cluster(point_lists, origins, eps, min_points=20, pick="largest"):
     org = np.array(np.broadcast_to(np.asarray(origins, np.float64).reshape(-1, 3), (n, 3))) if n else np.zeros((1, 3))
     r = depth_cluster_arrays(point_lists, org, np.arange(n, dtype=np.int32), eps, min_points, pick)
     return [r["cl_idx"][r["cl_off"][k]:r["cl_off"][k + 1]] for k in range(n)], r["cl_status"]
+
+
+# ----------------------------------------------------------------------------- yaw fit (opt-in)
+def bev_fit(xyz, off, angles=128, d0=0.05, min_points=20, min_length=1.0, idx_cap=None):
+    """cm3d_bev_fit on lists laid out back to back (host statement: bevfit.bev_fit_host).  xyz: (n, 2..4) float32, the points of all
+    lists; off: int32 (M + 1,), list m at [off[m], off[m + 1]); idx_cap: the capacity the call is told (default: the rows of xyz) --
+    offsets beyond it are clamped by the call, nothing at or beyond it is read.  Returns (fit_k (M,), fit_rect (M, 6), fit_status (M,))."""
+    from .bevfit import angle_table
+    L = _lib.lib()
+    p = np.asarray(xyz, np.float32)
+    p = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 3)
+    cap = int(p.shape[0] if idx_cap is None else idx_cap)
+    P4 = np.zeros((max(p.shape[0], cap, 1), 4), np.float32)
+    P4[:p.shape[0], :min(p.shape[1], 4)] = p[:, :4]
+    off = np.ascontiguousarray(off, np.int32)
+    M = off.size - 1
+    d_xyz, d_off, d_cs = _t(P4), _t(off), _t(angle_table(angles))
+    fk, fr, fs = _e(max(M, 1)), _e(max(M, 1), _lib.MATCH_BOX_STRIDE, dtype=torch.float64), _e(max(M, 1))
+    check(L.cm3d_bev_fit(d_xyz.data_ptr(), d_off.data_ptr(), M, max(cap, 1) if M > 0 else 0, d_cs.data_ptr(), int(angles), float(d0),
+                         int(min_points), float(min_length), fk.data_ptr(), fr.data_ptr(), fs.data_ptr(), _st()), "cm3d_bev_fit")
+    return fk.cpu().numpy()[:M], fr.cpu().numpy()[:M], fs.cpu().numpy()[:M]
+
+
+def yaw_select(fit_rect, fit_status, medoid_pos, mask_frame, class_id, is_vehicle, lane_dist, lane, lane_off, frame_lane, lane_idx,
+               lane_min_dist=0.0, pose_rt=None):
+    """cm3d_yaw_select (host statement: bevfit.yaw_select_host).  lane (L, 3) float32 x, y, yaw with lane_off (T + 1,), frame_lane (F,)
+    and lane_idx (M,) as cm3d_lane_nn leaves them; pose_rt (F, 12) float32 on Waymo.  Returns (yaw (M,) float32, yaw_idx, yaw_src)."""
+    L = _lib.lib()
+    M, F = len(medoid_pos), len(frame_lane)
+    lane = np.ascontiguousarray(lane, np.float32).reshape(-1, 3)
+    c = lambda a, dt: _t(np.array(a, dt))          # (a copy: the caller's arrays may be read-only)
+    d = dict(rect=c(fit_rect, np.float64), st=c(fit_status, np.int32), mp=c(medoid_pos, np.int32), mf=c(mask_frame, np.int32),
+             cls=c(class_id, np.int32), veh=c(is_vehicle, np.int32), ld=c(lane_dist, np.float64), lane=c(lane, np.float32), lo=c(lane_off, np.int32),
+             fl=c(frame_lane, np.int32), li=c(lane_idx, np.int32))
+    prt = c(pose_rt, np.float32) if pose_rt is not None else None
+    tab, idx, src = _e(M, 3, dtype=torch.float32), _e(M), _e(M)
+    check(L.cm3d_yaw_select(d["rect"].data_ptr(), d["st"].data_ptr(), d["mp"].data_ptr(), d["mf"].data_ptr(), d["cls"].data_ptr(),
+                            d["veh"].data_ptr(), len(is_vehicle), d["ld"].data_ptr(), float(lane_min_dist), d["lane"].data_ptr(),
+                            d["lo"].data_ptr(), d["fl"].data_ptr(), d["li"].data_ptr(), len(lane_off) - 1, lane.shape[0],
+                            prt.data_ptr() if prt is not None else 0, M, F, tab.data_ptr(), idx.data_ptr(), src.data_ptr(), _st()),
+          "cm3d_yaw_select")
+    t = tab.cpu().numpy()
+    assert not t[:, :2].any()
+    return t[:, 2].copy(), idx.cpu().numpy(), src.cpu().numpy()
 
 
 # ----------------------------------------------------------------------------- a18 (KITTI)

@@ -19,6 +19,7 @@ import torch
 
 from . import cluster as clmod
 from . import nms as nmsmod
+from . import bevfit
 from . import dist as cdist
 from . import lifting, nusc_io
 
@@ -220,7 +221,7 @@ def _token_batches(batches, index, host_s):
         host_s = 0.0
 
 
-def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None):
+def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None, yaw=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
@@ -228,9 +229,12 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
     contiguous run of the output order, with (None, 0, 0) otherwise.  filters: the opt-in stage-2 filters (lifting.Stage2Filters); the
     time of their launch goes into the reference's "drivable" bucket.  cluster: the opt-in depth clustering (cluster.DepthCluster); its
     launches lie between the compaction's event and the medoid's, and their time goes into a "cluster" bucket instead of "medoid".
-    nms: the opt-in rotated-box NMS (nms.RotatedNms); its launch lies behind the last event."""
-    pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms)
-    n_evs = 5 + (2 if filters is not None and filters.active else 0) + (2 if cluster is not None else 0)
+    nms: the opt-in rotated-box NMS (nms.RotatedNms); its launch lies behind the last event.  yaw: the opt-in yaw fit (bevfit.YawFit);
+    its two events come last, and the time between them goes into a "yawfit" bucket."""
+    kw = {} if yaw is None else {"yaw": yaw}
+    pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms, **kw)
+    n_f, n_c, n_y = (2 if filters is not None and filters.active else 0), (2 if cluster is not None else 0), (2 if yaw is not None else 0)
+    n_evs = 5 + n_f + n_c + n_y
     records, pending, segments = [], [], []                            # pending: (slot, frame ids, stage events) in flight, oldest first
 
     def spent(key, since):
@@ -254,10 +258,12 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
                     spans.append(("drivable", 5, 6))
                 for key, a, b in spans:
                     timer[key] = timer.get(key, 0.0) + evs[a].elapsed_time(evs[b]) * 1e-3
-                if cluster is not None:                                # the last two events, inside the "medoid" span
-                    dt = evs[-2].elapsed_time(evs[-1]) * 1e-3
+                if cluster is not None:                                # the two events behind the filter's, inside the "medoid" span
+                    dt = evs[5 + n_f].elapsed_time(evs[6 + n_f]) * 1e-3
                     timer["cluster"] = timer.get("cluster", 0.0) + dt
                     timer["medoid"] -= dt
+                if yaw is not None:                                    # the last two events, behind the pass
+                    timer["yawfit"] = timer.get("yawfit", 0.0) + evs[-2].elapsed_time(evs[-1]) * 1e-3
 
     try:
         for hb, ids, host_s in prepared:
@@ -287,7 +293,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
 
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                 scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None,
-                cluster=None, nms=None):
+                cluster=None, nms=None, yaw=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -320,7 +326,7 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
                 pool.terminate()
                 pool.join()
     with contextlib.closing(prepared()) as batches:
-        return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms)
+        return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms, yaw=yaw)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -395,7 +401,7 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
 
 
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
-                       scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None):
+                       scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None, yaw=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -438,7 +444,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 hb, rows = got
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
-        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms)
+        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -471,9 +477,11 @@ def main(argv=None):
                     help="the same for the pushed (vehicle) classes (the reference's commented value: 4)")
     clmod.add_arguments(ap)
     nmsmod.add_arguments(ap)
+    bevfit.add_arguments(ap)
     args = ap.parse_args(argv)
     cluster = clmod.from_namespace(args)
     nms = nmsmod.from_args(args)
+    yaw = bevfit.from_namespace(args)
     filters = lifting.Stage2Filters.from_args(args.drivable_filter, args.lane_max_dist, args.vehicle_lane_max_dist)
 
     total_start = time.time()
@@ -547,7 +555,7 @@ def main(argv=None):
             write_q.put((rec_np, first, count))
         mine = lift_scenes_native(nt, names[lo:hi], args.mask_dir, classes, device, row_to_out, args.n_sweeps, args.ratio, args.masks, timer,
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
-                                  on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms)
+                                  on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms, yaw=yaw)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
@@ -555,7 +563,7 @@ def main(argv=None):
         tokens = sample_tokens(tables, names)                  # the whole job's samples, identical on every rank
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
-                           token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms)
+                           token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms, yaw=yaw)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.

@@ -27,6 +27,7 @@ import torch
 
 from . import cluster as clmod
 from . import nms as nmsmod
+from . import bevfit
 from . import dist as cdist
 from . import lifting
 from . import waymo as wm
@@ -128,6 +129,7 @@ def main(argv=None):
                     help="the same for the pushed (vehicle) classes (the reference's commented value: 4)")
     clmod.add_arguments(ap)
     nmsmod.add_arguments(ap)
+    bevfit.add_arguments(ap)
     args = ap.parse_args(argv)
     filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
@@ -140,7 +142,7 @@ def main(argv=None):
     pri = json.load(open(args.priors)) if os.path.exists(args.priors) else None
     classes = lifting.ClassTable.waymo(pri)
     eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args),
-                             nms=nmsmod.from_args(args))
+                             nms=nmsmod.from_args(args), yaw=bevfit.from_namespace(args))
     lo, hi = cdist.shard_range(len(scenes), rank, world)
     mine, meta = [], {}
     for si in range(lo, hi):

@@ -808,6 +808,94 @@ typedef struct cm3d_depth_cluster_desc {
  * so the medoid, colsum and cm3d_obb see the clustered lists and medoid_pos is a position in them; the raw lists stay what they were. */
 int cm3d_lift_pass_clustered(const cm3d_lift_pass_desc *desc, const cm3d_depth_cluster_desc *cluster, cm3d_stream_t stream);
 
+/* ---- Vehicle yaw from the in-mask points: L-shape fit, and the yaw-fitted pass (opt-in) ----
+ * Added within ABI v5: new symbols only, no existing call changes, so CM3D_ABI_VERSION stays.
+ * On nuScenes and Waymo the reference takes a box's heading from the nearest lane point (2d_to_3d.py:295) and never from the points.
+ * cm3d_bev_fit fits a heading AXIS to every list: search-based L-shape fitting with the closeness criterion (Zhang et al., IV 2017) on
+ * the list's bird's-eye view, in whatever frame the list is in; host statement: cm3d_amd.bevfit.bev_fit_host.  What it does to label
+ * quality has not been measured, and the defaults of its parameters (cm3d_amd.bevfit.YawFit) have not been tuned.
+ *
+ * Per mask m: its list is positions hit_off[m] .. hit_off[m+1] of hit_xyz, n points (xi, yi) of float32; z is not used.  All
+ * arithmetic is float64, every product and sum rounded on its own (no contraction):
+ *   x = (double)xi - (double)x0, y = (double)yi - (double)y0, (x0, y0) the list's first point
+ *   per angle k, (c, s) = angle_cs[k]:  c1 = (x*c) + (y*s), c2 = (y*c) - (x*s); lo1, hi1, lo2, hi2 their minima and maxima over the list;
+ *     d = max(min(min(hi1 - c1, c1 - lo1), min(hi2 - c2, c2 - lo2)), d0); q_k = (((+0.0 + 1.0/d_0) + 1.0/d_1) + ...) in LIST ORDER
+ *   k* = the k of the greatest q_k, the smallest on a tie; at k*: a = hi1 - lo1, b = hi2 - lo2; length = max(a, b), width = min(a, b);
+ *     the heading axis is the longer side, (c, s) when a >= b, else (-s, c);
+ *     m1 = (lo1 + hi1) * 0.5, m2 = (lo2 + hi2) * 0.5;  cx = ((m1*c) - (m2*s)) + (double)x0,  cy = ((m1*s) + (m2*c)) + (double)y0
+ *   fit_status[m]: tested in this order -- 2 empty list; 1 fewer than min_points points; 4 a non-finite x or y in the list (tested
+ *     before any minimum or maximum is taken); 3 length < min_length; else 0 fitted.  For a status other than 0 the record is six
+ *     zeros and fit_k[m] = -1.
+ *  hit_xyz   float[idx_cap][4], 16-byte aligned; hit_off int32[n_masks+1].  An offset outside [0, idx_cap] is clamped into it and a
+ *            list end below its start is an empty list: no position >= idx_cap is read whatever hit_off holds.  Every list length up
+ *            to idx_cap gives the statement's answer: a list is staged through LDS CM3D_BEV_FIT_CHUNK points at a time.
+ *  angle_cs  double[K][2], 16-byte aligned: cos, sin of k * pi / (2K), computed by the caller (cm3d_amd.bevfit.angle_table) so that
+ *            device and host use the same bits; the kernel does no trigonometry.  K: 64, 128, 192 or 256
+ *  d0 > 0, min_points >= 2, min_length >= 0, all finite: anything else is CM3D_ERR_ARG and no launch
+ *  fit_k     int32[n_masks] OUT;  fit_status int32[n_masks] OUT
+ *  fit_rect  double[n_masks][CM3D_MATCH_BOX_STRIDE] OUT: cx, cy, length, width, cos, sin -- the record of cm3d_bev_match; the heading
+ *            is an axis, not yet resolved modulo pi
+ * One launch, one workgroup of K threads per mask: lanes are angles, a lane walks the list twice (the rule's order of summation is
+ * the lane's own loop).  No atomics, no allocation, no workspace: every run gives the same bytes. */
+#define CM3D_BEV_FIT_CHUNK 512   /* points of a list cm3d_bev_fit stages in LDS at a time (16 bytes each) */
+int cm3d_bev_fit(const float *hit_xyz, const int32_t *hit_off, int32_t n_masks, int32_t idx_cap, const double *angle_cs, int32_t K,
+                 double d0, int32_t min_points, double min_length, int32_t *fit_k, double *fit_rect, int32_t *fit_status,
+                 cm3d_stream_t stream);
+
+/* The yaw each mask's box is built with, one thread per mask; host statement: cm3d_amd.bevfit.yaw_select_host.
+ * A mask takes the fit iff medoid_pos[m] >= 0 && fit_status[m] == 0 && is_vehicle[class] && lane_dist[m] >= lane_min_dist
+ * (lane_min_dist 0: always; a positive value trusts the lanes on the road and the fit away from it).  Then, with (c, s) the record's
+ * axis:  pose_rt != NULL (Waymo: the lists are in the vehicle frame) rotates it by the float32 pose's upper-left 2x2 widened to
+ * float64, cg = (R00*c) + (R01*s), sg = (R10*c) + (R11*s), else cg = c, sg = s;  yl = (double) the lane point's float32 yaw,
+ * dot = (cg*cos(yl)) + (sg*sin(yl));  dot < 0: both negated -- the fit gives the axis, the map which way along it;
+ * yaw = (float)atan2(sg, cg).  Every other mask with a medoid gets its lane point's yaw bit for bit -- the point cm3d_box_nms reads,
+ * lane[lane_off[frame_lane[mask_frame[m]]] + lane_idx[m]] -- and a mask without a medoid gets 0.  Indices are clamped into their
+ * arrays (n_frames, n_tables, n_lane_points).
+ *  pose_rt  float[F][12] as in cm3d_centroid_transform, or NULL;  lane_min_dist >= 0 (NaN: CM3D_ERR_ARG)
+ *  yaw_tab  float[n_masks][3] OUT: 0, 0, yaw -- a lane table of n_masks rows;  yaw_idx int32[n_masks] OUT: yaw_idx[m] = m
+ *  yaw_src  int32[n_masks] OUT: 0 lane, 1 fit */
+int cm3d_yaw_select(const double *fit_rect, const int32_t *fit_status, const int32_t *medoid_pos, const int32_t *mask_frame,
+                    const int32_t *class_id, const int32_t *is_vehicle, int32_t n_classes, const double *lane_dist,
+                    double lane_min_dist, const float *lane, const int32_t *lane_off, const int32_t *frame_lane,
+                    const int32_t *lane_idx, int32_t n_tables, int32_t n_lane_points, const float *pose_rt, int32_t n_masks,
+                    int32_t n_frames, float *yaw_tab, int32_t *yaw_idx, int32_t *yaw_src, cm3d_stream_t stream);
+
+/* What the yaw-fitted pass needs beyond cm3d_lift_pass_desc.  `size` is sizeof(cm3d_yaw_fit_desc) (another value: CM3D_ERR_ARG).
+ *  hit_xyz, hit_off  the lists to fit; NULL: the pass descriptor's (a clustered pass hands its cl_xyz, cl_off)
+ *  medoid_pos        the positions that decide which masks have a box; NULL: the pass descriptor's (a filtered pass hands its
+ *                    medoid_pos_kept)
+ *  tab_off   int32[2] = {0, n_masks};  tab_frame int32[n_frames] = zeros: filled by the caller once, they make yaw_tab the lane table
+ *            of every frame
+ *  the other fields as in cm3d_bev_fit and cm3d_yaw_select */
+typedef struct cm3d_yaw_fit_desc {
+    int64_t size;
+    const double *angle_cs;
+    const float *hit_xyz; const int32_t *hit_off; const int32_t *medoid_pos;
+    int32_t *fit_k; double *fit_rect; int32_t *fit_status;
+    float *yaw_tab; int32_t *yaw_idx; int32_t *yaw_src;
+    const int32_t *tab_off; const int32_t *tab_frame;
+    void *ev[2];                 /* optional hipEvent_t, recorded in front of cm3d_bev_fit and behind cm3d_yaw_select */
+    double d0, min_length, lane_min_dist;
+    int32_t K, min_points;
+} cm3d_yaw_fit_desc;
+
+/* The three launches behind a pass that has run (host code, csrc/pass_yawfit.cpp).  Enqueues on `stream`, stopping at and returning
+ * the first error; a wrong `size` or a null table or output: CM3D_ERR_ARG and no call:
+ *
+ *   record fit->ev[0]
+ *   cm3d_bev_fit                          the lists -> fit_k, fit_rect, fit_status
+ *   cm3d_yaw_select                       lane_idx, lane_dist, lane tables ... of desc -> yaw_tab, yaw_idx, yaw_src
+ *   record fit->ev[1]
+ *   cm3d_box_nms_bounded                  as in the plain pass, with lane = yaw_tab, lane_off = tab_off, frame_lane = tab_frame,
+ *                                         lane_idx = yaw_idx (and fit->medoid_pos when given): `box` and `flags` written anew
+ *
+ * k_box_nms reads nothing of a lane point but its yaw, so it is untouched.  Column 5 of the box record ("lane yaw") then holds the yaw
+ * that was USED: the fitted one where yaw_src[m] == 1.  A mask with yaw_src[m] == 0 gets the record the plain pass gave it. */
+int cm3d_yaw_fit_boxes(const cm3d_lift_pass_desc *desc, const cm3d_yaw_fit_desc *fit, cm3d_stream_t stream);
+/* The opt-in yaw-fitted pass: cm3d_lift_pass(desc), then cm3d_yaw_fit_boxes(desc, fit).  cm3d_lift_pass and cm3d_pipe_submit know
+ * nothing of it. */
+int cm3d_lift_pass_yaw_fitted(const cm3d_lift_pass_desc *desc, const cm3d_yaw_fit_desc *fit, cm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
