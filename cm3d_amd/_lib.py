@@ -112,6 +112,7 @@ SIGNATURES = {
     "cm3d_yaw_select": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _p, C.c_double, _p, _p, _p, _p, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p]),
     "cm3d_yaw_fit_boxes": (_i32, [_p, _p, _p]),
     "cm3d_lift_pass_yaw_fitted": (_i32, [_p, _p, _p]),
+    "cm3d_lift_pass_opt": (_i32, [_p, _p, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order
@@ -157,6 +158,16 @@ class YawFitDesc(C.Structure):
                                                       "yaw_tab", "yaw_idx", "yaw_src", "tab_off", "tab_frame")]
                 + [("ev", _p * 2), ("d0", C.c_double), ("min_length", C.c_double), ("lane_min_dist", C.c_double), ("K", _i32),
                    ("min_points", _i32)])
+
+
+class RotatedNmsDesc(C.Structure):
+    """cm3d_rotated_nms_desc of include/cm3d_hip.h, field for field."""
+    _fields_ = [("size", _i64), ("thr", _p), ("n_thr", _i32), ("measure", _i32), ("class_agnostic", _i32), ("reserved", _i32)]
+
+
+class LiftPassOptions(C.Structure):
+    """cm3d_lift_pass_options of include/cm3d_hip.h, field for field: pointers to the descriptors above, NULL for a stage that is off."""
+    _fields_ = [("size", _i64)] + [(n, _p) for n in ("cluster", "filter", "yaw", "nms")]
 
 
 class Cm3dError(RuntimeError):

@@ -1,4 +1,5 @@
-"""Host side of the opt-in yaw fit (include/cm3d_hip.h: cm3d_bev_fit, cm3d_yaw_select, cm3d_lift_pass_yaw_fitted).
+"""Host side of the opt-in yaw fit (include/cm3d_hip.h: cm3d_bev_fit, cm3d_yaw_select, cm3d_yaw_fit_boxes; a stage of
+cm3d_lift_pass_opt).
 
 On nuScenes and Waymo a box's heading is the yaw of the nearest lane point (2d_to_3d.py:295): the in-mask points are never looked at.
 What stands here is a heading fitted to them: search-based L-shape fitting with the closeness criterion (Zhang, Xu, Dolan, Gong: "Efficient

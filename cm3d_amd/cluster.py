@@ -1,4 +1,4 @@
-"""Host side of the depth clustering of the in-mask lists (include/cm3d_hip.h: cm3d_depth_cluster, cm3d_lift_pass_clustered).
+"""Host side of the depth clustering of the in-mask lists (include/cm3d_hip.h: cm3d_depth_cluster; a stage of cm3d_lift_pass_opt).
 
 The reference carries a clustering step it never calls: clusters_hdbscan (src/kitti/2d_to_3d.py:159-174, src/waymo/2d_to_3d.py:102-117,
 min_cluster_size=20, cluster_selection_epsilon=1; its only call site is commented out at src/kitti/2d_to_3d.py:1192).  What stands

@@ -1,4 +1,5 @@
-"""Host side of the drivable-area test and of the stage-2 filters (include/cm3d_hip.h: cm3d_points_in_polygons, cm3d_stage2_filter).
+"""Host side of the drivable-area test and of the stage-2 filters (include/cm3d_hip.h: cm3d_points_in_polygons, cm3d_stage2_filter; a stage of
+cm3d_lift_pass_opt).
 
 The reference tests box centres against the map's drivable-area polygons in two places: the evaluator's filter
 (eval_custom.py:496-526) and the stage-2 filters it ships commented out (src/nuscenes/2d_to_3d.py:755-785, labels "Object lane

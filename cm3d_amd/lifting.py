@@ -432,25 +432,19 @@ class LiftEngine:
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
         obb: also fit KITTI's oriented box of every mask on the device (stage_obb, cm3d_obb: src/kitti/2d_to_3d.py:855-876, :1524);
         download() then returns `obb_yaw` and `obb_status`.  Off: no OBB buffer, no OBB launch.
-        filters: the opt-in stage-2 filters (drivable.Stage2Filters; the reference ships them commented out, :755-785).  With any of them
-        on, `run` enqueues cm3d_lift_pass_filtered -- the plain pass, cm3d_stage2_filter, the box launch again on the kept medoid
-        positions -- and download(full=True) adds `on_road` and `medoid_pos_kept`; `drivable` needs batches with polygon tables
-        (HostBatch.polygons).  None, or all switches off: nothing changes, neither a buffer nor a launch.
-        cluster: the opt-in depth clustering of the in-mask lists (cluster.DepthCluster; the reference's clusters_hdbscan is dead code).
-        `run` then enqueues cm3d_lift_pass_clustered -- the pass through the compaction, cm3d_depth_cluster with the batch's `ego_xyz` as
-        the frames' origins, the rest of the pass on the clustered lists -- so that `medoid_pos` is a position in the clustered list
-        (`cl_off`), and the OBB fit sees those lists too; download() adds `cl_off`, `cl_status` (full=True: `cl_idx`, `cl_xyz`), while
-        `hit_off` / `hit_idx` / `hit_xyz` stay the raw lists.  With filters also on, the filter and the second box launch follow
-        through their own calls.  None: nothing changes, neither a buffer nor a launch.
-        nms: the opt-in rotated-box NMS (nms.RotatedNms; the reference's rotated-rectangle nms is dead code).  `run` then enqueues
-        cm3d_box_rotated_nms as the last launch of whichever pass it is: bit 1 of `flags` and column 9 of `box` are decided again by the
-        bird's-eye-view overlap of the boxes the pass wrote, everything else stays what the pass wrote.  None: nothing changes, neither
-        a buffer nor a launch.
-        yaw: the opt-in yaw fit (bevfit.YawFit; nuScenes and Waymo batches -- KITTI's yaw comes from cm3d_obb).  `run` then enqueues
-        cm3d_lift_pass_yaw_fitted -- the plain pass, cm3d_bev_fit on the in-mask lists, cm3d_yaw_select, the box launch again with the
-        chosen yaws where the lane tables stood -- or, behind a clustered or filtered pass, cm3d_yaw_fit_boxes on the `cl_*` lists and
-        on `medoid_pos_kept`; the rotated NMS stays last.  download() adds `yaw_src`, `fit_status`, `fit_k` and `fit_rect`, and
-        column 5 of `box` holds the yaw that was used.  None: nothing changes, neither a buffer nor a launch."""
+        The four opt-in stages below are off when None (or inactive): then nothing changes, neither a buffer nor a launch.  With any of
+        them on, `run` still makes one call, cm3d_lift_pass_opt; include/cm3d_hip.h states where each stage stands in the pass.
+        filters: the stage-2 filters (drivable.Stage2Filters; the reference ships them commented out, :755-785).  download(full=True)
+        adds `on_road` and `medoid_pos_kept`; `drivable` needs batches with polygon tables (HostBatch.polygons).
+        cluster: the depth clustering of the in-mask lists (cluster.DepthCluster; the reference's clusters_hdbscan is dead code), with
+        the batch's `ego_xyz` as the frames' origins.  `medoid_pos` is then a position in the clustered list (`cl_off`), and the OBB fit
+        sees those lists too; download() adds `cl_off`, `cl_status` (full=True: `cl_idx`, `cl_xyz`), while `hit_off` / `hit_idx` /
+        `hit_xyz` stay the raw lists.
+        nms: the rotated-box NMS (nms.RotatedNms; the reference's rotated-rectangle nms is dead code): bit 1 of `flags` and column 9 of
+        `box` are decided again by the bird's-eye-view overlap of the boxes the pass wrote, everything else stays what the pass wrote.
+        yaw: the yaw fit (bevfit.YawFit; nuScenes and Waymo batches -- KITTI's yaw comes from cm3d_obb), on the clustered lists and the
+        kept positions where the engine has those.  download() adds `yaw_src`, `fit_status`, `fit_k` and `fit_rect`, and column 5 of
+        `box` holds the yaw that was used."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -608,15 +602,18 @@ class LiftEngine:
         # what a pass hands to the library (cm3d_lift_pass), filled once; `refresh_pass_descriptor` adds what changes from pass to pass
         b.desc = self._batch_descriptor(b)
         b.desc_ref = ctypes.byref(b.desc)
-        if self.filters is not None:
-            b.filter_desc = self._filter_descriptor(b)
-            b.filter_desc_ref = ctypes.byref(b.filter_desc)
-        if self.cluster is not None:
-            b.cluster_desc = self._cluster_descriptor(b)
-            b.cluster_desc_ref = ctypes.byref(b.cluster_desc)
-        if self.yaw is not None:
-            b.yaw_desc = self._yaw_descriptor(b)
-            b.yaw_desc_ref = ctypes.byref(b.yaw_desc)
+        # the opt-in stages (cm3d_lift_pass_opt): one descriptor per stage the engine has -- `b.filter_desc` ... `b.nms_desc`, which keep
+        # them alive -- and the record that points at them.  `timed`: those with an event pair, in the order `run` appends their events
+        stages = {"filter": self.filters and self._filter_descriptor(b), "cluster": self.cluster and self._cluster_descriptor(b),
+                  "yaw": self.yaw and self._yaw_descriptor(b), "nms": self.nms and self._nms_descriptor()}
+        stages = {name: desc for name, desc in stages.items() if desc is not None}
+        b.opts = _lib.LiftPassOptions()
+        b.opts.size = ctypes.sizeof(_lib.LiftPassOptions)
+        for name, desc in stages.items():
+            setattr(b, name + "_desc", desc)
+            setattr(b.opts, name, ctypes.addressof(desc))
+        b.timed = {name: desc for name, desc in stages.items() if name != "nms"}
+        b.opts_ref = ctypes.byref(b.opts) if stages else None
         self.b = b
         return b
 
@@ -636,7 +633,7 @@ class LiftEngine:
         return hit
 
     def _filter_descriptor(self, b):
-        """cm3d_stage2_filter_desc of the resident batch (refresh_pass_descriptor's counterpart, run, sets its events)."""
+        """cm3d_stage2_filter_desc of the resident batch (refresh_pass_descriptor sets its events)."""
         f = _lib.Stage2FilterDesc()
         f.size = ctypes.sizeof(_lib.Stage2FilterDesc)
         if b.polygon_index is not None:
@@ -649,7 +646,7 @@ class LiftEngine:
         return f
 
     def _cluster_descriptor(self, b):
-        """cm3d_depth_cluster_desc of the resident batch (run sets its events).  The origin of frame f is ego_xyz[f]: the LIDAR_TOP ego
+        """cm3d_depth_cluster_desc of the resident batch (refresh_pass_descriptor sets its events).  The origin of frame f is ego_xyz[f]: the LIDAR_TOP ego
         translation on nuScenes, zeros on Waymo (vehicle frame) and on KITTI (reference-camera frame)."""
         c = _lib.DepthClusterDesc()
         c.size = ctypes.sizeof(_lib.DepthClusterDesc)
@@ -661,8 +658,9 @@ class LiftEngine:
         return c
 
     def _yaw_descriptor(self, b):
-        """cm3d_yaw_fit_desc of the resident batch (run sets its events).  The lists that are fitted are the clustered ones when the
-        engine clusters, the positions that decide about a box the kept ones when it filters."""
+        """cm3d_yaw_fit_desc of the resident batch (refresh_pass_descriptor sets its events).  The lists that are fitted are the clustered
+        ones when the engine clusters, the positions that decide about a box the kept ones when it filters: what cm3d_lift_pass_opt
+        derives itself, stated here for cm3d_yaw_fit_boxes alone (stage_yaw_fit)."""
         y = _lib.YawFitDesc()
         y.size = ctypes.sizeof(_lib.YawFitDesc)
         y.angle_cs = _ptr(self.angle_cs)
@@ -676,6 +674,13 @@ class LiftEngine:
         y.K, y.min_points = self.yaw.angles, self.yaw.min_points
         y.d0, y.min_length, y.lane_min_dist = self.yaw.d0, self.yaw.min_length, self.yaw.lane_min_dist
         return y
+
+    def _nms_descriptor(self):
+        """cm3d_rotated_nms_desc of the engine: what cm3d_box_rotated_nms takes beyond the pass descriptor."""
+        n = _lib.RotatedNmsDesc()
+        n.size = ctypes.sizeof(_lib.RotatedNmsDesc)
+        n.thr, n.n_thr, n.measure, n.class_agnostic = _ptr(self.rot_thr), self.rot_thr.numel(), self.nms.measure_index, int(self.nms.class_agnostic)
+        return n
 
     def _batch_descriptor(self, b):
         """cm3d_lift_pass_desc of the resident batch: the arguments of the calls a pass makes, name for name (the fields that belong to
@@ -714,11 +719,12 @@ class LiftEngine:
             raise Cm3dError("dense masks requested but not resident: call decode_masks_dense() or pass dense_masks")
         return b.dense.data_ptr()
 
-    def refresh_pass_descriptor(self, dense=None, project_events=None, stage_events=None):
-        """The descriptor of the next pass over the resident batch, for cm3d_lift_pass / cm3d_pipe_submit: sets what may change between
-        two passes over one batch -- the mask route (`dense`: resident_masks), the reset, the hint switch, the lane index in use and
-        whether its build has to be waited for, the events (project_events: a pair of torch.cuda.Event, stage_events: five) -- and
-        counts the pass.  The build of the lane index must have been started (start_lane_grid)."""
+    def refresh_pass_descriptor(self, dense=None, project_events=None, stage_events=None, option_events=None):
+        """The descriptor of the next pass over the resident batch, for cm3d_lift_pass[_opt] / cm3d_pipe_submit: sets what may change
+        between two passes over one batch -- the mask route (`dense`: resident_masks), the reset, the hint switch, the lane index in use
+        and whether its build has to be waited for, the events (project_events: a pair of torch.cuda.Event, stage_events: five,
+        option_events: stage name -> pair, for `b.timed`; every slot is set or cleared on every pass, so none keeps the event of an
+        earlier one) -- and counts the pass.  The build of the lane index must have been started (start_lane_grid)."""
         b = self.b
         d = b.desc
         d.dense = dense
@@ -732,6 +738,8 @@ class LiftEngine:
         d.lane_ready = None if ln.get("done") else ln["built_event"].cuda_event
         d.ev_project[:] = self._raw_events(project_events, 2)
         d.ev_stage[:] = self._raw_events(stage_events, 5)
+        for name, desc in b.timed.items():
+            desc.ev[:] = self._raw_events((option_events or {}).get(name), 2)
         ln["passes_since_build"] = ln.get("passes_since_build", 0) + 1
         return b.desc_ref
 
@@ -897,10 +905,13 @@ class LiftEngine:
                                     _ptr(b.frame_lane), b.n_tables, b.n_lane, _ptr(b.grid), _ptr(b.lane_idx),
                                     _ptr(b.lane_dist), _ptr(b.ws), b.ws_bytes, st), "cm3d_lane_nn")
 
-    def stage_boxes(self, st):
+    def stage_boxes(self, st, medoid_pos=None):
+        """The box launch on the resident results.  medoid_pos: the positions that decide which masks have a box (None: the medoid
+        stage's; an engine with filters hands `b.medoid_pos_kept` for the launch behind the filter)."""
         b = self.b
         # (`planes` words of mask bits per point: no frame of the batch has more than 32 * planes masks -- the bound cm3d_lift_pass hands over)
-        check(self.lib.cm3d_box_nms_bounded(_ptr(b.centroid_g), _ptr(b.medoid_pos), _ptr(b.mask_off), b.F, b.M, _ptr(b.class_id),
+        check(self.lib.cm3d_box_nms_bounded(_ptr(b.centroid_g), _ptr(b.medoid_pos if medoid_pos is None else medoid_pos), _ptr(b.mask_off),
+                                            b.F, b.M, _ptr(b.class_id),
                                             _ptr(b.score), _ptr(b.lane), _ptr(b.lane_off), _ptr(b.frame_lane), _ptr(b.lane_idx),
                                             _ptr(b.lane_dist), _ptr(self.prior_wlh), _ptr(self.is_vehicle), _ptr(self.nms_group),
                                             _ptr(self.nms_thr), len(self.classes.names), _ptr(b.ego_xyz), _ptr(b.pose_inv),
@@ -921,30 +932,10 @@ class LiftEngine:
                                           c.eps, c.min_points, c.pick, c.cl_off, c.cl_tile_off, c.cl_idx, c.cl_xyz, c.cl_status, c.ws,
                                           c.ws_bytes, st), "cm3d_depth_cluster")
 
-    def stage_filter(self, st, events=None):
-        """The stage-2 filter on the resident results and the box launch again on the kept medoid positions (what
-        cm3d_lift_pass_filtered enqueues behind the plain pass), for the pass that is not the plain one.  events: optional pair of
-        torch.cuda.Event recorded around the filter launch."""
-        b, f = self.b, self.b.filter_desc
-        if events is not None:
-            events[0].record(torch.cuda.current_stream(self.dev))
-        check(self.lib.cm3d_stage2_filter(_ptr(b.centroid_g), _ptr(b.medoid_pos), _ptr(b.mask_frame), _ptr(b.frame_lane), _ptr(b.class_id),
-                                          _ptr(b.lane_dist), b.M, b.F, f.tab_y, f.tab_slab, f.slab_off, f.ent_edge, f.ent_ring, f.edge,
-                                          f.ring_info, f.n_poly_tables, f.needs_road, _ptr(self.is_vehicle), len(self.classes.names),
-                                          f.lane_max_dist, f.vehicle_lane_max_dist, f.medoid_pos_kept, f.on_road, st), "cm3d_stage2_filter")
-        if events is not None:
-            events[1].record(torch.cuda.current_stream(self.dev))
-        check(self.lib.cm3d_box_nms_bounded(_ptr(b.centroid_g), _ptr(b.medoid_pos_kept), _ptr(b.mask_off), b.F, b.M, _ptr(b.class_id),
-                                            _ptr(b.score), _ptr(b.lane), _ptr(b.lane_off), _ptr(b.frame_lane), _ptr(b.lane_idx),
-                                            _ptr(b.lane_dist), _ptr(self.prior_wlh), _ptr(self.is_vehicle), _ptr(self.nms_group),
-                                            _ptr(self.nms_thr), len(self.classes.names), _ptr(b.ego_xyz), _ptr(b.pose_inv),
-                                            min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), _ptr(b.box), _ptr(b.flags), st),
-              "cm3d_box_nms_bounded")
-
     def stage_yaw_fit(self, st):
         """The yaw fit's three launches alone, on what the last pass left resident (cm3d_yaw_fit_boxes: cm3d_bev_fit, cm3d_yaw_select,
         the box launch with the chosen yaws)."""
-        check(self.lib.cm3d_yaw_fit_boxes(self.b.desc_ref, self.b.yaw_desc_ref, st), "cm3d_yaw_fit_boxes")
+        check(self.lib.cm3d_yaw_fit_boxes(self.b.desc_ref, ctypes.byref(self.b.yaw_desc), st), "cm3d_yaw_fit_boxes")
 
     def stage_bev_fit(self, st):
         """cm3d_bev_fit alone, on the lists the yaw-fitted pass fits."""
@@ -954,11 +945,11 @@ class LiftEngine:
 
     def stage_rotated_nms(self, st):
         """The opt-in rotated-box NMS on the box rows and flags the pass's (last) box launch wrote (cm3d_box_rotated_nms)."""
-        b = self.b
+        b, n = self.b, self.b.nms_desc
         check(self.lib.cm3d_box_rotated_nms(_ptr(b.box), _ptr(b.flags), _ptr(b.mask_off), b.F, b.M, _ptr(b.class_id), _ptr(self.prior_wlh),
-                                            _ptr(self.nms_group), len(self.classes.names), _ptr(self.rot_thr), self.rot_thr.numel(),
-                                            self.nms.measure_index, int(self.nms.class_agnostic), int(b.pose_inv is not None),
-                                            min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), st), "cm3d_box_rotated_nms")
+                                            _ptr(self.nms_group), len(self.classes.names), n.thr, n.n_thr, n.measure, n.class_agnostic,
+                                            int(b.pose_inv is not None), min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), st),
+              "cm3d_box_rotated_nms")
 
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
@@ -967,53 +958,21 @@ class LiftEngine:
         torch.cuda.Event recorded around the projection launch on the launch stream (bench.py's roofline timing).
         stage_events: optional list; gets five timing events appended -- before the point/mask stages, behind the compaction,
         the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them.
-        An engine with filters appends two more, around the filter launch (the "drivable" bucket), and enqueues the filtered pass.
-        An engine with a depth clustering appends two more after those, around the clustering's launches (the "cluster" bucket; they
-        lie between the second and the third of the five), and enqueues the clustered pass.
-        An engine with a yaw fit appends two more after those, around the fit's two launches (the "yawfit" bucket; behind the fifth
-        event), and enqueues the yaw-fitted pass -- or, behind a clustered or filtered pass, the fit's three launches.
-        An engine with a rotated-box NMS enqueues its launch last, behind the fifth event; no allocation, no synchronisation."""
+        Each opt-in stage the engine has appends two more behind those, in this order: around the filter launch (the "drivable"
+        bucket), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
+        the yaw fit's two launches (the "yawfit" bucket; behind the fifth event).  One library call enqueues the pass, opt-in stages
+        included (cm3d_lift_pass_opt; include/cm3d_hip.h states the order); no allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
             self.start_lane_grid()
-        marks = None
+        marks = omarks = None
         if stage_events is not None:
             marks = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
-            stage_events.extend(marks)
+            omarks = {name: [torch.cuda.Event(enable_timing=True) for _ in range(2)] for name in self.b.timed}
+            stage_events.extend(marks + [ev for pair in omarks.values() for ev in pair])
         st = torch.cuda.current_stream(self.dev).cuda_stream
-        fmarks = cmarks = ymarks = None
-        if self.filters is not None and stage_events is not None:
-            fmarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            stage_events.extend(fmarks)
-        if self.yaw is not None:
-            if stage_events is not None:
-                ymarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-            self.b.yaw_desc.ev[:] = self._raw_events(ymarks, 2)
-        if self.cluster is not None:
-            if stage_events is not None:
-                cmarks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-                stage_events.extend(cmarks)
-            self.b.cluster_desc.ev[:] = self._raw_events(cmarks, 2)
-            check(self.lib.cm3d_lift_pass_clustered(self.refresh_pass_descriptor(dense, project_events, marks), self.b.cluster_desc_ref, st),
-                  "cm3d_lift_pass_clustered")
-            if self.filters is not None:             # the filter and the boxes again, on what the clustered pass left: the existing calls
-                self.stage_filter(st, fmarks)
-        elif self.filters is not None:
-            self.b.filter_desc.ev[:] = self._raw_events(fmarks, 2)
-            check(self.lib.cm3d_lift_pass_filtered(self.refresh_pass_descriptor(dense, project_events, marks), self.b.filter_desc_ref, st),
-                  "cm3d_lift_pass_filtered")
-        elif self.yaw is not None:
-            check(self.lib.cm3d_lift_pass_yaw_fitted(self.refresh_pass_descriptor(dense, project_events, marks), self.b.yaw_desc_ref, st),
-                  "cm3d_lift_pass_yaw_fitted")
-        else:
-            check(self.lib.cm3d_lift_pass(self.refresh_pass_descriptor(dense, project_events, marks), st), "cm3d_lift_pass")
-        if self.yaw is not None:
-            if self.cluster is not None or self.filters is not None:      # behind the pass that is not the plain one: the three launches alone
-                self.stage_yaw_fit(st)
-            if ymarks is not None:
-                stage_events.extend(ymarks)
-        if self.nms is not None:                     # behind the pass's last box launch, whichever pass it was
-            self.stage_rotated_nms(st)
+        check(self.lib.cm3d_lift_pass_opt(self.refresh_pass_descriptor(dense, project_events, marks, omarks), self.b.opts_ref, st),
+              "cm3d_lift_pass_opt")
 
     def capture_graph(self, masks="rle"):
         """Captures one pass over the resident batch into a HIP graph and returns it (`g.replay()` re-runs the pass
@@ -1033,7 +992,6 @@ class LiftEngine:
     def hit_chunk_rows(self) -> int:
         """Rows of the resident batch that lie in a 256-row block with at least one in-mask point after the last pass: the rows
         whose hit words the projection wrote and the compaction read (bench.py's byte accounting; synchronises the stream)."""
-        import ctypes
         b = self.b
         out = ctypes.c_int64(0)
         check(self.lib.cm3d_project_hit_rows(_ptr(b.pg_ws), b.pg_ws_bytes, b.F, b.max_pts, b.planes, ctypes.addressof(out),
@@ -1151,9 +1109,9 @@ class LiftPipeline:
     variable read, never set; 4 queues when it is unset.  With that many streams or more than slots, slot s runs on `streams[s]` as
     it always did.  With fewer, pass number k runs on `streams[k % n]`, the slots take turns, and a slot's event keeps two passes of
     one slot in order when they land on different streams ("Passes rotate over as many streams as the process has queues
-    for").  `exec_streams` overrides the policy (tests).  Every pass is enqueued by one library call (cm3d_lift_pass): `submit` and a
-    `rerun` that has to start the build of the lane index go through `LiftEngine.run` on the chosen stream, every other `rerun` hands the
-    slot's descriptor to cm3d_pipe_submit, which picks the stream itself.
+    for").  `exec_streams` overrides the policy (tests).  Every pass is enqueued by one library call (cm3d_lift_pass[_opt]): `submit`, a
+    `rerun` that has to start the build of the lane index and every pass of engines with opt-in stages go through `LiftEngine.run` on the
+    chosen stream, every other `rerun` hands the slot's descriptor to cm3d_pipe_submit, which picks the stream itself.
 
     Rule for callers that use `streams[slot]` or `engines[slot]` directly (an upload, a pass stage by stage, a graph capture): the device
     must be idle before and after -- `torch.cuda.synchronize()` on both sides --, because the slot's last pass need not have run on
@@ -1246,13 +1204,13 @@ class LiftPipeline:
         eng = self.engines[slot]
         mode = masks or self.masks[slot]
         self._pin_if_captured()
-        if eng._lane["built"] and eng.filters is None and eng.cluster is None and eng.nms is None and eng.yaw is None:     # (cm3d_pipe_submit knows only the plain pass)
+        if eng._lane["built"] and eng.b.opts_ref is None:     # (cm3d_pipe_submit knows only the plain pass)
             # (no stream context, no Python between the launches: what bench.py's headline times.  A pair of events around the
             # projection kernel rides along, so that a timed pass costs the host what an untimed one does)
             rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor(eng.resident_masks(mode), project_events))
             if rc < 0:
                 check(rc, "cm3d_pipe_submit")
-        else:                                # the pass has to start the build of the lane index first, or is not the plain one (filters, clustering, rotated NMS): Python's to do
+        else:                                # the pass has to start the build of the lane index first, or has opt-in stages: LiftEngine.run's to do
             st = self.streams[self._acquire(slot)]
             try:
                 with torch.cuda.stream(st):

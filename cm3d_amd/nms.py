@@ -1,4 +1,4 @@
-"""Host side of the rotated-box NMS (include/cm3d_hip.h: cm3d_rotated_nms, cm3d_box_rotated_nms).
+"""Host side of the rotated-box NMS (include/cm3d_hip.h: cm3d_rotated_nms, cm3d_box_rotated_nms; the last stage of cm3d_lift_pass_opt).
 
 Every pseudo-label file passes through the reference's class-aware circle NMS (circle_nms, src/nuscenes/2d_to_3d.py:309-332): a box goes
 when another box of its class has its centre within a per-class radius, wherever the two rectangles lie.  The reference also carries a

@@ -738,16 +738,8 @@ typedef struct cm3d_stage2_filter_desc {
     int32_t n_poly_tables, reserved;
 } cm3d_stage2_filter_desc;
 
-/* The opt-in filtered pass (host code, csrc/pass_filter.cpp; cm3d_lift_pass and cm3d_pipe_submit know nothing of it).  Enqueues on
- * `stream`, stopping at and returning the first error:
- *
- *   cm3d_lift_pass(desc)                  the plain pass, boxes of every mask included
- *   record filter->ev[0]
- *   cm3d_stage2_filter                    centroid_g, medoid_pos, lane_dist ... of desc -> medoid_pos_kept, on_road
- *   record filter->ev[1]
- *   cm3d_box_nms_bounded                  as in the plain pass, with medoid_pos_kept for medoid_pos: `box` and `flags` written anew
- *
- * k_box_nms treats a negative position as "no box", so a dropped mask neither gets a box nor suppresses one. */
+/* The opt-in filtered pass: cm3d_lift_pass_opt (below) with only `filter` set; a NULL `filter` is CM3D_ERR_ARG.  k_box_nms treats a
+ * negative position as "no box", so a dropped mask neither gets a box nor suppresses one. */
 int cm3d_lift_pass_filtered(const cm3d_lift_pass_desc *desc, const cm3d_stage2_filter_desc *filter, cm3d_stream_t stream);
 
 /* ---- Depth clustering of every mask's in-mask list, and the clustered pass (opt-in) ----
@@ -796,16 +788,8 @@ typedef struct cm3d_depth_cluster_desc {
     int32_t min_points, pick;
 } cm3d_depth_cluster_desc;
 
-/* The opt-in clustered pass (host code, csrc/pass_cluster.cpp; cm3d_lift_pass and cm3d_pipe_submit know nothing of it).  Enqueues on
- * `stream`, stopping at and returning the first error; a wrong `size` or a null output: CM3D_ERR_ARG and no call:
- *
- *   cm3d_lift_pass_head(desc)             through the compaction: hit_off, tile_off, hit_idx, hit_xyz
- *   record cluster->ev[0]
- *   cm3d_depth_cluster                    desc's lists -> cl_off, cl_tile_off, cl_idx, cl_xyz, cl_status
- *   record cluster->ev[1]
- *   cm3d_lift_pass_tail(desc')            desc' = desc with hit_off, tile_off, hit_idx, hit_xyz = the cl_* arrays and tile_work = NULL
- *
- * so the medoid, colsum and cm3d_obb see the clustered lists and medoid_pos is a position in them; the raw lists stay what they were. */
+/* The opt-in clustered pass: cm3d_lift_pass_opt (below) with only `cluster` set; a NULL `cluster` is CM3D_ERR_ARG.  The medoid, colsum
+ * and cm3d_obb see the clustered lists and medoid_pos is a position in them; the raw lists stay what they were. */
 int cm3d_lift_pass_clustered(const cm3d_lift_pass_desc *desc, const cm3d_depth_cluster_desc *cluster, cm3d_stream_t stream);
 
 /* ---- Vehicle yaw from the in-mask points: L-shape fit, and the yaw-fitted pass (opt-in) ----
@@ -861,9 +845,9 @@ int cm3d_yaw_select(const double *fit_rect, const int32_t *fit_status, const int
                     int32_t n_frames, float *yaw_tab, int32_t *yaw_idx, int32_t *yaw_src, cm3d_stream_t stream);
 
 /* What the yaw-fitted pass needs beyond cm3d_lift_pass_desc.  `size` is sizeof(cm3d_yaw_fit_desc) (another value: CM3D_ERR_ARG).
- *  hit_xyz, hit_off  the lists to fit; NULL: the pass descriptor's (a clustered pass hands its cl_xyz, cl_off)
- *  medoid_pos        the positions that decide which masks have a box; NULL: the pass descriptor's (a filtered pass hands its
- *                    medoid_pos_kept)
+ *  hit_xyz, hit_off  the lists cm3d_yaw_fit_boxes fits; NULL: the pass descriptor's
+ *  medoid_pos        the positions that decide for cm3d_yaw_fit_boxes which masks have a box; NULL: the pass descriptor's
+ *                    (cm3d_lift_pass_opt derives all three itself: there each is NULL or what it derives)
  *  tab_off   int32[2] = {0, n_masks};  tab_frame int32[n_frames] = zeros: filled by the caller once, they make yaw_tab the lane table
  *            of every frame
  *  the other fields as in cm3d_bev_fit and cm3d_yaw_select */
@@ -879,7 +863,7 @@ typedef struct cm3d_yaw_fit_desc {
     int32_t K, min_points;
 } cm3d_yaw_fit_desc;
 
-/* The three launches behind a pass that has run (host code, csrc/pass_yawfit.cpp).  Enqueues on `stream`, stopping at and returning
+/* The three launches behind a pass that has run (host code, csrc/pass_options.cpp).  Enqueues on `stream`, stopping at and returning
  * the first error; a wrong `size` or a null table or output: CM3D_ERR_ARG and no call:
  *
  *   record fit->ev[0]
@@ -892,9 +876,42 @@ typedef struct cm3d_yaw_fit_desc {
  * k_box_nms reads nothing of a lane point but its yaw, so it is untouched.  Column 5 of the box record ("lane yaw") then holds the yaw
  * that was USED: the fitted one where yaw_src[m] == 1.  A mask with yaw_src[m] == 0 gets the record the plain pass gave it. */
 int cm3d_yaw_fit_boxes(const cm3d_lift_pass_desc *desc, const cm3d_yaw_fit_desc *fit, cm3d_stream_t stream);
-/* The opt-in yaw-fitted pass: cm3d_lift_pass(desc), then cm3d_yaw_fit_boxes(desc, fit).  cm3d_lift_pass and cm3d_pipe_submit know
- * nothing of it. */
+/* The opt-in yaw-fitted pass: cm3d_lift_pass_opt (below) with only `yaw` set; a NULL `fit` is CM3D_ERR_ARG. */
 int cm3d_lift_pass_yaw_fitted(const cm3d_lift_pass_desc *desc, const cm3d_yaw_fit_desc *fit, cm3d_stream_t stream);
+
+/* ---- One pass with any of the opt-in stages, in one call ----
+ * Added within ABI v5: new symbols only, so CM3D_ABI_VERSION stays.  Host code (csrc/pass_options.cpp): no kernel of its own;
+ * cm3d_lift_pass and cm3d_pipe_submit know nothing of it. */
+typedef struct cm3d_rotated_nms_desc {     /* what cm3d_box_rotated_nms takes beyond the pass descriptor */
+    int64_t size;
+    const double *thr; int32_t n_thr, measure, class_agnostic, reserved;
+} cm3d_rotated_nms_desc;
+
+typedef struct cm3d_lift_pass_options {    /* NULL member: that stage is off */
+    int64_t size;
+    const cm3d_depth_cluster_desc *cluster;
+    const cm3d_stage2_filter_desc *filter;
+    const cm3d_yaw_fit_desc       *yaw;
+    const cm3d_rotated_nms_desc   *nms;
+} cm3d_lift_pass_options;
+
+/* Every pass with an opt-in stage: enqueues on `stream`, stopping at and returning the first error (a failed event call:
+ * CM3D_ERR_LAUNCH); NULL events are skipped; no descriptor of the caller's is written.  This is the only statement of a composed
+ * pass's order -- cm3d_amd.lifting.LiftEngine.run and the three single-option passes end here:
+ *
+ *   every present descriptor is checked first: `size` of opt, desc and each member; cluster's cl_off, cl_tile_off, cl_xyz, cl_status
+ *   (and cl_idx when desc has hit_idx); filter's medoid_pos_kept, on_road; yaw's tables and outputs as in cm3d_yaw_fit_boxes, and its
+ *   hit_xyz, hit_off, medoid_pos each NULL or what `yaw` below derives; nms's thr.  CM3D_ERR_ARG and NO call at all, whichever is bad
+ *   cluster ?  cm3d_lift_pass_head(desc); record cluster->ev[0]; cm3d_depth_cluster (desc's lists -> the cl_* arrays); record cluster->ev[1]
+ *              cm3d_lift_pass_tail(desc')            desc' = desc with hit_off, tile_off, hit_idx, hit_xyz = the cl_* arrays, tile_work = NULL
+ *           :  cm3d_lift_pass(desc)                  the plain pass, boxes of every mask included
+ *   filter  ?  record filter->ev[0]; cm3d_stage2_filter (centroid_g, medoid_pos, lane_dist ... of desc -> medoid_pos_kept, on_road);
+ *              record filter->ev[1]
+ *              cm3d_box_nms_bounded                  as in the plain pass, with medoid_pos_kept for medoid_pos: `box`, `flags` written anew
+ *   yaw     ?  cm3d_yaw_fit_boxes' sequence          lists = cluster ? cl_xyz, cl_off : desc's;  positions = filter ? medoid_pos_kept : desc's
+ *   nms     ?  cm3d_box_rotated_nms                  box, flags, mask_off ... of desc; waymo = pose_inv != NULL; bound as the box launch's
+ *   opt == NULL or every member NULL: exactly cm3d_lift_pass(desc) */
+int cm3d_lift_pass_opt(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, cm3d_stream_t stream);
 
 #ifdef __cplusplus
 }

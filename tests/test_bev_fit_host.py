@@ -1,4 +1,4 @@
-"""CPU: the host side of the yaw fit (cm3d_amd/bevfit.py, csrc/pass_yawfit.cpp).  The statement's axis against the true yaw of
+"""CPU: the host side of the yaw fit (cm3d_amd/bevfit.py, csrc/pass_options.cpp).  The statement's axis against the true yaw of
 noise-free two-face lists, within a bound that is derived and not measured; the statement against a separately written plain loop; the
 conditions the case tables of tests/bev_fit_cases.py must meet; YawFit's argument checks; the new descriptor's layout; and the call
 sequences of cm3d_lift_pass_yaw_fitted / cm3d_yaw_fit_boxes, traced over stubs by a stand-alone program built with the address and
@@ -14,7 +14,7 @@ import pytest
 
 from cm3d_amd import bevfit
 from tests import bev_fit_cases as cases
-from tests.test_pipe_sched_host import SANITIZED
+from tests import pass_options_trace as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -216,62 +216,32 @@ def test_new_symbols_within_abi_5_and_bad_descriptors_never_launch():
         assert fn(ctypes.byref(d), ctypes.byref(y), None) == -1                      # no tables, no outputs
 
 
+WAYMO_EVENTS = dict(ev=0x50, K=64, d0="0.1", mn="5,2.5", lmd="1.5", pose="pose_rt", pose_inv="pose_inv", bound=1024)
 SEQ_CASES = {
     "plain": dict(first=True),
     "boxes_alone": dict(first=False),
-    "waymo_events_own_lists": dict(first=True, events=True, lists="cl_xyz,cl_off", pos="kept", K=64, d0="0.1", mn="5,2.5", lmd="1.5", pose="pose_rt",
-                                   pose_inv="pose_inv", bound=1024),
+    "waymo_events": dict(first=True, **WAYMO_EVENTS),
+    # (lists of the caller's own: cm3d_yaw_fit_boxes alone takes them, a pass fits what it derives -- "own_lists_in_a_pass" below)
+    "waymo_events_own_lists": dict(first=False, lists="cl_xyz,cl_off", pos="kept", **WAYMO_EVENTS),
 }
 
 
-def _sequence(first, events=False, lists="hit_xyz,hit_off", pos="medoid_pos", K=128, d0="0.05", mn="20,1", lmd="0", pose="null", pose_inv="null",
-              bound=96):
-    return ((["cm3d_lift_pass size=ok n_masks=7"] if first else []) + (["record 0x50"] if events else [])
-            + [f"cm3d_bev_fit in={lists} n=7,4096 cs=set K={K} d0={d0} min={mn} out=set,set,set",
-               f"cm3d_yaw_select pos={pos} rest=set classes=10 dist=lane_dist,{lmd} lane=lane,lane_off,frame_lane,lane_idx n=2,900 pose={pose} "
-               "n=7,3 out=yaw_tab,yaw_idx,set"]
-            + (["record 0x51"] if events else [])
-            + [f"cm3d_box_nms_bounded pos={pos} lane=yaw_tab,tab_off,tab_frame,yaw_idx dist=lane_dist rest=set n=3,7,10 pose_inv={pose_inv} "
-               f"bound={bound} out=box,flags"])
-
-
-def test_yaw_fitted_pass_sequence_under_sanitizers(tmp_path):
-    """cm3d_lift_pass_yaw_fitted and cm3d_yaw_fit_boxes over stubs: the plain pass, the fit on the pass's lists (or the fit's own), the
-    selection on the pass's lane results, the events around those two, the box launch with the yaw table where the lane tables stood and
-    the real lane_dist; a descriptor of another size or a null table or output makes no call; and whichever call fails, the pass ends
-    there with that call's error."""
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    if shutil.which("g++") is None or not os.path.exists(os.path.join(rocm, "include", "hip", "hip_runtime_api.h")):
-        pytest.skip("no g++ or no HIP headers")
-    exe = tmp_path / "pass_yawfit_sim"
-    r = subprocess.run(SANITIZED + ["-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include"),
-                                    os.path.join(ROOT, "tests", "pass_yawfit_sim.cpp"), os.path.join(ROOT, "cm3d_amd", "csrc", "pass_yawfit.cpp"),
-                                    "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.endswith("pass_yawfit_sim done\n"), r.stdout + r.stderr
-    got = {}
-    for line in r.stdout.splitlines()[:-1]:
-        if line.startswith("case "):
-            calls, rc, fails = got.setdefault(line[5:], ([], [], []))
-        elif line.startswith("rc "):
-            rc.append(int(line[3:]))
-        elif line.startswith("fail "):
-            fails.append(tuple(int(x) for x in line.split()[1:]))
-        else:
-            calls.append(line)
-    refused = ["wrong_size", "wrong_size_boxes", "wrong_pass_size", "no_angle_cs", "no_fit_k", "no_fit_rect", "no_fit_status", "no_yaw_tab",
-               "no_yaw_idx", "no_yaw_src", "no_tab_off", "no_tab_frame", "null_pass", "null_fit"]
+def test_yaw_fitted_pass_sequence_under_sanitizers():
+    """cm3d_lift_pass_yaw_fitted and cm3d_yaw_fit_boxes over stubs (tests/pass_options_sim.cpp): the plain pass, the fit on the pass's
+    lists (cm3d_yaw_fit_boxes alone: or the fit's own), the selection on the pass's lane results, the events around those two, the box
+    launch with the yaw table where the lane tables stood and the real lane_dist; a descriptor of another size or a null table or
+    output makes no call, nor does a pass that is handed lists it does not derive itself; and whichever call fails, the pass ends there
+    with that call's error."""
+    got = T.group("yaw")
+    refused = ["wrong_size", "wrong_size_boxes", "wrong_pass_size", "wrong_pass_size_boxes", "no_angle_cs", "no_fit_k", "no_fit_rect",
+               "no_fit_status", "no_yaw_tab", "no_yaw_idx", "no_yaw_src", "no_tab_off", "no_tab_frame", "null_pass", "null_fit",
+               "null_fit_pass", "own_lists_in_a_pass"]
     for name in refused:
-        assert got.pop(name) == ([], [-1], []), name
+        T.assert_refused(got.pop(name), name)
     assert set(got) == set(SEQ_CASES)
-    code = {"cm3d_lift_pass": -2, "record": -2, "cm3d_bev_fit": -1, "cm3d_yaw_select": -3, "cm3d_box_nms_bounded": -2}
     for name, kw in SEQ_CASES.items():
-        calls, rc, fails = got[name]
-        assert calls == _sequence(**kw), name
-        assert rc == [0], name
-        want = [code[c.split()[0]] for c in calls]             # the stubs' own error codes: the pass hands the failing call's on
-        assert fails == [(k, want[k], k + 1) for k in range(len(calls))], name
+        kw = dict(kw)
+        T.assert_pass(got[name], (T.plain_sequence() if kw.pop("first") else []) + T.yaw_sequence(**kw), name)
 
 
 def test_pipeline_cpp_does_not_know_the_yaw_fitted_pass():

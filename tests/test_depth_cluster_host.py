@@ -1,4 +1,4 @@
-"""CPU: the host side of the depth clustering (cm3d_amd/cluster.py, csrc/pass_cluster.cpp).  The host statement -- sort by (range,
+"""CPU: the host side of the depth clustering (cm3d_amd/cluster.py, csrc/pass_options.cpp).  The host statement -- sort by (range,
 position), boundaries where neighbours lie more than eps apart -- against the O(n^2) connected components of "|ri - rj| <= eps" on the
 hand-written rows and the random recipe of tests/depth_cluster_cases.py; DepthCluster's argument checks; the new descriptor's layout;
 and the call sequence of cm3d_lift_pass_clustered, traced over stubs by a stand-alone program built with the address and
@@ -13,7 +13,7 @@ import pytest
 
 from cm3d_amd import cluster
 from tests import depth_cluster_cases as cases
-from tests.test_pipe_sched_host import SANITIZED
+from tests import pass_options_trace as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -137,52 +137,22 @@ def test_new_symbols_within_abi_5_and_bad_arguments_never_launch():
 
 
 CLUSTERED_CASES = {
-    "plain": dict(events=False, eps="1", mp=20, pick=0),
-    "events": dict(events=True, eps="0.5", mp=3, pick=1),
+    "plain": dict(eps="1", mp=20, pick=0),
+    "events": dict(ev=0x50, eps="0.5", mp=3, pick=1),
 }
 
 
-def _clustered_sequence(events, eps, mp, pick):
-    half = "{} size=ok hit_off={l} tile_off={l} hit_idx={l} hit_xyz={l} tile_work={tw} n_masks=7"
-    return ([half.format("cm3d_lift_pass_head", l="raw", tw="raw")] + (["record 0x50"] if events else [])
-            + [f"cm3d_depth_cluster in=raw,raw,raw frame=set n=7,4096,3 origin=set eps={eps} min={mp} pick={pick} out=cl,cl,cl,cl status=set ws=set,16"]
-            + (["record 0x51"] if events else []) + [half.format("cm3d_lift_pass_tail", l="cl", tw="null")])
-
-
-def test_clustered_pass_sequence_under_sanitizers(tmp_path):
-    """cm3d_lift_pass_clustered over stubs: the head on the raw lists, the clustering from the raw lists into the cl_* arrays, the tail
-    on the cl_* arrays with a null tile_work, the events around the clustering; a descriptor of another size, a null output or a null
-    pointer makes no call; and whichever call fails, the pass ends there with that call's error."""
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    if shutil.which("g++") is None or not os.path.exists(os.path.join(rocm, "include", "hip", "hip_runtime_api.h")):
-        pytest.skip("no g++ or no HIP headers")
-    exe = tmp_path / "pass_cluster_sim"
-    r = subprocess.run(SANITIZED + ["-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include"),
-                                    os.path.join(ROOT, "tests", "pass_cluster_sim.cpp"), os.path.join(ROOT, "cm3d_amd", "csrc", "pass_cluster.cpp"),
-                                    "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.endswith("pass_cluster_sim done\n"), r.stdout + r.stderr
-    got = {}
-    for line in r.stdout.splitlines()[:-1]:
-        if line.startswith("case "):
-            calls, rc, fails = got.setdefault(line[5:], ([], [], []))
-        elif line.startswith("rc "):
-            rc.append(int(line[3:]))
-        elif line.startswith("fail "):
-            fails.append(tuple(int(x) for x in line.split()[1:]))
-        else:
-            calls.append(line)
+def test_clustered_pass_sequence_under_sanitizers():
+    """cm3d_lift_pass_clustered over stubs (tests/pass_options_sim.cpp): the head on the raw lists, the clustering from the raw lists into
+    the cl_* arrays, the tail on the cl_* arrays with a null tile_work, the events around the clustering; a descriptor of another size,
+    a null output or a null pointer makes no call; and whichever call fails, the pass ends there with that call's error (the stubs
+    answer -2 for head, tail and events, -3 for the clustering)."""
+    got = T.group("cluster")
     for name in ("wrong_size", "no_cl_off", "no_cl_tile_off", "no_cl_idx", "no_cl_xyz", "no_cl_status", "null_pass", "null_cluster"):
-        assert got.pop(name) == ([], [-1], []), name
+        T.assert_refused(got.pop(name), name)
     assert set(got) == set(CLUSTERED_CASES)
     for name, kw in CLUSTERED_CASES.items():
-        calls, rc, fails = got[name]
-        assert calls == _clustered_sequence(**kw), name
-        assert rc == [0], name
-        # the stubs answer -2 (head, tail, events) and -3 (the clustering): the pass hands the failing call's own code on
-        want = [-3 if c.startswith("cm3d_depth_cluster") else -2 for c in calls]
-        assert fails == [(k, want[k], k + 1) for k in range(len(calls))], name
+        T.assert_pass(got[name], T.cluster_sequence(**kw), name)
 
 
 def test_pipeline_cpp_does_not_know_the_clustered_pass():

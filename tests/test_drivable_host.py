@@ -1,4 +1,4 @@
-"""CPU: the host side of the drivable-area test and of the stage-2 filters (cm3d_amd/drivable.py, csrc/pass_filter.cpp).  The y-slab
+"""CPU: the host side of the drivable-area test and of the stage-2 filters (cm3d_amd/drivable.py, csrc/pass_options.cpp).  The y-slab
 index and the walk the kernel makes through it, restated in numpy, against eval_detection.point_in_polygons on the cases of
 tests/drivable_cases.py; the index invariant; the filter rule on hand-written rows; the new descriptor's layout; and the call sequence
 of cm3d_lift_pass_filtered, traced over stubs by a stand-alone program built with the address and undefined-behaviour sanitizers."""
@@ -13,7 +13,7 @@ import pytest
 from cm3d_amd import drivable, eval_detection as ev
 from cm3d_amd.lifting import ClassTable
 from tests import drivable_cases as dc
-from tests.test_pipe_sched_host import SANITIZED
+from tests import pass_options_trace as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -177,50 +177,20 @@ def test_new_symbols_within_abi_5_and_bad_arguments_never_launch():
     assert L.cm3d_stage2_filter(*([None] * 6), 4, 1, *([None] * 7), 0, None, None, 10, 20.0, 4.0, None, None, None) == -1
 
 
-def _filtered_sequence(polygons=False, events=False, bound=32, pose=False, tables=0):
-    ev_ = lambda i: [f"record {0x40 + i:#x}"] if events else []
-    return (["cm3d_lift_pass size=ok"] + ev_(0)
-            + [f"cm3d_stage2_filter med=pass n=7,3,10 polygons={'set' if polygons else 'null'} tables={tables} "
-               f"needs_road={'set' if polygons else 'null'} thr=20,4 kept=kept on_road=set"] + ev_(1)
-            + [f"cm3d_box_nms_bounded med=kept bound={bound} pose_inv={'set' if pose else 'null'}"])
+FILTERED_CASES = {"lanes_only": dict(bound=32), "polygons": dict(polygons=True, tables=2, bound=32), "events": dict(ev=0x40, bound=32),
+                  "pose_planes": dict(bound=96, pose_inv="pose_inv"), "planes_32": dict(bound=1024, pose_inv="pose_inv")}
 
 
-FILTERED_CASES = {"lanes_only": {}, "polygons": dict(polygons=True, tables=2), "events": dict(events=True),
-                  "pose_planes": dict(bound=96, pose=True), "planes_32": dict(bound=1024, pose=True)}
-
-
-def test_filtered_pass_sequence_under_sanitizers(tmp_path):
-    """cm3d_lift_pass_filtered over stubs: the plain pass, the filter on the pass's medoid positions, the boxes again on the kept ones, in
-    that order and with the events around the filter; a descriptor of another size, one without outputs or a null pointer makes no
-    call; and whichever call fails, the pass ends there with that call's error."""
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    if shutil.which("g++") is None or not os.path.exists(os.path.join(rocm, "include", "hip", "hip_runtime_api.h")):
-        pytest.skip("no g++ or no HIP headers")
-    exe = tmp_path / "pass_filter_sim"
-    r = subprocess.run(SANITIZED + ["-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include"),
-                                    os.path.join(ROOT, "tests", "pass_filter_sim.cpp"), os.path.join(ROOT, "cm3d_amd", "csrc", "pass_filter.cpp"),
-                                    "-o", str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
-    assert r.returncode == 0 and r.stdout.endswith("pass_filter_sim done\n"), r.stdout + r.stderr
-    got = {}
-    for line in r.stdout.splitlines()[:-1]:
-        if line.startswith("case "):
-            calls, rc, fails = got.setdefault(line[5:], ([], [], []))
-        elif line.startswith("rc "):
-            rc.append(int(line[3:]))
-        elif line.startswith("fail "):
-            fails.append(tuple(int(x) for x in line.split()[1:]))
-        else:
-            calls.append(line)
-    for name in ("wrong_size", "no_output", "null_pass", "null_filter"):
-        assert got.pop(name) == ([], [-1], []), name
+def test_filtered_pass_sequence_under_sanitizers():
+    """cm3d_lift_pass_filtered over stubs (tests/pass_options_sim.cpp): the plain pass, the filter on the pass's medoid positions, the
+    boxes again on the kept ones, in that order and with the events around the filter; a descriptor of another size, one without
+    outputs or a null pointer makes no call; and whichever call fails, the pass ends there with that call's error."""
+    got = T.group("filter")
+    for name in ("wrong_size", "no_output", "no_on_road", "null_pass", "null_filter"):
+        T.assert_refused(got.pop(name), name)
     assert set(got) == set(FILTERED_CASES)
     for name, kw in FILTERED_CASES.items():
-        calls, rc, fails = got[name]
-        assert calls == _filtered_sequence(**kw), name
-        assert rc == [0], name
-        assert fails == [(k, -2, k + 1) for k in range(len(calls))], name
+        T.assert_pass(got[name], T.plain_sequence() + T.filter_sequence(**kw), name)
 
 
 def test_pipeline_cpp_and_the_kernels_do_not_know_the_filtered_pass():

@@ -18,7 +18,7 @@ from cm3d_amd import nms as nmsmod
 from tests import bev_fit_cases as fc
 from tests import optin_pass_cases as oc
 from tests import yaw_fit_pass_cases as yc
-from tests.test_gpu_optin_passes import _check_nms, _check_pass, _poison, _run, _same_bytes
+from tests.test_gpu_optin_passes import _check_nms, _check_pass, _poison, _run, _same_bytes, _sync_download
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -117,6 +117,87 @@ def test_yaw_fit_in_front_of_the_rotated_nms(oracle):
     assert took.sum() >= 10
     lane_only = _run(_engine(b, nms=r), b.hb)
     assert lane_only["box"][:, :9].tobytes() != both["box"][:, :9].tobytes()
+
+
+def _all_four(oracle, name):
+    """The batch, the four options and the CPU expectation of the pass with the first three (the rotated NMS judges what they wrote)."""
+    b = yc.batch(name)
+    c = clustermod.DepthCluster(1.0, 20)
+    f = oc.lane_filters(yc.expected_of(oracle, name, cluster=c))
+    front = yc.expected_of(oracle, name, cluster=c, filters=f)
+    return b, c, f, nmsmod.RotatedNms(class_agnostic=True), front, yc.fitted(oracle, b, front, Y)
+
+
+def _check_verdict_only(both, base):
+    """both: the pass with the rotated NMS, base: the same pass without.  Only bit 1 of flags and column 9 of box may differ."""
+    assert set(both) == set(base)
+    for key in base:
+        if key not in ("box", "flags"):
+            assert both[key].dtype == base[key].dtype and both[key].tobytes() == base[key].tobytes(), key
+    assert both["box"][:, :9].tobytes() == base["box"][:, :9].tobytes() and np.array_equal(both["flags"] & 1, base["flags"] & 1)
+    assert np.array_equal(both["box"][:, 9], both["flags"].astype(np.float64)) and set(np.unique(both["flags"]).tolist()) <= {0, 1, 3}
+
+
+@pytest.mark.parametrize("name", ["nusc", "waymo"])
+def test_all_four_options_in_one_pass(oracle, name):
+    """Clustering, filters, yaw fit and rotated NMS together: one cm3d_lift_pass_opt call.  The fit sees the clustered lists and the
+    kept positions, the rotated NMS the fitted boxes."""
+    b, c, f, r, front, exp = _all_four(oracle, name)
+    dropped = (front["medoid_pos"] >= 0) & (front["medoid_pos_kept"] < 0)
+    assert dropped.sum() >= 3 and not exp["yaw_src"][dropped].any() and exp["yaw_src"].any()
+    assert not np.array_equal(exp["fit_rect"], yc.fitted(oracle, b, yc.plain(oracle, name), Y)["fit_rect"])
+    if name == "nusc":
+        cpu_keep = oc.rotated_keep(exp["box"], exp["flags"], b.hb, r, b.classes)
+        assert (((exp["flags"] & 1) == 1) & (cpu_keep == 0)).sum() >= 1
+    three = _run(_engine(b, cluster=c, filters=f, yaw=Y), b.hb)
+    _check_fitted(b, three, exp, front)
+    eng = _engine(b, cluster=c, filters=f, yaw=Y, nms=r)
+    got = _run(eng, b.hb)
+    if name == "nusc":
+        took, keep = _check_nms(b.hb, got, three, r)
+        assert (took & (keep == 0)).sum() >= 1
+    else:                          # (the host statement of the decision reads nuScenes records: tests/test_gpu_rotated_nms.py has Waymo's)
+        _check_verdict_only(got, three)
+
+    def poison():
+        _poison(eng)
+        for k in ("fit_k", "fit_status", "yaw_src", "yaw_idx", "medoid_pos_kept"):
+            getattr(eng.b, k).fill_(-3)
+        eng.b.fit_rect.fill_(-3.0); eng.b.yaw_tab.fill_(-3.0); eng.b.on_road.fill_(7)
+    poison()
+    _same_bytes(_run(eng), got)
+    g = eng.capture_graph(masks="rle")
+    poison()
+    g.replay()
+    _same_bytes(_sync_download(eng), got)
+
+
+def test_pipeline_with_all_four_options_times_every_stage_and_reruns(oracle):
+    """submit(stage_events=) hands back the five events of the plain pass and a pair per opt-in stage, each where the header puts its
+    stage; a rerun gives the first pass's bytes and records into none of those events."""
+    import torch
+    from cm3d_amd import lifting
+    b, c, f, r, _, _ = _all_four(oracle, "nusc")
+    pipe = lifting.LiftPipeline("cuda:0", depth=2, classes=b.classes, cluster=c, filters=f, yaw=Y, nms=r)
+    ev = []
+    slot = pipe.submit(b.hb, "rle", stage_events=ev)
+    assert len(ev) == 11
+    first = pipe.collect(slot)[1]
+    torch.cuda.synchronize()
+    five, (f0, f1), (c0, c1), (y0, y1) = ev[:5], ev[5:7], ev[7:9], ev[9:11]
+    order = [five[0], five[1], c0, c1, five[2], five[3], five[4], f0, f1, y0, y1]
+    before = [a.elapsed_time(z) for a, z in zip(order, order[1:])]
+    assert min(before) >= 0.0
+    eng = pipe.engines[slot]
+    _poison(eng)
+    for k in ("fit_k", "fit_status", "yaw_src", "medoid_pos_kept"):
+        getattr(eng.b, k).fill_(-3)
+    torch.cuda.synchronize()                       # (the fills ran on another stream than the pass will)
+    pipe.rerun(slot)
+    again = pipe.collect(slot)[1]
+    torch.cuda.synchronize()
+    _same_bytes(first, again)
+    assert [a.elapsed_time(z) for a, z in zip(order, order[1:])] == before
 
 
 @pytest.mark.parametrize("name", ["nusc", "waymo"])
