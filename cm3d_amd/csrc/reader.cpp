@@ -4,6 +4,7 @@
 //   pool, straight into the caller's page-locked staging buffers here.
 // Plain C++17 + pthreads; no HIP, no Python.
 #include "../../include/cm3d_reader.h"
+#include "../../include/cm3d_reader_velocity.h"
 
 #include <atomic>
 #include <limits>
@@ -630,6 +631,16 @@ struct JP {
         p = end;
         return v;
     }
+    int64_t integer()                                           // an integer as the file holds it (a timestamp in microseconds: no double in between)
+    {
+        ws();
+        char *end = nullptr;
+        const long long v = strtoll(p, &end, 10);
+        if (end == p || end > e) { ok = false; return 0; }
+        if (end < e && (*end == '.' || *end == 'e' || *end == 'E')) return (int64_t)num();      // (written as a float after all)
+        p = end;
+        return (int64_t)v;
+    }
     bool boolean()
     {
         ws();
@@ -709,7 +720,7 @@ bool walk_table(const std::vector<uint8_t> &buf, Begin begin, Field field)
 struct PoseRow { std::string token; double t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0}; };
 struct CsRow { std::string token, sensor_tok; double t[3] = {0, 0, 0}, q[4] = {1, 0, 0, 0}, K[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; bool has_k = false; int channel = -1; };
 struct SdRow { std::string token, sample_tok, pose_tok, cs_tok, next_tok, filename; bool key = false; int sample = -1, pose = -1, cs = -1, next = -1; };
-struct SampleRow { std::string token, next_tok, scene_tok; int next = -1; int data[7] = {-1, -1, -1, -1, -1, -1, -1}; };   // [0] LIDAR_TOP, [1..6] CAM_LIST
+struct SampleRow { std::string token, next_tok, scene_tok; int next = -1; int64_t timestamp = 0; int data[7] = {-1, -1, -1, -1, -1, -1, -1}; };   // [0] LIDAR_TOP, [1..6] CAM_LIST
 struct SceneRow { std::string token, name, log_tok, first_tok; int first = -1, log = -1, nbr = 0; };
 struct NameRow { std::string token, value; };
 
@@ -764,7 +775,8 @@ extern "C" cm3d_tables *cm3d_tables_open(cm3d_reader *r, const char *dataroot, c
                     }); break;
                 case 1: ok = walk_table(buf, [&] { t->samples.emplace_back(); }, [&](JP &j, const std::string &k) {
                         SampleRow &s = t->samples.back();
-                        if (k == "token") s.token = j.str(); else if (k == "next") s.next_tok = j.str(); else if (k == "scene_token") s.scene_tok = j.str(); else j.skip();
+                        if (k == "token") s.token = j.str(); else if (k == "next") s.next_tok = j.str(); else if (k == "scene_token") s.scene_tok = j.str();
+                        else if (k == "timestamp") s.timestamp = j.integer(); else j.skip();
                     }); break;
                 case 2: ok = walk_table(buf, [&] { t->sds.emplace_back(); }, [&](JP &j, const std::string &k) {
                         SdRow &s = t->sds.back();
@@ -898,6 +910,18 @@ extern "C" int64_t cm3d_tables_job_tokens(const cm3d_tables *t, const char *cons
         }
     }
     return need;
+}
+
+extern "C" int cm3d_tables_sample_links(const cm3d_tables *t, const int32_t *rows, int32_t n, int32_t *next_row, int64_t *timestamp)
+{
+    if (!t || n < 0 || (n && (!rows || !next_row || !timestamp))) return CM3D_RD_ERR_ARG;
+    for (int i = 0; i < n; ++i)
+        if (rows[i] < 0 || rows[i] >= (int32_t)t->samples.size()) return CM3D_RD_ERR_ARG;
+    for (int i = 0; i < n; ++i) {
+        next_row[i] = t->samples[rows[i]].next;
+        timestamp[i] = t->samples[rows[i]].timestamp;
+    }
+    return CM3D_RD_OK;
 }
 
 namespace {
@@ -1183,6 +1207,11 @@ void py_float_repr(double x, std::string &out)
     }
 }
 
+// cm3d_write_results_json (vel == NULL) and cm3d_write_results_json_vel, whose comments state the arguments
+int64_t write_results_json(const double *records, const double *vel, int64_t n, const char *tokens, int32_t n_tokens,
+                           const char *const *cls_mid, const char *const *cls_score, const char *const *cls_tail, int32_t n_classes,
+                           const char *prefix, char *out, int64_t cap);
+
 }   // namespace
 
 // The text json.dump writes for the reference's result dict (:808-817, :929-930), straight from the gathered box records:
@@ -1195,6 +1224,27 @@ void py_float_repr(double x, std::string &out)
 extern "C" int64_t cm3d_write_results_json(const double *records, int64_t n, const char *tokens, int32_t n_tokens, const char *const *cls_mid,
                                            const char *const *cls_score, const char *const *cls_tail, int32_t n_classes, const char *prefix,
                                            char *out, int64_t cap)
+{
+    return write_results_json(records, nullptr, n, tokens, n_tokens, cls_mid, cls_score, cls_tail, n_classes, prefix, out, cap);
+}
+
+// The same with a velocity per record (include/cm3d_reader_velocity.h): vel double[n][2], row i beside records row i.  Behind the
+// rotation it writes '], "velocity": [vx, vy' itself and then cls_score[class], which here starts at the bracket that closes the
+// velocity ('], "detection_name": ...').
+extern "C" int64_t cm3d_write_results_json_vel(const double *records, const double *vel, int64_t n, const char *tokens, int32_t n_tokens,
+                                               const char *const *cls_mid, const char *const *cls_score, const char *const *cls_tail,
+                                               int32_t n_classes, const char *prefix, char *out, int64_t cap)
+{
+    static const double none[2] = {0.0, 0.0};                   // (n == 0: nothing reads it)
+    if (!vel && n) return 0;
+    return write_results_json(records, vel ? vel : none, n, tokens, n_tokens, cls_mid, cls_score, cls_tail, n_classes, prefix, out, cap);
+}
+
+namespace {
+
+int64_t write_results_json(const double *records, const double *vel, int64_t n, const char *tokens, int32_t n_tokens,
+                           const char *const *cls_mid, const char *const *cls_score, const char *const *cls_tail, int32_t n_classes,
+                           const char *prefix, char *out, int64_t cap)
 {
     if ((!records && n) || !tokens || n_tokens < 0 || !cls_mid || !cls_score || !cls_tail) return 0;
     try {
@@ -1227,6 +1277,10 @@ extern "C" int64_t cm3d_write_results_json(const double *records, int64_t n, con
                 py_float_repr(r[0], s); s += ", "; py_float_repr(r[1], s); s += ", "; py_float_repr(r[2], s);
                 s += cls_mid[ci];
                 py_float_repr(r[3], s); s += ", 0.0, 0.0, "; py_float_repr(r[4], s);
+                if (vel) {
+                    const double *v = vel + 2 * order[q];
+                    s += "], \"velocity\": ["; py_float_repr(v[0], s); s += ", "; py_float_repr(v[1], s);
+                }
                 s += cls_score[ci];
                 py_float_repr(r[7], s);
                 s += cls_tail[ci];
@@ -1241,3 +1295,5 @@ extern "C" int64_t cm3d_write_results_json(const double *records, int64_t n, con
         return 0;
     }
 }
+
+}   // namespace

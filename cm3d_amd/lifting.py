@@ -26,6 +26,7 @@ from .drivable import Stage2Filters  # noqa: F401  (LiftEngine(filters=Stage2Fil
 from .cluster import DepthCluster  # noqa: F401  (LiftEngine(cluster=DepthCluster(...)))
 from .bevfit import YawFit, angle_table  # noqa: F401  (LiftEngine(yaw=YawFit(...)))
 from .nms import RotatedNms  # noqa: F401  (LiftEngine(nms=RotatedNms(...)))
+from .velocity import Velocity, link_table  # noqa: F401  (LiftEngine(velocity=Velocity(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -142,6 +143,9 @@ class HostBatch:
     polygons: Optional[list] = None           # drivable-area polygon tables, one per lane table (eval_detection.load_drivable_polygons); only
                                               # an engine with Stage2Filters(drivable=True) reads them
     polygon_key: Optional[tuple] = None       # which polygon tables these are, from a caller that knows (else a checksum: polygon_tables_key)
+    frame_next: Optional[np.ndarray] = None   # (F,) int32 batch index of the same scene's following keyframe, -1 for none; with
+    frame_time: Optional[np.ndarray] = None   # (F,) float64 seconds since the batch's first frame (velocity.frame_times): only an engine
+                                              # with Velocity(...) reads them; None: that option cannot be enabled for this batch
     _lane_crc: Optional[tuple] = field(default=None, init=False, repr=False, compare=False)
 
     def lane_tables_key(self):
@@ -291,10 +295,23 @@ def frame_detections(frames, classes: ClassTable):
     return class_id, score, mask_cam, [list(fr.labels) for fr in frames], per_frame
 
 
+def frame_links(frames):
+    """(frame_next, frame_time) of frames that carry the sample table's `timestamp` (integer microseconds) and `next_token`
+    (nusc_io.scene_manifest, frames_of_scene): the batch index of every frame's follower -- -1 when it is not in the batch -- and the
+    seconds since the batch's first frame (velocity.frame_next_of, frame_times).  (None, None) for frames without them."""
+    from .velocity import frame_next_of, frame_times
+    stamps = [getattr(f, "timestamp", None) for f in frames]
+    if not stamps or any(t is None for t in stamps):
+        return None, None
+    return frame_next_of([f.token for f in frames], [getattr(f, "next_token", "") or "" for f in frames]), frame_times(stamps)
+
+
 def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane: Sequence[int],
-                classes: Optional[ClassTable] = None, layout: Optional[str] = None, keep_intensity: bool = True) -> HostBatch:
+                classes: Optional[ClassTable] = None, layout: Optional[str] = None, keep_intensity: bool = True,
+                frame_next=None, frame_time=None) -> HostBatch:
     """frames: objects with the attributes of cm3d_amd.synthetic.Frame.  layout: "rows" (the sweeps as they are) or
-    "quads" (rows_to_quads); None = default_layout().
+    "quads" (rows_to_quads); None = default_layout().  frame_next, frame_time: HostBatch's fields of those names (the velocity stage);
+    None: frame_links(frames).
     The masks of a batch may have different image sizes (Waymo's front and side cameras inside one frame, KITTI's frames among each
     other): the batch's `width`, `height` are the CANVAS -- the elementwise maximum over the frames' and the masks' sizes --, every run
     list stays as the producer wrote it, and `mask_wh` lists the masks' own sizes (None when they all have the canvas size)."""
@@ -302,6 +319,8 @@ def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane:
     layout = layout or default_layout()
     if layout not in ("rows", "quads"):
         raise ValueError(layout)
+    if frame_next is None and frame_time is None:
+        frame_next, frame_time = frame_links(frames)
     W = max([int(fr.width) for fr in frames] + [int(rl["size"][0]) for fr in frames for rl in fr.rles])
     H = max([int(fr.height) for fr in frames] + [int(rl["size"][1]) for fr in frames for rl in fr.rles])
     if W > 4096:
@@ -349,7 +368,9 @@ def pack_frames(frames: Sequence, lane_tables: Sequence[np.ndarray], frame_lane:
         class_id=class_id, score=score, detections_per_frame=per_frame, lane_tables=lane_tables, frame_lane=frame_lane,
         ego_xyz=[np.asarray(fr.ego_xyz, np.float64) for fr in frames], width=W, height=H, tokens=[fr.token for fr in frames], labels=labels,
         pose_rt=np.stack(pose_rt).astype(np.float32) if posed else None, pose_inv=np.stack(pose_inv).astype(np.float32) if posed else None,
-        ego_box=not (posed or all(getattr(f, "no_ego_box", False) for f in frames)))
+        ego_box=not (posed or all(getattr(f, "no_ego_box", False) for f in frames)),
+        frame_next=None if frame_next is None else np.asarray(frame_next, np.int32),
+        frame_time=None if frame_time is None else np.asarray(frame_time, np.float64))
 
 
 def require_one_mask_size(hb: HostBatch):
@@ -385,12 +406,14 @@ def pack_manifest(man, lane_tables, frame_lane, classes: Optional[ClassTable], r
         else:
             raw, row_off = rd.load_sweeps([p for m in man for p in m.sweep_paths], stride, alloc)
     class_id, score, mask_cam, labels, per_frame = frame_detections(man, classes)
+    frame_next, frame_time = frame_links(man)
     hb = assemble_batch(
         raw=raw, raw_stride=stride, intensity=intensity, frame_rows=frame_rows, sweep_row_off=row_off,
         sweep_xf=np.concatenate([np.asarray(m.sweep_xf, np.float32).reshape(-1, _lib.SWEEP_XF_STRIDE) for m in man], 0),
         frame_sweep_off=fso, cams=[m.cams for m in man], mask_off=fmo, mask_cam=mask_cam, mask_wh=wh, rle_counts=counts, rle_off=rle_off,
         class_id=class_id, score=score, detections_per_frame=per_frame, lane_tables=lane_tables, frame_lane=frame_lane,
-        ego_xyz=[m.ego_xyz for m in man], width=int(wh[0, 0]), height=int(wh[0, 1]), tokens=[m.token for m in man], labels=labels)
+        ego_xyz=[m.ego_xyz for m in man], width=int(wh[0, 0]), height=int(wh[0, 1]), tokens=[m.token for m in man], labels=labels,
+        frame_next=frame_next, frame_time=frame_time)
     return hb, list(range(len(man)))
 
 
@@ -426,7 +449,8 @@ class LiftEngine:
 
     def __init__(self, device="cuda:0", classes: Optional[ClassTable] = None, min_dist=MIN_DIST,
                  hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
-                 cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None):
+                 cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None,
+                 velocity: Optional[Velocity] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -444,7 +468,10 @@ class LiftEngine:
         `box` are decided again by the bird's-eye-view overlap of the boxes the pass wrote, everything else stays what the pass wrote.
         yaw: the yaw fit (bevfit.YawFit; nuScenes and Waymo batches -- KITTI's yaw comes from cm3d_obb), on the clustered lists and the
         kept positions where the engine has those.  download() adds `yaw_src`, `fit_status`, `fit_k` and `fit_rect`, and column 5 of
-        `box` holds the yaw that was used."""
+        `box` holds the yaw that was used.
+        velocity: the box velocity stage (velocity.Velocity; nuScenes batches, whose boxes are in the global frame): a call of its own
+        behind the pass (cm3d_box_velocity) associates the kept boxes of consecutive frames.  It needs batches with `frame_next` and
+        `frame_time`; download() adds `vel`, `vel_src`, `next_match` and `prev_match`.  None: no buffer, no call."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -460,6 +487,7 @@ class LiftEngine:
         self.cluster = cluster if cluster is not None and cluster.active else None
         self.nms = nms if nms is not None and nms.active else None
         self.yaw = yaw if yaw is not None and yaw.active else None
+        self.velocity = velocity if velocity is not None and velocity.active else None
         _verify_matrix_pipe(self.lib, self.dev)
         self.b = None
         self._lane = None                                    # the lane tables on the device and their spatial index (upload)
@@ -479,6 +507,7 @@ class LiftEngine:
         self.needs_road = torch.from_numpy(np.ascontiguousarray(self.classes.needs_road, np.int32)).to(d) if self.filters else None
         self.rot_thr = torch.from_numpy(self.nms.thr_by_group(self.classes)).to(d) if self.nms else None
         self.angle_cs = torch.from_numpy(angle_table(self.yaw.angles)).to(d) if self.yaw else None
+        self.vel_speed = torch.from_numpy(self.velocity.speed_by_group(self.classes)).to(d) if self.velocity else None
 
     # -- upload + allocation
     def upload(self, hb: HostBatch, dense_masks: Optional[torch.Tensor] = None):
@@ -592,6 +621,21 @@ class LiftEngine:
             b.fit_k = e(M); b.fit_status = e(M); b.fit_rect = e(M, _lib.MATCH_BOX_STRIDE, dtype=torch.float64)
             b.yaw_tab = e(M, 3, dtype=torch.float32); b.yaw_idx = e(M); b.yaw_src = e(M)
             b.yaw_tab_off = t(np.array([0, M], np.int32)); b.yaw_tab_frame = torch.zeros(F, dtype=torch.int32, device=d)
+        if self.velocity is not None:
+            if hb.frame_next is None or hb.frame_time is None:
+                raise ValueError("the velocity stage needs HostBatch.frame_next and frame_time (the batch was assembled without the "
+                                 "sample table's `next` and `timestamp`): it cannot be enabled for this batch")
+            if hb.pose_rt is not None:
+                raise ValueError("the velocity stage takes boxes in the global frame (nuScenes); this batch's are in the vehicle frame")
+            nxt, tim = _as(hb.frame_next, np.int32).reshape(-1), _as(hb.frame_time, np.float64).reshape(-1)
+            if nxt.size != F or tim.size != F:
+                raise ValueError("frame_next / frame_time: one entry per frame")
+            pair_off = link_table(hb.mask_off, nxt, tim, self.velocity.max_dt, M)[2]      # from the host's arrays alone: no read-back
+            b.frame_next, b.frame_time, b.vel_pair_off, b.vel_pairs = t(nxt), t(tim), t(pair_off), int(pair_off[-1])
+            b.next_match = e(M); b.prev_match = e(M); b.vel_src = e(M); b.vel = e(M, 2, dtype=torch.float64)
+            b.vel_status = torch.zeros(1, dtype=torch.int32, device=d)
+            b.vel_ws_bytes = int(L.cm3d_box_velocity_workspace_bytes(b.vel_pairs, M))
+            b.vel_ws = torch.empty(max(b.vel_ws_bytes, 16), dtype=torch.uint8, device=d)
         b.dense = dense_masks
         # The bulk data LAST: sweeps and run lengths come from page-locked staging buffers (cm3d_amd.reader) and copy
         # asynchronously; the small arrays above are pageable, their copies block the host until everything queued before them on
@@ -614,6 +658,7 @@ class LiftEngine:
             setattr(b.opts, name, ctypes.addressof(desc))
         b.timed = {name: desc for name, desc in stages.items() if name != "nms"}
         b.opts_ref = ctypes.byref(b.opts) if stages else None
+        b.plain_pass = not stages and self.velocity is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
         self.b = b
         return b
 
@@ -951,6 +996,15 @@ class LiftEngine:
                                             int(b.pose_inv is not None), min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), st),
               "cm3d_box_rotated_nms")
 
+    def stage_velocity(self, st):
+        """The opt-in velocity stage on the box rows and flags the pass (its rotated NMS included) left (cm3d_box_velocity)."""
+        b, v = self.b, self.velocity
+        check(self.lib.cm3d_box_velocity(_ptr(b.box), _ptr(b.flags), _ptr(b.mask_off), b.F, b.M, _ptr(b.class_id), _ptr(self.nms_group),
+                                         _ptr(self.vel_speed), len(self.classes.names), self.vel_speed.numel(), _ptr(b.frame_next),
+                                         _ptr(b.frame_time), v.max_dt, _ptr(b.vel_pair_off), b.F, b.vel_pairs, _ptr(b.next_match),
+                                         _ptr(b.prev_match), _ptr(b.vel), _ptr(b.vel_src), _ptr(b.vel_status), _ptr(b.vel_ws),
+                                         b.vel_ws_bytes, st), "cm3d_box_velocity")
+
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
     def run(self, masks="dense", project_events=None, stage_events=None):
@@ -973,6 +1027,8 @@ class LiftEngine:
         st = torch.cuda.current_stream(self.dev).cuda_stream
         check(self.lib.cm3d_lift_pass_opt(self.refresh_pass_descriptor(dense, project_events, marks, omarks), self.b.opts_ref, st),
               "cm3d_lift_pass_opt")
+        if self.velocity is not None:                    # behind the pass, on its final kept set: one more library call
+            self.stage_velocity(st)
 
     def capture_graph(self, masks="rle"):
         """Captures one pass over the resident batch into a HIP graph and returns it (`g.replay()` re-runs the pass
@@ -1023,6 +1079,12 @@ class LiftEngine:
             raise Cm3dError("a frame has too many masks or a cam_num is out of range")
         if s[0] & 8:
             raise Cm3dError("quad layout: a frame does not start on a multiple of 4 rows")
+        if self.velocity is not None:
+            v = int(self.b.vel_status.item())
+            if v & 1:
+                raise Cm3dError("velocity: a frame_next lies outside the batch")
+            if v & 2:
+                raise Cm3dError("velocity: pair_off disagrees with mask_off / frame_next, or a linked frame has too many masks")
         return s
 
     def removed_rows(self):
@@ -1059,6 +1121,8 @@ class LiftEngine:
                 out.update(cl_off=b.cl_off.cpu().numpy(), cl_status=b.cl_status.cpu().numpy())
             if self.yaw is not None:
                 out.update(self._yaw_results())
+            if self.velocity is not None:
+                out.update(self._velocity_results())
             return out
         n_rows, n_idx = int(s[1]), int(s[2])
         pt_off_rows = b.pt_off.cpu().numpy()
@@ -1090,7 +1154,14 @@ class LiftEngine:
                        cl_xyz=b.cl_xyz[:n_cl].cpu().numpy())
         if self.yaw is not None:
             out.update(self._yaw_results())
+        if self.velocity is not None:
+            out.update(self._velocity_results())
         return out
+
+    def _velocity_results(self):
+        b = self.b
+        return dict(vel=b.vel.cpu().numpy(), vel_src=b.vel_src.cpu().numpy(), next_match=b.next_match.cpu().numpy(),
+                    prev_match=b.prev_match.cpu().numpy())
 
     def _yaw_results(self):
         b = self.b
@@ -1204,7 +1275,7 @@ class LiftPipeline:
         eng = self.engines[slot]
         mode = masks or self.masks[slot]
         self._pin_if_captured()
-        if eng._lane["built"] and eng.b.opts_ref is None:     # (cm3d_pipe_submit knows only the plain pass)
+        if eng._lane["built"] and eng.b.plain_pass:     # (cm3d_pipe_submit knows only the plain pass)
             # (no stream context, no Python between the launches: what bench.py's headline times.  A pair of events around the
             # projection kernel rides along, so that a timed pass costs the host what an untimed one does)
             rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor(eng.resident_masks(mode), project_events))
@@ -1264,15 +1335,33 @@ def kept_box_records(b, frame_ids, device=None):
     return rec
 
 
-def nuscenes_boxes_from_records(rec, tokens, classes: Optional[ClassTable] = None):
+def kept_box_velocities(b):
+    """(k, 2) float64 velocities of the masks kept_box_records ships, in its order (an engine with Velocity(...); a device tensor)."""
+    return b.vel[(b.flags & 3) == 3].clone()
+
+
+def _velocity_rows(vel, n):
+    """The optional `vel` of the writers: None, or (n, 2) float64 rows beside the n records (kept_box_velocities)."""
+    if vel is None:
+        return None
+    vel = np.ascontiguousarray(vel, np.float64).reshape(-1, 2)
+    if vel.shape[0] != n:
+        raise ValueError(f"vel: {vel.shape[0]} rows for {n} records")
+    return vel
+
+
+def nuscenes_boxes_from_records(rec, tokens, classes: Optional[ClassTable] = None, vel=None):
     """Gathered records (numpy (k, 10), see kept_box_records) -> the reference's per-sample box dict lists (:808-817 after NMS
-    :913-924): {sample_token: [box, ...]} with every token of `tokens` present ([] when a sample has no box, :845)."""
+    :913-924): {sample_token: [box, ...]} with every token of `tokens` present ([] when a sample has no box, :845).
+    vel: None -- "velocity": [0, 0], the reference's constant --, or the records' (k, 2) velocities (kept_box_velocities): [vx, vy]."""
     classes = classes or ClassTable.nuscenes()
     results = {t: [] for t in tokens}
     # plain Python floats / ints in one go (tolist), per-class constants built once: the loop below only assembles dicts
     rows = np.asarray(rec, np.float64).reshape(-1, _lib.BOX_STRIDE).tolist()
+    vel = _velocity_rows(vel, len(rows))
+    vels = vel.tolist() if vel is not None else None
     sizes = [[float(v) for v in wlh] for wlh in classes.prior_wlh]
-    for r in rows:
+    for k, r in enumerate(rows):
         token, ci = tokens[int(r[REC_FRAME_A])], int(r[8])
         name = classes.names[ci]
         results[token].append({
@@ -1280,7 +1369,7 @@ def nuscenes_boxes_from_records(rec, tokens, classes: Optional[ClassTable] = Non
             "translation": [r[0], r[1], r[2]],
             "size": list(sizes[ci]),
             "rotation": [r[3], 0.0, 0.0, r[4]],
-            "velocity": [0, 0],
+            "velocity": [0, 0] if vels is None else vels[k],
             "detection_name": name,
             "detection_score": r[7],
             "attribute_name": ATTRIBUTE_NAMES[name],
@@ -1288,60 +1377,68 @@ def nuscenes_boxes_from_records(rec, tokens, classes: Optional[ClassTable] = Non
     return results
 
 
-def nuscenes_results_json(rec, tokens, classes: Optional[ClassTable] = None, meta=None):
-    """The text json.dumps({"meta": meta, "results": nuscenes_boxes_from_records(rec, tokens, classes)}) produces, written out
+def nuscenes_results_json(rec, tokens, classes: Optional[ClassTable] = None, meta=None, vel=None):
+    """The text json.dumps({"meta": meta, "results": nuscenes_boxes_from_records(rec, tokens, classes, vel)}) produces, written out
     directly from the records: same keys, key order, separators and float repr -- the writer of the reference (:929-930) without
     60 000 dicts and a generic encoder in between (tests/test_host_logic.py holds the two against each other)."""
     import json
     classes = classes or ClassTable.nuscenes()
     rows = np.asarray(rec, np.float64).reshape(-1, _lib.BOX_STRIDE).tolist()
+    vel = _velocity_rows(vel, len(rows))
+    vels = vel.tolist() if vel is not None else None
     tok_js = [json.dumps(t) for t in tokens]
     # everything of a box that only depends on its class, rendered once
     tail = []
     for ci, name in enumerate(classes.names):
         size = json.dumps([float(v) for v in classes.prior_wlh[ci]])
-        tail.append((size, f'"velocity": [0, 0], "detection_name": {json.dumps(name)}, "detection_score": ',
+        tail.append((size, f'"detection_name": {json.dumps(name)}, "detection_score": ',
                      f', "attribute_name": {json.dumps(ATTRIBUTE_NAMES[name])}}}'))
     per = [[] for _ in tokens]
     from math import isfinite
 
     def fr(x):                      # json's float text: repr, but Infinity / -Infinity / NaN for what repr calls inf / nan
         return float.__repr__(x) if isfinite(x) else json.dumps(x)
-    for r in rows:
+    for k, r in enumerate(rows):
         ti, ci = int(r[REC_FRAME_A]), int(r[8])
         size, mid, end = tail[ci]
         x, y, z, qw, qz, sc = r[0], r[1], r[2], r[3], r[4], r[7]
+        velocity = '"velocity": [0, 0], ' if vels is None else f'"velocity": [{fr(vels[k][0])}, {fr(vels[k][1])}], '
         if isfinite(x + y + z + qw + qz + sc):          # (a sum that overflows only sends a finite row down the careful branch)
             per[ti].append(f'{{"sample_token": {tok_js[ti]}, "translation": [{x!r}, {y!r}, {z!r}], "size": {size}, '
-                           f'"rotation": [{qw!r}, 0.0, 0.0, {qz!r}], {mid}{sc!r}{end}')
+                           f'"rotation": [{qw!r}, 0.0, 0.0, {qz!r}], {velocity}{mid}{sc!r}{end}')
         else:
             per[ti].append(f'{{"sample_token": {tok_js[ti]}, "translation": [{fr(x)}, {fr(y)}, {fr(z)}], "size": {size}, '
-                           f'"rotation": [{fr(qw)}, 0.0, 0.0, {fr(qz)}], {mid}{fr(sc)}{end}')
+                           f'"rotation": [{fr(qw)}, 0.0, 0.0, {fr(qz)}], {velocity}{mid}{fr(sc)}{end}')
     body = ", ".join(f'{tok_js[i]}: [{", ".join(b)}]' for i, b in enumerate(per))
     return f'{{"meta": {json.dumps(meta if meta is not None else {})}, "results": {{{body}}}}}', sum(len(b) for b in per)
 
 
-def nuscenes_results_json_native(rec, tokens, classes: Optional[ClassTable] = None, meta=None, part=None) -> bytes:
+def nuscenes_results_json_native(rec, tokens, classes: Optional[ClassTable] = None, meta=None, part=None, vel=None) -> bytes:
     """nuscenes_results_json through the native writer (libcm3d_reader.so, cm3d_write_results_json): the same bytes
     (tests/test_reader.py), without a Python statement per box -- 60 000 boxes take milliseconds instead of a third of a second.
     part = (first, count): only the entries of tokens[first:first+count] (records whose column 5 lies in that range), without the
     file's head and tail -- the entry point formats every batch's share while the later batches are still on the GPU and joins
-    the parts with ", " between nuscenes_results_json_head(meta) and b"}}"."""
+    the parts with ", " between nuscenes_results_json_head(meta) and b"}}".
+    vel: None, or the (k, 2) velocities of the k records (of the part's records, with `part`): written by the entry point beside
+    cm3d_write_results_json that takes them (cm3d_write_results_json_vel)."""
     import json
     from . import reader as rdmod
     classes = classes or ClassTable.nuscenes()
+    vel = _velocity_rows(vel, np.asarray(rec).reshape(-1, _lib.BOX_STRIDE).shape[0])
     mid, score, tail = [], [], []
     for ci, name in enumerate(classes.names):
         size = json.dumps([float(v) for v in classes.prior_wlh[ci]])
         mid.append(f'], "size": {size}, "rotation": [')
-        score.append(f'], "velocity": [0, 0], "detection_name": {json.dumps(name)}, "detection_score": ')
+        # (with velocities the writer itself puts '], "velocity": [vx, vy' in front of this piece)
+        score.append(('], "velocity": [0, 0' if vel is None else '') + f'], "detection_name": {json.dumps(name)}, "detection_score": ')
         tail.append(f', "attribute_name": {json.dumps(ATTRIBUTE_NAMES[name])}}}')
+    prefix = nuscenes_results_json_head(meta).decode()
     if part is not None:
         first, count = part
         rec = np.array(rec, np.float64).reshape(-1, _lib.BOX_STRIDE)
         rec[:, REC_FRAME_A] -= first
-        return rdmod.write_results_json(rec, [json.dumps(t) for t in tokens[first:first + count]], mid, score, tail, None)
-    return rdmod.write_results_json(rec, [json.dumps(t) for t in tokens], mid, score, tail, nuscenes_results_json_head(meta).decode())
+        tokens, prefix = tokens[first:first + count], None
+    return rdmod.write_results_json(rec, [json.dumps(t) for t in tokens], mid, score, tail, prefix, vel=vel)
 
 
 def nuscenes_results_json_head(meta=None) -> bytes:

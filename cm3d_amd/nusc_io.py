@@ -150,7 +150,9 @@ def scene_manifest(tables: NuscTables, scene, mask_dir, n_sweeps=3, ratio=0.64, 
             cams.append(rec)
         out.append(SimpleNamespace(token=sample["token"], sweep_paths=paths, sweep_xf=np.stack(xfs), cams=np.stack(cams), mask_path=mp,
                                    labels=list(data["labels"]), scores=list(data["detection_scores"]), cam_nums=list(data["cam_nums"]),
-                                   ego_xyz=np.asarray(key_pose["translation"], np.float64), ratio=ratio))
+                                   ego_xyz=np.asarray(key_pose["translation"], np.float64), ratio=ratio,
+                                   # the sample table's own links: what the opt-in velocity stage associates frames by
+                                   timestamp=sample.get("timestamp"), next_token=sample.get("next", "")))
     return out
 
 
@@ -170,7 +172,7 @@ def frames_of_scene(tables: NuscTables, scene, mask_dir, n_sweeps=3, ratio=0.64,
             W, H = int(1600 * ratio), int(900 * ratio)
         frames.append(SimpleNamespace(
             token=m.token, sweeps_raw=raws, sweep_xf=m.sweep_xf, cams=m.cams, rles=list(rles), labels=m.labels, scores=m.scores,
-            cam_nums=m.cam_nums, ego_xyz=m.ego_xyz, width=int(W), height=int(H)))
+            cam_nums=m.cam_nums, ego_xyz=m.ego_xyz, width=int(W), height=int(H), timestamp=m.timestamp, next_token=m.next_token))
     return frames
 
 

@@ -475,6 +475,38 @@ def rotated_nms(rec, score, group, frame_off, thr, measure="iou", class_agnostic
     return keep.cpu().numpy()
 
 
+def box_velocity(box, flags, mask_off, class_id, frame_next, frame_time, track_group, max_speed, max_dt=1.5, out=None):
+    """The opt-in velocity stage on arrays (cm3d_box_velocity; velocity.track_velocity_host states it): box (M, BOX_STRIDE) float64 and
+    flags (M,) as a pass left them, mask_off (F + 1,), class_id (M,), frame_next (F,), frame_time (F,) seconds, track_group per class,
+    max_speed per group.  out: optional dict of device tensors next_match, prev_match, vel_src (M,) int32 and vel (M, 2) float64 to
+    write into (else allocated).  Returns a dict of numpy arrays next_match, prev_match, vel, vel_src and `status` (int; the bits of the
+    header, not raised: a caller decides)."""
+    from . import velocity as velmod
+    L = _lib.lib()
+    box = np.asarray(box, np.float64).reshape(-1, _lib.BOX_STRIDE)
+    M = box.shape[0]
+    off = np.asarray(mask_off, np.int32).reshape(-1)
+    F = off.size - 1
+    nxt, tim = np.asarray(frame_next, np.int32).reshape(F), np.asarray(frame_time, np.float64).reshape(F)
+    grp, spd = np.asarray(track_group, np.int32).reshape(-1), np.asarray(max_speed, np.float64).reshape(-1)
+    pair_off = velmod.link_table(off, nxt, tim, float(max_dt), M)[2]
+    total = int(pair_off[-1])
+    d_box, d_flags = _t(box if M else np.zeros((1, _lib.BOX_STRIDE))), _t(np.asarray(flags, np.int32).reshape(M) if M else np.zeros(1, np.int32))
+    d_cls = _t(np.asarray(class_id, np.int32).reshape(M) if M else np.zeros(1, np.int32))
+    d_off, d_nxt, d_tim, d_grp, d_spd, d_pair = _t(off), _t(nxt), _t(tim), _t(grp), _t(spd), _t(pair_off)
+    o = out or {}
+    nm, pm, src = (o[k] if k in o else _e(max(M, 1)) for k in ("next_match", "prev_match", "vel_src"))
+    vel = o["vel"] if "vel" in o else _e(max(M, 1), 2, dtype=torch.float64)
+    status = torch.zeros(1, dtype=torch.int32, device=_dev())
+    ws = _ws(L.cm3d_box_velocity_workspace_bytes(total, M))
+    check(L.cm3d_box_velocity(d_box.data_ptr(), d_flags.data_ptr(), d_off.data_ptr(), F, M, d_cls.data_ptr(), d_grp.data_ptr(),
+                              d_spd.data_ptr(), grp.size, spd.size, d_nxt.data_ptr(), d_tim.data_ptr(), float(max_dt), d_pair.data_ptr(), F,
+                              total, nm.data_ptr(), pm.data_ptr(), vel.data_ptr(), src.data_ptr(), status.data_ptr(), ws.data_ptr(),
+                              ws.numel(), _st()), "cm3d_box_velocity")
+    return dict(next_match=nm.cpu().numpy()[:M], prev_match=pm.cpu().numpy()[:M], vel=vel.cpu().numpy().reshape(-1, 2)[:M], vel_src=src.cpu().numpy()[:M],
+                status=int(status.item()))
+
+
 # ----------------------------------------------------------------------------- f4: SAM3D fusion matching
 def match_records(boxes7):
     """(n,7) [center_x, center_y, bottom_z, length, width, height, heading] -> (n,6) float64 records of

@@ -22,6 +22,7 @@ from . import nms as nmsmod
 from . import bevfit
 from . import dist as cdist
 from . import lifting, nusc_io
+from . import velocity as velmod
 
 # module constants of the reference (:55-59)
 VER_NAME = "v1.0-trainval"
@@ -221,7 +222,8 @@ def _token_batches(batches, index, host_s):
         host_s = 0.0
 
 
-def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None, yaw=None):
+def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
+                  velocity=None, vel_out=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
@@ -230,8 +232,13 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
     time of their launch goes into the reference's "drivable" bucket.  cluster: the opt-in depth clustering (cluster.DepthCluster); its
     launches lie between the compaction's event and the medoid's, and their time goes into a "cluster" bucket instead of "medoid".
     nms: the opt-in rotated-box NMS (nms.RotatedNms); its launch lies behind the last event.  yaw: the opt-in yaw fit (bevfit.YawFit);
-    its two events come last, and the time between them goes into a "yawfit" bucket."""
+    its two events come last, and the time between them goes into a "yawfit" bucket.  velocity: the opt-in velocity stage
+    (velocity.Velocity), one call behind every pass; the (k, 2) velocities of the returned records (lifting.kept_box_velocities, same
+    order) are appended to the list `vel_out` as ONE device tensor, and on_records gets a batch's share as a fourth argument."""
     kw = {} if yaw is None else {"yaw": yaw}
+    if velocity is not None:
+        kw["velocity"] = velocity
+    vels = []
     pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms, **kw)
     n_f, n_c, n_y = (2 if filters is not None and filters.active else 0), (2 if cluster is not None else 0), (2 if yaw is not None else 0)
     n_evs = 5 + n_f + n_c + n_y
@@ -245,11 +252,14 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
             t1 = time.time()
             slot, ids, evs = pending.pop(0)
             records.append(pipe.collect_records(slot, ids))           # stays on the device until the one gather at the end
+            if velocity is not None:                                   # (the slot's stream has been synchronised)
+                vels.append(lifting.kept_box_velocities(pipe.engines[slot].b))
             spent("gpu lifting", t1)
             if on_records is not None:
                 first = int(ids[0, 0]) if len(ids) else 0
+                extra = () if velocity is None else (vels[-1].cpu().numpy(),)
                 if len(ids) and np.array_equal(ids[:, 0], np.arange(first, first + len(ids))):
-                    on_records(records[-1].cpu().numpy(), first, len(ids))
+                    on_records(records[-1].cpu().numpy(), first, len(ids), *extra)
                 else:
                     on_records(None, 0, 0)
             if len(evs) == n_evs:                                      # (complete: the slot's stream has been synchronised)
@@ -286,6 +296,8 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
         drain(0)
     finally:
         _release(segments)
+    if vel_out is not None and velocity is not None:
+        vel_out.append(torch.cat(vels, 0) if vels else torch.zeros(0, 2, dtype=torch.float64, device=device))
     if records:
         return torch.cat(records, 0)
     return torch.zeros(0, 10, dtype=torch.float64, device=device)
@@ -293,7 +305,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
 
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                 scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None,
-                cluster=None, nms=None, yaw=None):
+                cluster=None, nms=None, yaw=None, velocity=None, vel_out=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -326,7 +338,8 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
                 pool.terminate()
                 pool.join()
     with contextlib.closing(prepared()) as batches:
-        return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms, yaw=yaw)
+        return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms, yaw=yaw, velocity=velocity,
+                             vel_out=vel_out)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -392,6 +405,8 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
         class_id=man.class_id, score=man.score, detections_per_frame=[np.diff(man.frame_mask_off)], lane_tables=lanes, frame_lane=frame_lane,
         ego_xyz=man.ego_xyz, width=int(wh[0, 0]), height=int(wh[0, 1]),
         lane_key=(nt.dataroot, tuple(locs)))              # which lane tables these are: LiftEngine keeps their spatial index across batches
+    next_rows, stamps = nt.sample_links(man.sample_index)      # the sample table's `next` and `timestamp`: what lifting.Velocity reads
+    hb.frame_next, hb.frame_time = velmod.frame_next_of_rows(man.sample_index, next_rows), velmod.frame_times(stamps)
     if drivable:                                           # the same locations' polygons, cached like the lane tables
         _attach_polygons(hb, nt.dataroot, locs)
     if sub is not None:
@@ -401,7 +416,8 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
 
 
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
-                       scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None, yaw=None):
+                       scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
+                       velocity=None, vel_out=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -444,7 +460,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 hb, rows = got
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
-        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw)
+        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw, velocity, vel_out)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -478,10 +494,13 @@ def main(argv=None):
     clmod.add_arguments(ap)
     nmsmod.add_arguments(ap)
     bevfit.add_arguments(ap)
+    velmod.add_arguments(ap)
     args = ap.parse_args(argv)
     cluster = clmod.from_namespace(args)
     nms = nmsmod.from_args(args)
     yaw = bevfit.from_namespace(args)
+    velocity = velmod.from_args(args)
+    vel_mine = []                                  # with --velocity track: the velocities of this rank's records, one device tensor
     filters = lifting.Stage2Filters.from_args(args.drivable_filter, args.lane_max_dist, args.vehicle_lane_max_dist)
 
     total_start = time.time()
@@ -540,22 +559,23 @@ def main(argv=None):
                 item = write_q.get()
                 if item is None:
                     return
-                rec_np, first, count = item
+                rec_np, first, count, vel_np = item
                 t0 = time.time()
                 if rec_np is None or first != next_first[0]:
                     streamed[0] = False
                 elif streamed[0]:
-                    parts.append(lifting.nuscenes_results_json_native(rec_np, tokens, classes, None, part=(first, count)))
+                    parts.append(lifting.nuscenes_results_json_native(rec_np, tokens, classes, None, part=(first, count), vel=vel_np))
                     next_first[0] = first + count
                 timer["write"] += time.time() - t0
         writer = threading.Thread(target=write_worker, daemon=True)
         writer.start()
 
-        def on_records(rec_np, first, count):
-            write_q.put((rec_np, first, count))
+        def on_records(rec_np, first, count, vel_np=None):
+            write_q.put((rec_np, first, count, vel_np))
         mine = lift_scenes_native(nt, names[lo:hi], args.mask_dir, classes, device, row_to_out, args.n_sweeps, args.ratio, args.masks, timer,
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
-                                  on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms, yaw=yaw)
+                                  on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
+                                  velocity=velocity, vel_out=vel_mine)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
@@ -563,18 +583,21 @@ def main(argv=None):
         tokens = sample_tokens(tables, names)                  # the whole job's samples, identical on every rank
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
-                           token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms, yaw=yaw)
+                           token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
+                           velocity=velocity, vel_out=vel_mine)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.
     t0 = time.time()
     gathered = cdist.gather_records(mine, dst=0)
+    gathered_vel = cdist.gather_records(vel_mine[0], dst=0) if velocity is not None else None      # rank order is sample order here too
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
     if rank != 0:
         return 0
     rec = torch.cat([g.cpu() for g in gathered], 0).numpy()
+    vel = torch.cat([g.cpu() for g in gathered_vel], 0).numpy() if velocity is not None else None
     timer["gather"] = time.time() - t0
 
     # the writer (:929-930): the records straight to the text json.dump would produce for the reference's dict of box lists
@@ -585,9 +608,9 @@ def main(argv=None):
             if streamed[0]:
                 f.write(lifting.nuscenes_results_json_head(dict(META)) + b", ".join(parts) + b"}}")
             else:
-                f.write(lifting.nuscenes_results_json_native(rec, tokens, classes, dict(META)))
+                f.write(lifting.nuscenes_results_json_native(rec, tokens, classes, dict(META), vel=vel))
     else:
-        text, _ = lifting.nuscenes_results_json(rec, tokens, classes, dict(META))
+        text, _ = lifting.nuscenes_results_json(rec, tokens, classes, dict(META), vel=vel)
         with open(os.path.join(args.output_dir, args.output_name), "w") as f:
             f.write(text)
     timer["write"] += time.time() - t0

@@ -56,6 +56,10 @@ def lib():
         h.cm3d_manifest_load_masks.restype, h.cm3d_manifest_load_masks.argtypes = C.c_int, [p, p, p, i64, p, p, p, i32, p, p]
         h.cm3d_write_results_json.restype = i64
         h.cm3d_write_results_json.argtypes = [p, i64, C.c_char_p, i32, p, p, p, i32, C.c_char_p, p, i64]
+        # include/cm3d_reader_velocity.h
+        h.cm3d_tables_sample_links.restype, h.cm3d_tables_sample_links.argtypes = C.c_int, [p, p, i32, p, p]
+        h.cm3d_write_results_json_vel.restype = i64
+        h.cm3d_write_results_json_vel.argtypes = [p, p, i64, C.c_char_p, i32, p, p, p, i32, C.c_char_p, p, i64]
         _lib = h
     return _lib
 
@@ -303,6 +307,15 @@ class Tables:
         L.cm3d_tables_job_tokens(self.h, arr, len(names), buf, need, rows.ctypes.data, n)
         return [x.decode() for x in buf.raw[:need].split(b"\0")[:-1]], rows[:n]
 
+    def sample_links(self, rows):
+        """-> (row in sample.json of every given row's `next`, -1 for none, int32; their `timestamp`s in microseconds, int64)."""
+        rows = np.ascontiguousarray(rows, np.int32).reshape(-1)
+        nxt, ts = np.zeros(max(rows.size, 1), np.int32), np.zeros(max(rows.size, 1), np.int64)
+        rc = lib().cm3d_tables_sample_links(self.h, rows.ctypes.data, rows.size, nxt.ctypes.data, ts.ctypes.data)
+        if rc != 0:
+            raise ReaderError(rc, "cm3d_tables_sample_links")
+        return nxt[:rows.size], ts[:rows.size]
+
     def manifest(self, names, mask_dir, n_sweeps, ratio, class_names, missing_ok=False):
         return Manifest(self, names, mask_dir, n_sweeps, ratio, class_names, missing_ok)
 
@@ -430,18 +443,27 @@ class Manifest:
         raise ReaderError(rc, "cm3d_manifest_load_masks")
 
 
-def write_results_json(rec, tokens_json, cls_mid, cls_score, cls_tail, prefix):
+def write_results_json(rec, tokens_json, cls_mid, cls_score, cls_tail, prefix, vel=None):
     """The text of the reference's result file (json.dump of the dict of box lists, :929-930) from the gathered box records,
-    written natively (cm3d_write_results_json); see lifting.nuscenes_results_json for the Python form it must equal."""
+    written natively (cm3d_write_results_json); see lifting.nuscenes_results_json for the Python form it must equal.
+    vel: (n, 2) float64 velocities beside the records -- cm3d_write_results_json_vel, with cls_score as that entry point takes it."""
     L = lib()
     rec = np.ascontiguousarray(rec, np.float64).reshape(-1, 10)
+    if vel is not None:
+        vel = np.ascontiguousarray(vel, np.float64).reshape(-1, 2)
+        if vel.shape[0] != rec.shape[0]:
+            raise ReaderError(ERR_ARG, "cm3d_write_results_json_vel: one velocity per record")
     blob = b"".join(t.encode() + b"\0" for t in tokens_json)
     a, b, c = _paths(cls_mid), _paths(cls_score), _paths(cls_tail)
-    cap = int(rec.shape[0]) * 360 + len(blob) * 2 + len(prefix or "") + 256
+    cap = int(rec.shape[0]) * (360 if vel is None else 410) + len(blob) * 2 + len(prefix or "") + 256
     for _ in range(2):
         out = C.create_string_buffer(cap)
-        n = L.cm3d_write_results_json(rec.ctypes.data if rec.size else None, rec.shape[0], blob, len(tokens_json), a, b, c, len(cls_mid),
-                                      None if prefix is None else prefix.encode(), out, cap)
+        if vel is None:
+            n = L.cm3d_write_results_json(rec.ctypes.data if rec.size else None, rec.shape[0], blob, len(tokens_json), a, b, c, len(cls_mid),
+                                          None if prefix is None else prefix.encode(), out, cap)
+        else:
+            n = L.cm3d_write_results_json_vel(rec.ctypes.data if rec.size else None, vel.ctypes.data if vel.size else None, rec.shape[0], blob,
+                                              len(tokens_json), a, b, c, len(cls_mid), None if prefix is None else prefix.encode(), out, cap)
         if n > 0:
             return out.raw[:n]
         if n == 0:

@@ -910,8 +910,61 @@ typedef struct cm3d_lift_pass_options {    /* NULL member: that stage is off */
  *              cm3d_box_nms_bounded                  as in the plain pass, with medoid_pos_kept for medoid_pos: `box`, `flags` written anew
  *   yaw     ?  cm3d_yaw_fit_boxes' sequence          lists = cluster ? cl_xyz, cl_off : desc's;  positions = filter ? medoid_pos_kept : desc's
  *   nms     ?  cm3d_box_rotated_nms                  box, flags, mask_off ... of desc; waymo = pose_inv != NULL; bound as the box launch's
- *   opt == NULL or every member NULL: exactly cm3d_lift_pass(desc) */
+ *   opt == NULL or every member NULL: exactly cm3d_lift_pass(desc)
+ *   behind the pass, a call of the caller's own and no member of opt: cm3d_box_velocity (below) on desc's box, flags, mask_off, class_id */
 int cm3d_lift_pass_opt(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, cm3d_stream_t stream);
+
+/* ---- box velocity from frame-to-frame association (opt-in; nuScenes: boxes in the global frame) --------------------
+ * The reference writes "velocity": [0, 0] into every box (src/nuscenes/2d_to_3d.py:808-817).  This stage fills the field: the kept
+ * boxes of consecutive keyframes of a scene are associated one to one by the maximum-weight assignment of csrc/assign.h, and a box's
+ * velocity is the difference of matched centres over the difference of their frames' times.  It is a call of its own BEHIND the
+ * pass -- cm3d_lift_pass_opt(desc, opt, stream); cm3d_box_velocity(desc's box, flags, mask_off, class_id ..., stream) -- and so
+ * behind the rotated NMS when that is on: its input is the final kept set.  cm3d_lift_pass_options has no member for it.  Host
+ * statement to the bit: cm3d_amd.velocity.track_velocity_host.
+ *
+ *  box, flags  double[n_masks][CM3D_BOX_STRIDE], int32[n_masks] as the last box launch or the rotated NMS left them; a box is KEPT iff
+ *              (flags & 3) == 3; its centre is box[0], box[1]
+ *  mask_off    int32[F+1]; a frame's start is clamped to [0, n_masks] and its end to [start, n_masks] before use; a frame of more than
+ *              CM3D_MAX_MASKS_PER_FRAME masks takes part in no link (status bit 1)
+ *  class_id    int32[n_masks]; track_group int32[n_classes] (the entry points pass nms_group); max_speed double[n_groups], m/s.  A
+ *              class outside [0, n_classes) or a group outside [0, n_groups) never matches
+ *  frame_next  int32[F]: batch index of the same scene's following keyframe, or -1.  A value outside [-1, F) sets status bit 0 and
+ *              is read as -1.  No two frames may name the same follower
+ *  frame_time  double[F] seconds, formed on the host from the int64 microsecond timestamps minus the batch's smallest, times 1e-6
+ *  max_dt      seconds, > 0 (the max_time_diff of the devkit's box_velocity; 1.5 at the entry points); NaN or <= 0: CM3D_ERR_ARG
+ *
+ *  Links.   f -> n = frame_next[f] is a link iff n >= 0 and 0 < dt = frame_time[n] - frame_time[f] <= max_dt.
+ *  Weights. Rows are ALL masks of f, columns all masks of n, in mask order.  A pair has weight 0 unless both boxes are kept and
+ *           track_group of their classes is equal (= g).  Then, every operation rounded on its own, no fma:
+ *             dx = bn[0] - bf[0];  dy = bn[1] - bf[1];  d2 = (dx * dx) + (dy * dy);  gate = max_speed[g] * dt
+ *             gate > 0 and d2 <= gate * gate ?  r = sqrt(d2) / gate;  weight = r <= 1 ? 1 + (int)((1.0 - r) * (double)(ASSIGN_KMAX - 1)) : 0
+ *                                            :  weight = 0                  (ASSIGN_KMAX = 1000000; NaN compares false: weight 0)
+ *           float64 sqrt and / are correctly rounded on the host and on the device: the integers are the same bits.
+ *  Assign.  Maximum total weight, one to one, by AssignSolver's steps and tie rule (an unassigned column first, then the lowest
+ *           column), rows = the smaller side as in cm3d_bev_match.  An assigned pair is a match iff its weight is positive.
+ *  Velocity of mask i of frame f at time t, float64: p+, t+ the centre and frame time of next_match[i], p-, t- of prev_match[i]; the
+ *           first of   central (p+ - p-) / (t+ - t-),  forward (p+ - p) / (t+ - t),  backward (p - p-) / (t - t-)
+ *           whose matches exist and whose time span is <= max_dt; else (0.0, 0.0).  vel_src: 0 none, 1 forward, 2 backward, 3 central.
+ *           A mask that is not kept has no match and gets zeros and 0.
+ *
+ *  pair_off    int64[n_links+1], n_links == n_frames: link slot f holds the pairs of f -> frame_next[f],
+ *              pair_off[f+1] - pair_off[f] = M_f * M_n for a link and 0 otherwise, total_pairs = pair_off[n_links]: computed by the
+ *              host from mask_off, frame_next and frame_time alone (no read-back).  A slot that disagrees with what the device derives
+ *              from those arrays, or leaves [0, total_pairs], is skipped (status bit 1)
+ *  next_match, prev_match  int32[n_masks] OUT: batch mask index of the match in the following / preceding frame, or -1
+ *  vel double[n_masks][2], vel_src int32[n_masks] OUT.  The first launch initialises all four outputs: a rerun gives the same bytes
+ *  status      int32[1], zero it before the call; bits are only ever set
+ *  workspace   cm3d_box_velocity_workspace_bytes(total_pairs, n_masks): the int32 weights, the first link of every 256-pair block and
+ *              every mask's frame
+ *  Launches: k_track_init (outputs, every mask's frame), k_assign_block_owner, k_track_weight (one thread per pair),
+ *  k_track_assign<1, 2, 4, 16> (one wave per link; weights in LDS up to 8192 pairs, from L2 above), k_track_velocity (one thread per
+ *  mask).  Plain stores; the only atomic is the status word's. */
+int64_t cm3d_box_velocity_workspace_bytes(int64_t total_pairs, int32_t n_masks);
+int cm3d_box_velocity(const double *box, const int32_t *flags, const int32_t *mask_off, int32_t n_frames, int32_t n_masks,
+                      const int32_t *class_id, const int32_t *track_group, const double *max_speed, int32_t n_classes,
+                      int32_t n_groups, const int32_t *frame_next, const double *frame_time, double max_dt, const int64_t *pair_off,
+                      int32_t n_links, int64_t total_pairs, int32_t *next_match, int32_t *prev_match, double *vel, int32_t *vel_src,
+                      int32_t *status, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
 
 #ifdef __cplusplus
 }
