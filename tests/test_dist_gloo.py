@@ -56,6 +56,54 @@ def test_gather_records_world2():
     assert all(np.all(g[:, 9] == 3) for g in got)
 
 
+def _velocity_of(rec):
+    """The velocity rows the ranks ship beside their records: a known function of the records' column 5."""
+    c5 = rec[:, 5:6]
+    return torch.cat([0.25 * c5 + 1.0, -2.0 * c5], 1)
+
+
+def _worker_velocity(rank, world, port, q, counts):
+    sys.path.insert(0, ROOT)
+    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    from cm3d_amd import dist as cdist
+    r, w, _ = cdist.init_from_env(backend="gloo")
+    k, first = counts[r], sum(counts[:r])
+    # what pipeline_nuscenes.main gathers with --velocity track: the (k, 10) records, then the (k, 2) float64 velocities of the same rows
+    rec = torch.zeros(k, 10, dtype=torch.float64)
+    rec[:, 5] = torch.arange(first, first + k, dtype=torch.float64)
+    rec[:, 6], rec[:, 9] = float(r), 3.0
+    vel = _velocity_of(rec)
+    assert vel.shape == (k, 2) and vel.dtype == torch.float64
+    out, out_vel = cdist.gather_records(rec, dst=0), cdist.gather_records(vel, dst=0)
+    if r == 0:
+        q.put(([o.numpy() for o in out], [o.numpy() for o in out_vel]))
+    else:
+        assert out is None and out_vel is None
+    torch.distributed.barrier()
+    torch.distributed.destroy_process_group()
+
+
+@pytest.mark.parametrize("counts", [(0, 5), (4, 1)], ids=["rank0_empty", "both"])
+def test_gather_velocity_rows_beside_the_records_world2(counts):
+    """The second exchange of a --velocity track job: every rank's (k_r, 2) velocity rows follow its (k_r, 10) records; on rank 0 the
+    concatenated rows line up, and a rank without a box contributes (0, 2)."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker_velocity, args=(r, 2, port, q, counts)) for r in range(2)]
+    for p in procs:
+        p.start()
+    recs, vels = q.get(timeout=120)
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    assert [r.shape for r in recs] == [(k, 10) for k in counts] and [v.shape for v in vels] == [(k, 2) for k in counts]
+    assert all(v.dtype == np.float64 for v in vels)
+    rec, vel = np.concatenate(recs, 0), np.concatenate(vels, 0)
+    assert np.array_equal(rec[:, 5], np.arange(sum(counts))) and np.array_equal(rec[:, 6], np.repeat([0.0, 1.0], counts))
+    assert vel.tobytes() == _velocity_of(torch.from_numpy(rec)).numpy().tobytes()          # row i of the velocities belongs to record i
+
+
 def test_single_process_passthrough():
     from cm3d_amd import dist as cdist
     t = torch.zeros(3, 10, dtype=torch.float64)

@@ -79,6 +79,91 @@ def test_bad_frame_next_changes_only_the_status(host):
     assert (bad["next_match"] >= 0).sum() == 2                     # the other scene's link is there
 
 
+def test_over_capacity_sets_the_status_and_leaves_the_third_scene_alone(host):
+    """(the parametrised test above holds the case to the host statement with guard words; this one says what the case is)"""
+    from cm3d_amd import ops
+    case = vc.by_name("over_capacity")
+    got = ops.box_velocity(*vc.args_of(case))
+    m4 = int(case["mask_off"][4])
+    assert got["status"] == 2 and (got["next_match"][:m4] == -1).all() and (got["prev_match"][:m4] == -1).all()
+    assert (got["next_match"][m4:] >= 0).sum() == 3 and not got["vel_src"][:m4].any()
+
+
+WS_GUARD = 4096                 # bytes behind the workspace the call is told of
+
+
+def _raw_call(case, pair_off, total_pairs):
+    """cm3d_box_velocity through ctypes with a pair_off and a total_pairs of the caller's choosing, the workspace sized by that total:
+    (outputs as numpy, status).  Asserts the guard words around the four outputs and the guard bytes behind the workspace."""
+    import torch
+    from cm3d_amd import _lib
+    L = _lib.lib()
+    M, F = len(case["flags"]), len(case["mask_off"]) - 1
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
+    d = {k: t(case[k]) for k in ("box", "flags", "mask_off", "class_id", "track_group", "max_speed", "frame_next", "frame_time")}
+    d_pair = t(np.asarray(pair_off, np.int64))
+    bufs = _guarded(M)
+    for _, view in bufs.values():
+        view.fill_(42)
+    status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ws_bytes = int(L.cm3d_box_velocity_workspace_bytes(int(total_pairs), M))
+    ws = torch.full((ws_bytes + WS_GUARD,), 0xA5, dtype=torch.uint8, device="cuda")
+    rc = L.cm3d_box_velocity(d["box"].data_ptr(), d["flags"].data_ptr(), d["mask_off"].data_ptr(), F, M, d["class_id"].data_ptr(),
+                             d["track_group"].data_ptr(), d["max_speed"].data_ptr(), case["track_group"].size, case["max_speed"].size,
+                             d["frame_next"].data_ptr(), d["frame_time"].data_ptr(), float(case["max_dt"]), d_pair.data_ptr(), F,
+                             int(total_pairs), bufs["next_match"][1].data_ptr(), bufs["prev_match"][1].data_ptr(), bufs["vel"][1].data_ptr(),
+                             bufs["vel_src"][1].data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes, torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    assert rc == 0
+    _guards_intact(bufs, M)
+    assert (ws[ws_bytes:].cpu().numpy() == 0xA5).all()
+    out = {k: v[1].cpu().numpy() for k, v in bufs.items()}
+    out["vel"] = out["vel"].reshape(-1, 2)
+    return out, int(status.item())
+
+
+@pytest.mark.parametrize("variant", ["slot_claims_too_many", "total_ends_inside_the_last_slot"])
+def test_a_slot_that_disagrees_loses_its_link_and_nothing_else(variant):
+    """pair_off comes from the caller.  A slot that does not hold exactly M_f * M_n pairs inside [0, total_pairs] sets status bit 1 and
+    holds no match; every other output byte is the host statement of the batch without that link.  pair_off stays monotone: the header
+    promises nothing for overlapping slots."""
+    case = vc.by_name("three_link_chain")
+    pair_off = V.link_table(case["mask_off"], case["frame_next"], case["frame_time"], case["max_dt"])[2]
+    assert pair_off.tolist() == [0, 30, 54, 82, 82]
+    if variant == "slot_claims_too_many":          # slot 1 claims 7 pairs too many; the slots behind it are shifted but consistent
+        bad, total = 1, int(pair_off[-1]) + 7
+        pair_off = pair_off + np.array([0, 0, 7, 7, 7])
+    else:                                          # the total ends inside the last link's slot
+        bad, total = 2, int(pair_off[2]) + 10
+    assert (np.diff(pair_off) >= 0).all()
+    got, status = _raw_call(case, pair_off, total)
+    nxt = case["frame_next"].copy()
+    nxt[bad] = -1
+    exp = V.track_velocity_host(*vc.args_of(dict(case, frame_next=nxt)))
+    whole = V.track_velocity_host(*vc.args_of(case))
+    assert status & 2 and exp["status"] == 0
+    f0, f1 = int(case["mask_off"][bad]), int(case["mask_off"][bad + 1])
+    assert (whole["next_match"][f0:f1] >= 0).any() and (got["next_match"][f0:f1] == -1).all()
+    for k in ("next_match", "prev_match", "vel_src", "vel"):
+        assert got[k].tobytes() == exp[k].tobytes(), k
+    assert (got["next_match"] >= 0).sum() == (exp["next_match"] >= 0).sum() >= 7         # the other two links are there
+
+
+@pytest.mark.parametrize("pair", vc.clamp_cases(), ids=[c["name"] for c, _ in vc.clamp_cases()])
+def test_mask_off_is_read_clamped(pair):
+    """A last mask_off entry far beyond the masks, a negative first one: every frame's range is clamped into [0, M] before it indexes
+    anything, so the outputs are the host statement on the clamped offsets and the guard words stand."""
+    from cm3d_amd import ops
+    raw, clamped = pair
+    M = len(raw["flags"])
+    exp = V.track_velocity_host(*vc.args_of(clamped))
+    bufs = _guarded(M)
+    got = ops.box_velocity(*vc.args_of(raw), out={k: v[1] for k, v in bufs.items()})
+    _assert_equal(got, exp)
+    _guards_intact(bufs, M)
+    assert got["status"] == 0 and (got["next_match"] >= 0).sum() == 4
+
+
 def test_argument_errors_return_before_any_launch():
     """Negative counts, a wrong link count, a bad max_dt: CM3D_ERR_ARG; a workspace one byte short: CM3D_ERR_WORKSPACE.  The outputs
     keep their poison: nothing was launched."""

@@ -163,16 +163,9 @@ def test_pipeline_rerun_and_kept_velocities(tracked):
 
 # ------------------------------------------------------------------------------------------------ the entry point
 def _write_dataset(tmp_path, monkeypatch):
-    """The moving scenes in the reference's on-disk formats: nusc_io.write_synthetic_dataset with velocity_pass_cases.moved_frame for
-    its frames (timestamps 500000 * f, as the writer sets them) and the one-yaw lane table for both map locations."""
-    from cm3d_amd import nusc_io, synthetic as syn
-    real = syn.make_frame
-    monkeypatch.setattr(syn, "make_frame", lambda cfg, index: pc.moved_frame(real(cfg, 1000 * (index // 1000)), index // 1000, index % 1000))
-    dataroot, mask_dir, names = nusc_io.write_synthetic_dataset(str(tmp_path), pc.config(), n_scenes=2, frames_per_scene=pc.FRAMES_PER_SCENE)
-    monkeypatch.undo()
-    for s in range(2):
-        np.save(os.path.join(dataroot, "lanes", f"synthtown-{s}.npy"), pc.lane_table())
-    return dataroot, mask_dir, names
+    """The two moving scenes in the reference's on-disk formats (velocity_pass_cases.write_dataset), the one-yaw lane table for both
+    map locations."""
+    return pc.write_dataset(tmp_path, n_scenes=2)
 
 
 def _entry_point(dataroot, mask_dir, out_dir, *flags):

@@ -72,6 +72,9 @@ def _plain(box, flags, mask_off, class_id, frame_next, frame_time, track_group, 
             continue
         f0, n0 = mask_off[f], mask_off[n]
         P, G = mask_off[f + 1] - f0, mask_off[n + 1] - n0
+        if P > 1024 or G > 1024:                   # CM3D_MAX_MASKS_PER_FRAME: the solver's capacity; no link, status bit 1
+            status |= 2
+            continue
         W = [[0] * G for _ in range(P)]
         for a in range(P):
             for b in range(G):
@@ -180,6 +183,41 @@ def test_every_family_is_exercised(host):
     assert {0, 1, 2, 3} <= set(np.concatenate([r["vel_src"] for r in host.values()]).tolist())
     assert host["frame_next_out_of_range_7"]["status"] == 1 and host["two_scenes"]["status"] == 0
     assert 0 not in host["dt_one_ulp_above_max_dt"]["weights"] and 0 in host["dt_exactly_max_dt"]["weights"]
+
+
+def test_a_frame_beyond_the_capacity_takes_its_link_out_and_no_other(host):
+    """1025 masks on either side of a link: status bit 1, the slot holds no pair, none of its masks gets a match or a velocity; the
+    third scene's link of 5 x 4 masks is the one of the same batch without the two scenes in front."""
+    from cm3d_amd import _lib
+    case, res = vc.by_name("over_capacity"), host["over_capacity"]
+    assert max(max(c) for c in vc.OVER_CAPACITY_COUNTS) == _lib.MAX_MASKS_PER_FRAME + 1
+    off = case["mask_off"]
+    assert np.diff(off).tolist() == [n for pair in vc.OVER_CAPACITY_COUNTS for n in pair]
+    assert res["status"] == 2 and res["pair_off"].tolist() == [0, 0, 0, 0, 0, 20, 20] and list(res["weights"]) == [4]
+    m4 = int(off[4])
+    for k in ("next_match", "prev_match"):
+        assert (res[k][:m4] == -1).all(), k
+    assert not res["vel_src"][:m4].any() and not res["vel"][:m4].any()
+    assert (res["next_match"][m4:] >= 0).sum() == 3 and (res["next_match"][m4:][res["next_match"][m4:] >= 0] >= off[5]).all()
+    alone = dict(case, box=case["box"][m4:], flags=case["flags"][m4:], class_id=case["class_id"][m4:], mask_off=off[4:] - m4,
+                 frame_next=np.array([1, -1], np.int32), frame_time=case["frame_time"][4:])
+    lone = V.track_velocity_host(*vc.args_of(alone))
+    assert lone["status"] == 0 and np.array_equal(np.where(lone["next_match"] >= 0, lone["next_match"] + m4, -1), res["next_match"][m4:])
+    assert lone["vel"].tobytes() == res["vel"][m4:].tobytes() and np.array_equal(lone["vel_src"], res["vel_src"][m4:])
+
+
+@pytest.mark.parametrize("pair", vc.clamp_cases(), ids=[c["name"] for c, _ in vc.clamp_cases()])
+def test_mask_off_is_read_clamped(pair):
+    """A mask_off entry outside [0, M] is read as the nearest bound: the statement on the raw offsets is the statement on the clamped
+    ones, byte for byte."""
+    raw, clamped = pair
+    M = len(raw["flags"])
+    assert not np.array_equal(raw["mask_off"], clamped["mask_off"])
+    assert np.array_equal(np.clip(raw["mask_off"], 0, M), clamped["mask_off"]) and (np.diff(clamped["mask_off"]) >= 0).all()
+    a, b = V.track_velocity_host(*vc.args_of(raw)), V.track_velocity_host(*vc.args_of(clamped))
+    for k in ("next_match", "prev_match", "vel_src", "vel", "pair_off"):
+        assert a[k].tobytes() == b[k].tobytes(), k
+    assert a["status"] == b["status"] == 0 and (a["next_match"] >= 0).sum() == 4
 
 
 def test_the_greedy_case_differs_from_greedy(host):

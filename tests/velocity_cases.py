@@ -2,10 +2,11 @@
 
 A case is the argument set of velocity.track_velocity_host / ops.box_velocity as a dict (box, flags, mask_off, class_id, frame_next,
 frame_time, track_group, max_speed, max_dt) plus `name` and, where the answer is known in closed form, `expect` (a dict of the outputs
-that are pinned).  Four families:
+that are pinned).  Five families, and the clamp pairs (clamp_cases) beside them:
 
   links     the last frame of a scene; two scenes in one batch; dt exactly max_dt and one ulp above; dt <= 0; a middle frame without a
-            kept box; a frame_next out of range
+            kept box; a frame_next out of range; a chain of three links
+  capacity  a frame of 1025 masks on either side of a link
   weights   group mismatch; a box that is not kept on either side; d2 == gate^2 exactly and one ulp outside; identical centres;
             global-magnitude coordinates
   assign    a pair of mutual nearest neighbours the optimum separates; a "domino" chain (tests/assign_cases.py); an all-equal matrix;
@@ -88,7 +89,52 @@ def link_cases():
                          [0.0, 0.5, 9.0, 9.5],
                          expect=dict(status=1, next_match=[-1, -1, -1, -1, 6, 7, -1, -1], prev_match=[-1] * 6 + [4, 5],
                                      vel_src=[0, 0, 0, 0, 1, 1, 2, 2])))
+    out.append(chain_case())
     return out
+
+
+CHAIN_COUNTS = (5, 6, 4, 7)
+
+
+def chain_case():
+    """0 -> 1 -> 2 -> 3: three links in the slots 0, 1, 2 (pair_off 0, 30, 54, 82, 82), boxes 64 m apart (gate: 20 m) that move by
+    (1, 0.5) a frame; frame k shows the first CHAIN_COUNTS[k] of them, one of frame 1 is not kept.  The batch of the tests that hand
+    cm3d_box_velocity a pair_off that disagrees with it."""
+    p = np.array([[64.0 * i, 8.0 * (i % 3)] for i in range(max(CHAIN_COUNTS))]) + [900.0, 1800.0]
+    frames = [(p[:n] + k * np.array([1.0, 0.5]), 0, 3) for k, n in enumerate(CHAIN_COUNTS)]
+    frames[1] = (frames[1][0], 0, [3, 3, 1, 3, 3, 3])
+    return _case("three_link_chain", frames, [1, 2, 3, -1], [0.0, 0.5, 1.0, 1.5],
+                 expect=dict(pair_off=[0, 30, 54, 82, 82], next_match=[5, 6, -1, 8, 9] + [11, 12, -1, 14, -1, -1] + [15, 16, 17, 18] + [-1] * 7,
+                             vel_src=[1, 1, 0, 1, 1] + [3, 3, 0, 3, 2, 0] + [3, 3, 1, 3] + [2, 2, 2, 2, 0, 0, 0]))
+
+
+# ------------------------------------------------------------------------------------------------------------- capacity
+OVER_CAPACITY_COUNTS = [(1025, 3), (3, 1025), (5, 4)]
+
+
+def capacity_cases():
+    """Three two-frame scenes; the first two hold a frame of 1025 masks, one more than CM3D_MAX_MASKS_PER_FRAME, on either side of
+    their link: status bit 1, no pair in their slots, no match; the third scene's link is untouched."""
+    rng = np.random.default_rng(11)
+    frames = [fr for P, G in OVER_CAPACITY_COUNTS for fr in _scatter_link(rng, P, G)]
+    n = len(OVER_CAPACITY_COUNTS)
+    times = np.repeat(np.arange(n) * 30.0, 2) + np.tile([0.0, 0.5], n)
+    return [_case("over_capacity", frames, _pairs_of_scenes(n), times, max_speed=[8.0, 6.0, 4.0],
+                  expect=dict(status=2, pair_off=[0, 0, 0, 0, 0, 20, 20]))]
+
+
+# ---------------------------------------------------------------------------------------------------------------- clamp
+def clamp_cases():
+    """(case, the same case with mask_off as the rule reads it) pairs: a mask_off whose last entry lies beyond the masks, one whose
+    first entry is negative.  Every frame's range is clamped into [0, M] (velocity._frame_masks, track_frame_masks), so each is the
+    batch `two_scenes` -- whose first and last frame are both part of a link -- with mask_off = 0, 2, 4, 6, 8.  Not members of
+    all_cases(): the plain loop of test_velocity_host takes mask_off as it stands."""
+    base = by_name("two_scenes")
+    M = len(base["flags"])
+    hi, lo = base["mask_off"].copy(), base["mask_off"].copy()
+    hi[-1], lo[0] = M + 1000, -5
+    return [(dict(base, name="mask_off_last_beyond", mask_off=hi, expect={}), base),
+            (dict(base, name="mask_off_first_negative", mask_off=lo, expect={}), base)]
 
 
 # -------------------------------------------------------------------------------------------------------------- weights
@@ -187,7 +233,7 @@ def velocity_cases():
 
 @functools.lru_cache(maxsize=None)
 def all_cases():
-    cases = link_cases() + weight_cases() + assign_cases() + velocity_cases()
+    cases = link_cases() + weight_cases() + assign_cases() + velocity_cases() + capacity_cases()
     assert len({c["name"] for c in cases}) == len(cases)
     return cases
 

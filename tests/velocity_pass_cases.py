@@ -34,10 +34,11 @@ T0_US = 1533151603547590                        # a nuScenes-sized timestamp
 
 
 def moved_frame(base, s, k, vel=VELOCITY):
-    """Frame k of scene s: `base` with every ego translation rebased to EGO0 and moved by k * DT * vel[s] (x, y only)."""
+    """Frame k of scene s: `base` with every ego translation rebased to EGO0 and moved by k * DT * vel[s % len(vel)] (x, y only)."""
     delta = (EGO0 - np.asarray(base.sweep_xf[0][21:23], np.float64)).astype(np.float32)      # the rebase: one float32 vector
-    step = (k * DT * np.asarray(vel[s], np.float64)).astype(np.float32)
-    assert np.array_equal(step.astype(np.float64), k * DT * np.asarray(vel[s], np.float64))
+    v = np.asarray(vel[s % len(vel)], np.float64)          # scenes beyond the table take its rows in turn: even ones move, odd ones stand
+    step = (k * DT * v).astype(np.float32)
+    assert np.array_equal(step.astype(np.float64), k * DT * v)
     xf, cams = np.array(base.sweep_xf, np.float32), np.array(base.cams, np.float32)
     xf[:, 21:23] = (xf[:, 21:23] + delta) + step
     cams[:, 0:2] = (cams[:, 0:2] - delta) - step
@@ -51,16 +52,18 @@ def moved_frame(base, s, k, vel=VELOCITY):
     return fr
 
 
-def lane_table():
-    """Lane points on a 4 m grid around EGO0, all with the yaw LANE_YAW."""
+def lane_table(yaw=LANE_YAW):
+    """Lane points on a 4 m grid around EGO0, all with the yaw `yaw`."""
     g = np.arange(-140.0, 141.0, 4.0)
     X, Y = np.meshgrid(EGO0[0] + g, EGO0[1] + g)
-    return np.stack([X.ravel(), Y.ravel(), np.full(X.size, LANE_YAW)], 1)
+    return np.stack([X.ravel(), Y.ravel(), np.full(X.size, yaw)], 1)
 
 
-def scene_frames(cfg, n_scenes=2, frames_per_scene=FRAMES_PER_SCENE):
+def scene_frames(cfg, n_scenes=2, frames_per_scene=FRAMES_PER_SCENE, first_scene=0):
+    """The frames of scenes first_scene .. first_scene + n_scenes - 1: scene s is synthetic frame 1000 s shown frames_per_scene times,
+    moving at VELOCITY[s % 2]."""
     frames = []
-    for s in range(n_scenes):
+    for s in range(first_scene, first_scene + n_scenes):
         base = syn.make_frame(cfg, 1000 * s)
         fs = [moved_frame(base, s, k) for k in range(frames_per_scene)]
         for k, fr in enumerate(fs):
@@ -71,6 +74,32 @@ def scene_frames(cfg, n_scenes=2, frames_per_scene=FRAMES_PER_SCENE):
 
 def config():
     return syn.config("tiny", n_masks=8, duplicate_prob=0.25)
+
+
+def write_dataset(root, n_scenes=2, frames_per_scene=FRAMES_PER_SCENE, lane_yaws=None, road_half=None):
+    """The moving scenes in the reference's on-disk formats: nusc_io.write_synthetic_dataset with moved_frame for its frames (timestamps
+    500000 * f, as the writer sets them) and a one-yaw lane table for every map location -- lane_yaws[s], LANE_YAW for all when None.
+    road_half: None, or one half side per scene: the location's drivable area becomes that square around EGO0 (the writer's is a 160 m
+    square with a hole for every scene).  Returns (dataroot, mask_dir, scene names)."""
+    import json
+    import os
+    from cm3d_amd import nusc_io
+    real = syn.make_frame
+    syn.make_frame = lambda cfg, index: moved_frame(real(cfg, 1000 * (index // 1000)), index // 1000, index % 1000)
+    try:
+        dataroot, mask_dir, names = nusc_io.write_synthetic_dataset(str(root), config(), n_scenes=n_scenes, frames_per_scene=frames_per_scene)
+    finally:
+        syn.make_frame = real
+    for s in range(n_scenes):
+        np.save(os.path.join(dataroot, "lanes", f"synthtown-{s}.npy"), lane_table(LANE_YAW if lane_yaws is None else lane_yaws[s]))
+        if road_half is not None:
+            h = float(road_half[s])
+            ring = [(EGO0[0] - h, EGO0[1] - h), (EGO0[0] + h, EGO0[1] - h), (EGO0[0] + h, EGO0[1] + h), (EGO0[0] - h, EGO0[1] + h)]
+            nodes = [{"token": f"node-{s}-ext-{i}", "x": float(x), "y": float(y)} for i, (x, y) in enumerate(ring)]
+            polygon = {"token": f"poly-{s}", "exterior_node_tokens": [n["token"] for n in nodes], "holes": []}
+            with open(os.path.join(dataroot, "maps", "expansion", f"synthtown-{s}.json"), "w") as fh:
+                json.dump({"node": nodes, "polygon": [polygon], "drivable_area": [{"token": f"da-{s}", "polygon_tokens": [polygon["token"]]}]}, fh)
+    return dataroot, mask_dir, names
 
 
 @functools.lru_cache(maxsize=None)

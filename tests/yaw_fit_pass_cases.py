@@ -107,32 +107,35 @@ def add_l_vehicle(fr, lane_yaw, to_lane=None, cam=0, depth=12.0):
 _BATCHES, _PLAIN, _EXP = {}, {}, {}
 
 
-def batch(name):
-    """`nusc` or `waymo`: two frames, a lane table of parallel lanes per frame, an L vehicle as the last mask of every frame.  Fields as
-    optin_pass_cases.batch, plus classes, l_masks (the L vehicles' mask numbers) and l_heading (their headings in the lanes' frame)."""
-    if name in _BATCHES:
-        return _BATCHES[name]
+def batch(name, first=0, n_frames=2):
+    """`nusc` or `waymo`: synthetic frames first .. first + n_frames - 1 (two frames from 0 unless told otherwise), a lane table of
+    parallel lanes per frame, an L vehicle as the last mask of every frame.  Fields as optin_pass_cases.batch, plus classes, l_masks
+    (the L vehicles' mask numbers) and l_heading (their headings in the lanes' frame)."""
+    key = name if (first, n_frames) == (0, 2) else (name, first, n_frames)         # plain(), expected_of() know the default batch by its name
+    if key in _BATCHES:
+        return _BATCHES[key]
     from cm3d_amd import lifting
+    ids = range(first, first + n_frames)
     if name == "nusc":
         cfg = syn.config("tiny", n_points=9000, n_masks=20, width=512, height=288, ratio=0.32, max_area=12000.0)
-        frames = [syn.make_frame(cfg, i) for i in range(2)]
+        frames = [syn.make_frame(cfg, i) for i in ids]
         classes = lifting.ClassTable.nuscenes()
         lanes = [parallel_lanes(f.ego_xyz[:2], LANE_YAW[name]) for f in frames]
         heading = [add_l_vehicle(f, LANE_YAW[name]) for f in frames]
     elif name == "waymo":
         cfg = syn.config("tiny", n_cams=5, n_points=9000, n_masks=17, width=512, height=288, ratio=0.32, max_area=12000.0)
-        frames = [syn.make_waymo_frame(cfg, i) for i in range(2)]
+        frames = [syn.make_waymo_frame(cfg, i) for i in ids]
         classes = lifting.ClassTable.waymo()
         poses = [np.asarray(f.pose, np.float64).reshape(4, 4) for f in frames]
         lanes = [parallel_lanes(P[:2, 3], LANE_YAW[name]) for P in poses]
         heading = [add_l_vehicle(f, LANE_YAW[name], P) for f, P in zip(frames, poses)]
     else:
         raise KeyError(name)
-    frame_lane = [0, 1]
+    frame_lane = list(range(n_frames))
     hb = lifting.pack_frames(frames, lanes, frame_lane, classes)
-    _BATCHES[name] = SimpleNamespace(name=name, frames=frames, lanes=lanes, frame_lane=frame_lane, hb=hb, classes=classes,
-                                     l_masks=[int(m) - 1 for m in hb.mask_off[1:]], l_heading=heading)
-    return _BATCHES[name]
+    _BATCHES[key] = SimpleNamespace(name=name, frames=frames, lanes=lanes, frame_lane=frame_lane, hb=hb, classes=classes,
+                                    l_masks=[int(m) - 1 for m in hb.mask_off[1:]], l_heading=heading)
+    return _BATCHES[key]
 
 
 def plain(orc, name):
