@@ -116,6 +116,8 @@ SIGNATURES = {
     "cm3d_box_velocity_workspace_bytes": (_i64, [_i64, _i32]),
     "cm3d_box_velocity": (_i32, [_p, _p, _p, _i32, _i32, _p, _p, _p, _i32, _i32, _p, _p, C.c_double, _p, _i32, _i64, _p, _p, _p, _p, _p, _p,
                                  _i64, _p]),
+    "cm3d_box_tracks_workspace_bytes": (_i64, [_i32]),
+    "cm3d_box_tracks": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order

@@ -27,6 +27,7 @@ from .cluster import DepthCluster  # noqa: F401  (LiftEngine(cluster=DepthCluste
 from .bevfit import YawFit, angle_table  # noqa: F401  (LiftEngine(yaw=YawFit(...)))
 from .nms import RotatedNms  # noqa: F401  (LiftEngine(nms=RotatedNms(...)))
 from .velocity import Velocity, link_table  # noqa: F401  (LiftEngine(velocity=Velocity(...)))
+from .tracks import Tracks  # noqa: F401  (LiftEngine(velocity=Velocity(...), tracks=Tracks(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -450,7 +451,7 @@ class LiftEngine:
     def __init__(self, device="cuda:0", classes: Optional[ClassTable] = None, min_dist=MIN_DIST,
                  hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
                  cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None,
-                 velocity: Optional[Velocity] = None):
+                 velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -471,7 +472,11 @@ class LiftEngine:
         `box` holds the yaw that was used.
         velocity: the box velocity stage (velocity.Velocity; nuScenes batches, whose boxes are in the global frame): a call of its own
         behind the pass (cm3d_box_velocity) associates the kept boxes of consecutive frames.  It needs batches with `frame_next` and
-        `frame_time`; download() adds `vel`, `vel_src`, `next_match` and `prev_match`.  None: no buffer, no call."""
+        `frame_time`; download() adds `vel`, `vel_src`, `next_match` and `prev_match`.  None: no buffer, no call.
+        tracks: the track stage (tracks.Tracks; needs `velocity`): one more call behind the velocity stage's (cm3d_box_tracks) follows
+        the matches -- bit 1 of `flags`, columns 7 and 9 of `box` are what it leaves, download() adds `track_id`, `track_pos`,
+        `track_len`, `track_stat` and, with a smoothing window, `vel_smooth`, which kept_box_velocities then returns.  None or at its
+        defaults: no buffer, no call."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -488,6 +493,9 @@ class LiftEngine:
         self.nms = nms if nms is not None and nms.active else None
         self.yaw = yaw if yaw is not None and yaw.active else None
         self.velocity = velocity if velocity is not None and velocity.active else None
+        self.tracks = tracks if tracks is not None and tracks.active else None
+        if self.tracks is not None and self.velocity is None:
+            raise ValueError("tracks=Tracks(...) follows the matches of the velocity stage: it needs velocity=Velocity(...)")
         _verify_matrix_pipe(self.lib, self.dev)
         self.b = None
         self._lane = None                                    # the lane tables on the device and their spatial index (upload)
@@ -636,6 +644,12 @@ class LiftEngine:
             b.vel_status = torch.zeros(1, dtype=torch.int32, device=d)
             b.vel_ws_bytes = int(L.cm3d_box_velocity_workspace_bytes(b.vel_pairs, M))
             b.vel_ws = torch.empty(max(b.vel_ws_bytes, 16), dtype=torch.uint8, device=d)
+        if self.tracks is not None:
+            b.track_id = e(M); b.track_pos = e(M); b.track_len = e(M); b.track_stat = e(M, 4, dtype=torch.float64)
+            b.vel_smooth = e(M, 2, dtype=torch.float64) if self.tracks.smooth_window > 0 else None
+            b.track_status = torch.zeros(1, dtype=torch.int32, device=d)
+            b.track_ws_bytes = int(L.cm3d_box_tracks_workspace_bytes(M))
+            b.track_ws = torch.empty(max(b.track_ws_bytes, 16), dtype=torch.uint8, device=d)
         b.dense = dense_masks
         # The bulk data LAST: sweeps and run lengths come from page-locked staging buffers (cm3d_amd.reader) and copy
         # asynchronously; the small arrays above are pageable, their copies block the host until everything queued before them on
@@ -1005,6 +1019,14 @@ class LiftEngine:
                                          _ptr(b.prev_match), _ptr(b.vel), _ptr(b.vel_src), _ptr(b.vel_status), _ptr(b.vel_ws),
                                          b.vel_ws_bytes, st), "cm3d_box_velocity")
 
+    def stage_tracks(self, st):
+        """The opt-in track stage on the matches the velocity stage left; rewrites scores and keep bits in place (cm3d_box_tracks)."""
+        b, tr = self.b, self.tracks
+        check(self.lib.cm3d_box_tracks(_ptr(b.box), _ptr(b.flags), _ptr(b.mask_frame), _ptr(b.next_match), _ptr(b.prev_match),
+                                       _ptr(b.frame_time), b.M, b.F, tr.min_length, tr.score_mode, tr.smooth_window, _ptr(b.track_id),
+                                       _ptr(b.track_pos), _ptr(b.track_len), _ptr(b.track_stat), _ptr(b.vel_smooth), _ptr(b.track_status),
+                                       _ptr(b.track_ws), b.track_ws_bytes, st), "cm3d_box_tracks")
+
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
     def run(self, masks="dense", project_events=None, stage_events=None):
@@ -1029,6 +1051,8 @@ class LiftEngine:
               "cm3d_lift_pass_opt")
         if self.velocity is not None:                    # behind the pass, on its final kept set: one more library call
             self.stage_velocity(st)
+        if self.tracks is not None:                      # behind the velocity stage, on its matches: one more
+            self.stage_tracks(st)
 
     def capture_graph(self, masks="rle"):
         """Captures one pass over the resident batch into a HIP graph and returns it (`g.replay()` re-runs the pass
@@ -1085,6 +1109,14 @@ class LiftEngine:
                 raise Cm3dError("velocity: a frame_next lies outside the batch")
             if v & 2:
                 raise Cm3dError("velocity: pair_off disagrees with mask_off / frame_next, or a linked frame has too many masks")
+        if self.tracks is not None:
+            v = int(self.b.track_status.item())
+            if v & 1:
+                raise Cm3dError("tracks: a kept mask's frame lies outside the batch")
+            if v & 2:
+                raise Cm3dError("tracks: a next_match / prev_match lies outside the batch's masks")
+            if v & 4:
+                raise Cm3dError("tracks: a match is not mutual, not kept or not forward in time")
         return s
 
     def removed_rows(self):
@@ -1160,8 +1192,14 @@ class LiftEngine:
 
     def _velocity_results(self):
         b = self.b
-        return dict(vel=b.vel.cpu().numpy(), vel_src=b.vel_src.cpu().numpy(), next_match=b.next_match.cpu().numpy(),
-                    prev_match=b.prev_match.cpu().numpy())
+        out = dict(vel=b.vel.cpu().numpy(), vel_src=b.vel_src.cpu().numpy(), next_match=b.next_match.cpu().numpy(),
+                   prev_match=b.prev_match.cpu().numpy())
+        if self.tracks is not None:
+            out.update(track_id=b.track_id.cpu().numpy(), track_pos=b.track_pos.cpu().numpy(), track_len=b.track_len.cpu().numpy(),
+                       track_stat=b.track_stat.cpu().numpy())
+            if b.vel_smooth is not None:
+                out["vel_smooth"] = b.vel_smooth.cpu().numpy()
+        return out
 
     def _yaw_results(self):
         b = self.b
@@ -1336,8 +1374,10 @@ def kept_box_records(b, frame_ids, device=None):
 
 
 def kept_box_velocities(b):
-    """(k, 2) float64 velocities of the masks kept_box_records ships, in its order (an engine with Velocity(...); a device tensor)."""
-    return b.vel[(b.flags & 3) == 3].clone()
+    """(k, 2) float64 velocities of the masks kept_box_records ships, in its order (an engine with Velocity(...); a device tensor).
+    With Tracks(smooth_window > 0): the rows of `vel_smooth`, the slope over the track's window, in place of the neighbours' difference."""
+    vel = getattr(b, "vel_smooth", None)
+    return (b.vel if vel is None else vel)[(b.flags & 3) == 3].clone()
 
 
 def _velocity_rows(vel, n):

@@ -13,6 +13,8 @@ src/nuscenes/2d_to_3d.py so that parity tests read like calls into the reference
     points_in_polygons(polygon_tables, xy, table)        eval_custom.py:514-519 for many points
     depth_cluster(point_lists, origins, eps, ...)        the opt-in depth clustering of several lists (cluster.depth_cluster_host)
     bev_fit(xyz, off, ...) / yaw_select(...)             the opt-in yaw fit of several lists and the choice of each mask's yaw (bevfit.*_host)
+    box_velocity(box, flags, mask_off, ...)              the opt-in association of consecutive frames' boxes (velocity.track_velocity_host)
+    box_tracks(box, flags, mask_frame, next_match, ...)  the opt-in tracks behind it: ids, length filter, scores, smoothed velocity (tracks.box_tracks_host)
 
 They are conveniences for tests and small jobs; the batched path is lifting.LiftEngine.
 """
@@ -505,6 +507,46 @@ def box_velocity(box, flags, mask_off, class_id, frame_next, frame_time, track_g
                               ws.numel(), _st()), "cm3d_box_velocity")
     return dict(next_match=nm.cpu().numpy()[:M], prev_match=pm.cpu().numpy()[:M], vel=vel.cpu().numpy().reshape(-1, 2)[:M], vel_src=src.cpu().numpy()[:M],
                 status=int(status.item()))
+
+
+def box_tracks(box, flags, mask_frame, next_match, prev_match, frame_time, min_length=1, score="own", smooth_window=0, out=None):
+    """The opt-in track stage on arrays (cm3d_box_tracks; tracks.box_tracks_host states it): box (M, BOX_STRIDE) float64 and flags (M,)
+    as a pass left them, mask_frame (M,), next_match / prev_match (M,) as box_velocity left them, frame_time (F,) seconds.  out: optional
+    dict of device tensors track_id, track_pos, track_len (M,) int32, track_stat (M, 4), vel_smooth (M, 2) float64, and box (M, BOX_STRIDE)
+    float64, flags (M,) int32 to work in (else allocated; box and flags are filled from the arguments either way).  Returns a dict of
+    numpy arrays: the five outputs (vel_smooth only for smooth_window > 0), the new `box` and `flags`, and `status` (int; the bits of
+    the header, not raised: a caller decides)."""
+    from . import tracks as trmod
+    L = _lib.lib()
+    box = np.asarray(box, np.float64).reshape(-1, _lib.BOX_STRIDE)
+    M = box.shape[0]
+    tim = np.asarray(frame_time, np.float64).reshape(-1)
+    W = int(smooth_window)
+    o = out or {}
+    n = max(M, 1)
+    i32 = lambda a: np.asarray(a, np.int32).reshape(M) if M else np.zeros(1, np.int32)
+    if "box" in o:
+        d_box, d_flags = o["box"], o["flags"]
+        if M:
+            d_box.view(-1)[:M * _lib.BOX_STRIDE].copy_(_t(box).view(-1)); d_flags.view(-1)[:M].copy_(_t(i32(flags)))
+    else:
+        d_box, d_flags = _t(box if M else np.zeros((1, _lib.BOX_STRIDE))), _t(i32(flags))
+    d_frm, d_nm, d_pm, d_tim = _t(i32(mask_frame)), _t(i32(next_match)), _t(i32(prev_match)), _t(tim if tim.size else np.zeros(1))
+    tid, pos, ln = (o[k] if k in o else _e(n) for k in ("track_id", "track_pos", "track_len"))
+    stat = o["track_stat"] if "track_stat" in o else _e(n, 4, dtype=torch.float64)
+    vs = (o["vel_smooth"] if "vel_smooth" in o else _e(n, 2, dtype=torch.float64)) if W > 0 else None
+    status = torch.zeros(1, dtype=torch.int32, device=_dev())
+    ws = _ws(L.cm3d_box_tracks_workspace_bytes(M))
+    check(L.cm3d_box_tracks(d_box.data_ptr(), d_flags.data_ptr(), d_frm.data_ptr(), d_nm.data_ptr(), d_pm.data_ptr(), d_tim.data_ptr(), M,
+                            tim.size, int(min_length), trmod.score_code(score), W, tid.data_ptr(), pos.data_ptr(), ln.data_ptr(),
+                            stat.data_ptr(), vs.data_ptr() if vs is not None else None, status.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+          "cm3d_box_tracks")
+    res = dict(track_id=tid.cpu().numpy().reshape(-1)[:M], track_pos=pos.cpu().numpy().reshape(-1)[:M], track_len=ln.cpu().numpy().reshape(-1)[:M],
+               track_stat=stat.cpu().numpy().reshape(-1, 4)[:M], box=d_box.cpu().numpy().reshape(-1, _lib.BOX_STRIDE)[:M],
+               flags=d_flags.cpu().numpy().reshape(-1)[:M], status=int(status.item()))
+    if vs is not None:
+        res["vel_smooth"] = vs.cpu().numpy().reshape(-1, 2)[:M]
+    return res
 
 
 # ----------------------------------------------------------------------------- f4: SAM3D fusion matching

@@ -911,7 +911,8 @@ typedef struct cm3d_lift_pass_options {    /* NULL member: that stage is off */
  *   yaw     ?  cm3d_yaw_fit_boxes' sequence          lists = cluster ? cl_xyz, cl_off : desc's;  positions = filter ? medoid_pos_kept : desc's
  *   nms     ?  cm3d_box_rotated_nms                  box, flags, mask_off ... of desc; waymo = pose_inv != NULL; bound as the box launch's
  *   opt == NULL or every member NULL: exactly cm3d_lift_pass(desc)
- *   behind the pass, a call of the caller's own and no member of opt: cm3d_box_velocity (below) on desc's box, flags, mask_off, class_id */
+ *   behind the pass, a call of the caller's own and no member of opt: cm3d_box_velocity (below) on desc's box, flags, mask_off, class_id
+ *   behind cm3d_box_velocity, a call of the caller's own as well: cm3d_box_tracks (below) on desc's box, flags and the two match arrays */
 int cm3d_lift_pass_opt(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, cm3d_stream_t stream);
 
 /* ---- box velocity from frame-to-frame association (opt-in; nuScenes: boxes in the global frame) --------------------
@@ -965,6 +966,54 @@ int cm3d_box_velocity(const double *box, const int32_t *flags, const int32_t *ma
                       int32_t n_groups, const int32_t *frame_next, const double *frame_time, double max_dt, const int64_t *pair_off,
                       int32_t n_links, int64_t total_pairs, int32_t *next_match, int32_t *prev_match, double *vel, int32_t *vel_src,
                       int32_t *status, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
+
+/* ---- box tracks from the velocity stage's matches (opt-in; a call of its own BEHIND cm3d_box_velocity) ---------------
+ * Added within ABI v5: new symbols only.  cm3d_box_velocity leaves next_match / prev_match; this stage follows them: a track id,
+ * position and length per kept box, four statistics per track, a least-squares velocity over a window of the track, a track score
+ * and a length filter.  What it does to label quality has not been measured, and none of its defaults is tuned.  Host statement to
+ * the bit: cm3d_amd.tracks.box_tracks_host.  M = n_masks, F = n_frames.
+ *
+ *  box, flags  double[M][CM3D_BOX_STRIDE], int32[M], IN/OUT: only box[i][7], box[i][9] and bit 1 of flags[i] are ever written
+ *  mask_frame  int32[M] the batch frame of every mask;  frame_time double[F] seconds (as cm3d_box_velocity takes them)
+ *  next_match, prev_match  int32[M] as cm3d_box_velocity left them; read only
+ *
+ *  Kept.    kept(i) = (flags[i] & 3) == 3 and 0 <= mask_frame[i] < F.  Flag bits set but a frame outside [0, F): status bit 0, not kept.
+ *  Links.   For a kept i and j = next_match[i]:  j outside [-1, M): status bit 1, read as -1.  j >= 0 is a valid next link iff kept(j),
+ *           prev_match[j] == i and frame_time[mask_frame[j]] > frame_time[mask_frame[i]] (NaN compares false); else status bit 2, read
+ *           as -1.  prev_match symmetrically: p valid iff kept(p), next_match[p] == i and p's time < i's.  Valid links are mutual and
+ *           strictly forward in time: whatever the arrays hold, the structure is a set of disjoint paths of at most F masks each,
+ *           without cycles, and no index outside [0, M) or [0, F) addresses memory.  What cm3d_box_velocity writes sets none of the bits.
+ *  Tracks.  A head is a kept mask without a valid previous link; its track m_0 = head, m_1 = next(m_0), ..., m_{L-1}.  Every member:
+ *           track_id = m_0 (the head's batch mask index), track_pos = k, track_len = L, and track_stat[4], float64, every operation
+ *           rounded on its own (no fma), s_k = box[m_k][7] as on entry, t_k = m_k's frame time:
+ *             [0] (((+0.0 + s_0) + s_1) + ...) in track order        [1] the greatest s_k: s_0, replaced by every later s_k > it
+ *             [2] t_{L-1} - t_0                                      [3] sqrt((dx * dx) + (dy * dy)) of the last centre minus the first
+ *           A mask that is not kept: track_id -1, track_pos -1, track_len 0, zeros in track_stat and vel_smooth.
+ *  Smoothed velocity, smooth_window = W >= 1 (0: off; vel_smooth may then be NULL, and holds zeros if it is given).  Member i at position p: the window
+ *           is the n members at positions max(0, p - W) .. min(L - 1, p + W) in track order.  n < 2: zeros.  Else per window member j
+ *             t = time(j) - time(i);  x = box[j][0] - box[i][0];  y = box[j][1] - box[i][1]
+ *           six left-to-right sums from +0.0: St, Stt (of t * t), Sx, Sy, Stx (of t * x), Sty (of t * y); then
+ *             den = ((double)n * Stt) - (St * St);  den > 0 ?  vx = (((double)n * Stx) - (St * Sx)) / den,  vy alike  :  zeros
+ *           -- the least-squares slope through the window.  vel, vel_src and the match arrays of cm3d_box_velocity are never written.
+ *  Score, score_mode: 0 own, nothing written; 1 mean, box[i][7] = track_stat[0] / (double)L; 2 max, box[i][7] = track_stat[1].  Kept
+ *           masks only, from the scores as they were on entry.
+ *  Filter, min_length >= 1: a kept mask with L < min_length loses bit 1 of flags[i], and box[i][9] = (double)flags[i] as
+ *           cm3d_box_rotated_nms writes it; nothing else of the mask changes.  A whole track goes or stays.
+ *
+ *  CM3D_ERR_ARG before any launch: n_masks < 0, n_frames <= 0, min_length < 1, score_mode outside 0..2, smooth_window < 0,
+ *  smooth_window > 0 with vel_smooth NULL, a NULL array that M > 0 needs.  CM3D_ERR_WORKSPACE before any launch: workspace NULL or
+ *  shorter than cm3d_box_tracks_workspace_bytes(n_masks) (a double and two int32 per mask: time, validated next and previous link).
+ *  The first launch initialises track_id, track_pos, track_len, track_stat and vel_smooth: a rerun on restored inputs gives the same
+ *  bytes.  box and flags are IN/OUT: with min_length > 1 or score_mode != 0 a second call on the same arrays sees other scores and
+ *  another kept set, so it is no rerun -- the pass writes both anew before every call of the engine's.
+ *  status      int32[1], zero it before the call; bits 0..2 above are only ever set
+ *  Launches: k_tracks_links, k_tracks_walk, k_tracks_apply, one thread per mask each.  The third, which changes flags, reads validity
+ *  from the workspace alone.  Plain stores; the only atomic is the status word's OR; no allocation. */
+int64_t cm3d_box_tracks_workspace_bytes(int32_t n_masks);
+int cm3d_box_tracks(double *box, int32_t *flags, const int32_t *mask_frame, const int32_t *next_match, const int32_t *prev_match,
+                    const double *frame_time, int32_t n_masks, int32_t n_frames, int32_t min_length, int32_t score_mode,
+                    int32_t smooth_window, int32_t *track_id, int32_t *track_pos, int32_t *track_len, double *track_stat,
+                    double *vel_smooth, int32_t *status, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
 
 #ifdef __cplusplus
 }
