@@ -54,6 +54,7 @@ SIGNATURES = {
     "cm3d_project_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "cm3d_project_hit_rows": (_i32, [_p, _i64, _i32, _i32, _i32, _p, _p]),
     "cm3d_project_culling": (_i32, [_p, _i64, _i32, _i32, _i32, _p, _p]),
+    "cm3d_project_wedges": (_i32, [_p, _i64, _i32, _i32, _i32, _p, _p]),
     "cm3d_project_hits": (_i32, [_p, _p, _i32, _i32, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i32, _i32, _f32, _i32,
                                  _p, _p, _p, _p, _i64, _p, _p, _p]),
     "cm3d_sweep_project_hits": (_i32, [_p, _i32, _p, _p, _i32, _i32, _p, _p, _f32, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _i32, _p, _p,

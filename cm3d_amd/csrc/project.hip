@@ -183,8 +183,10 @@ static __device__ __forceinline__ void project_quad(const float *cm, int ns, int
 // rounding of the kernels' own float32 evaluation):
 //  * view wedge: a point in front of the camera can only pass the exact in-image test (0 < u < W - 1) if it lies on the inner
 //    side of the two planes through the camera centre and the image's left and right edges, u >= 0 and u <= W: in camera
-//    coordinates fx X + cx Z >= 0 and (W - cx) Z - fx X >= 0, linear in the global point.  out: [0..2] unit normal of the
-//    left plane (global), [3] its offset + margin, [4..7] the same for the right plane; a point is kept while
+//    coordinates fx X + cx Z >= 0 and (W - cx) Z - fx X >= 0, linear in the global point.  wedge_setup takes the column interval
+//    [u_lo, u_hi] the planes stand on -- fx X + (cx - u_lo) Z >= 0 and (u_hi - cx) Z - fx X >= 0 --; the image's wedge is the
+//    case u_lo = 0, u_hi = W (same bits as before the interval existed).  out: [0..2] unit normal of the left plane (global),
+//    [3] its offset + margin, [4..7] the same for the right plane; a point is kept while
 //    min(n_L . p + d_L, n_R . p + d_R) >= 0.  The margin (1e-6 max|o| + 1e-3 m) covers the float32 evaluation here and in
 //    the exact chain at global magnitudes ten times over.  (The circular cone of earlier versions needed 13 packed operations
 //    per point pair and camera and circumscribes the image; the wedge needs 7 and is 10 % narrower.)
@@ -196,8 +198,19 @@ static __device__ __forceinline__ void project_quad(const float *cm, int ns, int
 //    *margin_px = 1 + ceil(2 max(fx, fy) delta / zmin) pixels for every point the depth test can accept.
 // A camera record the derivation does not cover (skew, non-trivial last row of K, stages that are not rigid) disables both
 // tests for that camera (the wedge accepts everything, *apx_ok = false).
-static __device__ void wedge_setup(const float *cm_global, int W, int H, float min_dist, float *out, float *apx, int *margin_px, bool *apx_ok,
-                                  float *zmin_out)
+//
+// The work is split in two so that k_frame_tables can form the cameras' column hulls between the halves: wedge_compose is
+// everything that needs the record alone (the loads, the double-precision composition, apx, the bounds), wedge_setup the planes.
+struct WedgeCam {
+    double m0[3], m2[3];            // rows 0 and 2 of the composed rotation M (the planes' normals have no y component)
+    double c0, c2;                  // p_cam = M p + c
+    double fx, cx, margin;
+    bool planes;                    // the derivation covers the record (else: the wedge accepts everything)
+    int pad;                        // >= 0: pixel bound on the exact chain's column against the composed one (below); -1: none
+};
+
+static __device__ void wedge_compose(const float *cm_global, int W, float min_dist, WedgeCam *wc, float *apx, int *margin_px, bool *apx_ok,
+                                     float *zmin_out)
 {
     // the whole record in registers first (14 independent 16-byte loads in flight at once; the record is 224 bytes and
     // 16-byte aligned), so that the composition below never waits on memory stage by stage
@@ -245,25 +258,44 @@ static __device__ void wedge_setup(const float *cm_global, int W, int H, float m
     const float omax = (float)fmax(fmax(fabs(ox), fabs(oy)), fabs(oz));
     const float zmin = min_dist - 0.05f - 1e-4f * omax;
     *zmin_out = zmin;
-    for (int q = 0; q < 8; ++q) out[q] = (q & 3) == 3 ? 1.f : 0.f;                    // accept everything
-    if (!plain || !(dev < 1e-3)) return;
-    {
-        const double fx = (double)K[0], cxp = (double)K[2], margin = 1e-6 * (double)omax + 1e-3;
-        const double nc[2][3] = {{fx, 0.0, cxp}, {-fx, 0.0, (double)W - cxp}};         // left, right plane in camera coordinates
-        for (int e = 0; e < 2; ++e) {
-            const double len = sqrt(nc[e][0] * nc[e][0] + nc[e][2] * nc[e][2]);
-            const double a = nc[e][0] / len, b = nc[e][2] / len;                         // (the y component is 0)
-            out[4 * e + 0] = (float)(M[0] * a + M[6] * b);                               // M^T n
-            out[4 * e + 1] = (float)(M[1] * a + M[7] * b);
-            out[4 * e + 2] = (float)(M[2] * a + M[8] * b);
-            out[4 * e + 3] = (float)(a * c[0] + b * c[2] + margin);
-        }
-    }
-    (void)H;
-    if (zmin > 0.1f && dev < 1e-5) {
+    for (int q = 0; q < 3; ++q) { wc->m0[q] = M[q]; wc->m2[q] = M[6 + q]; }
+    wc->c0 = c[0]; wc->c2 = c[2];
+    wc->fx = (double)K[0]; wc->cx = (double)K[2]; wc->margin = 1e-6 * (double)omax + 1e-3;
+    wc->planes = plain && dev < 1e-3;
+    wc->pad = -1;
+    if (wc->planes && zmin > 0.1f && dev < 1e-5) {
         const float delta = 1e-6f * omax + 1e-4f;
         const float mg = 1.f + ceilf(2.f * fmaxf(K[0], K[4]) * delta / zmin);
         if (mg < 64.f) { *margin_px = (int)mg; *apx_ok = true; }
+        // Column hull (k_frame_tables).  The gather can give a point to a mask of this camera only if the EXACT chain's float32 pixel
+        // u_f has floor(u_f) inside the mask's eroded columns [bb.x, bb.z], i.e. bb.x <= u_f < bb.z + 1, and its depth passed the depth
+        // test, so its axial distance is >= zmin.  The exact chain's camera coordinates differ from the double composition's
+        // (X, Y, Z) by less than delta each (the budget of the approximate projection above holds both forms against it), so
+        // its column differs from the composed one, u = fx X / Z + cx, by less than fx delta (1 + |X / Z|) / Z, and inside the
+        // image |X / Z| <= max(cx, W - cx) / fx =: t.  The float32 K chain and division add ~3 ulp of a column number, < 1e-3
+        // pixels: the "1 +" holds them a thousand times over.  Hence
+        //     pad = 1 + ceil(max(2, 1 + t) max(fx, fy) delta / zmin)   (never below margin_px's form)
+        // and every such point has min bb.x - pad <= u <= max bb.z + 1 + pad: it lies inside the wedge on that interval, whose
+        // planes carry the same metric margin as the image's.  Where zmin or dev give no such bound the camera keeps the image.
+        const float t = fmaxf(K[2], (float)W - K[2]) / K[0];
+        const float pd = 1.f + ceilf(fmaxf(2.f, 1.f + t) * fmaxf(K[0], K[4]) * delta / zmin);
+        wc->pad = pd < 32768.f ? (int)pd : 32768;              // (as wide as any image: the interval clamps to it)
+    }
+}
+
+// the two planes of a composed camera on the column interval [u_lo, u_hi]
+static __device__ void wedge_setup(const WedgeCam &wc, double u_lo, double u_hi, float *out)
+{
+    for (int q = 0; q < 8; ++q) out[q] = (q & 3) == 3 ? 1.f : 0.f;                    // accept everything
+    if (!wc.planes) return;
+    const double nc[2][3] = {{wc.fx, 0.0, wc.cx - u_lo}, {-wc.fx, 0.0, u_hi - wc.cx}};        // left, right plane in camera coordinates
+    for (int e = 0; e < 2; ++e) {
+        const double len = sqrt(nc[e][0] * nc[e][0] + nc[e][2] * nc[e][2]);
+        const double a = nc[e][0] / len, b = nc[e][2] / len;                         // (the y component is 0)
+        out[4 * e + 0] = (float)(wc.m0[0] * a + wc.m2[0] * b);                       // M^T n
+        out[4 * e + 1] = (float)(wc.m0[1] * a + wc.m2[1] * b);
+        out[4 * e + 2] = (float)(wc.m0[2] * a + wc.m2[2] * b);
+        out[4 * e + 3] = (float)(a * wc.c0 + b * wc.c2 + wc.margin);
     }
 }
 
@@ -373,31 +405,10 @@ __global__ __launch_bounds__(64) void k_frame_tables(const PhSweepIn sw, int fus
         ft[7] = (n + PH_WC - 1) / PH_WC;
         ft[FT_FUSED] = fused ? 1 : 0;
     }
-    int ft_margin = 0;
-    {
-        int mg = 0;
-        bool ok = false;
-        float zmin = INFINITY;
-        if (lane < CM3D_MAX_CAMS) {
-            float *wedge = reinterpret_cast<float *>(ft + FT_WEDGE) + 8 * lane, *apx = reinterpret_cast<float *>(ft + FT_APX) + 16 * lane;
-            if (lane < n_cams) wedge_setup(cams + ((size_t)f * n_cams + lane) * CM3D_CAM_STRIDE, W, H, min_dist, wedge, apx, &mg, &ok, &zmin);
-            else                             // a slot without a camera: a wedge nothing is inside of (the projection kernel tests whole groups)
-                for (int q = 0; q < 8; ++q) wedge[q] = (q & 3) == 3 ? -1.f : 0.f;
-        }
-        const uint64_t okm = __ballot(ok);
-        mg = cm3d_wave_max(mg);
-        // the frame's smallest (the cameras' differ by 1e-4 of their distance from the origin).  As a float: the int reduction this
-        // used to go through truncated it towards zero (2.105 -> 2, 0.11 -> 0: still below every camera's own, so no result ever
-        // depended on it, but not the bound wedge_setup derived)
-        zmin = cm3d_wave_reduce_t(zmin, [](float a, float b) { return fminf(a, b); });
-        ft_margin = mg;
-        if (lane == 0) { ft[FT_MARGIN] = mg; ft[FT_APXOK] = (int)(uint32_t)okm; ft[FT_ZMIN] = __float_as_int(zmin); }
-    }
-    // the frame's masks sorted by camera: count per camera (lane c = masks of camera c), exclusive prefix, placement by
-    // ballot rank.  Every mask is loaded once per pass (twice when the frame has more than 64 masks).
+    // Order: the first 64 masks' loads go out first; the cameras' double-precision composition (wedge_compose: it needs the records
+    // alone) runs under them; then the masks are counted per camera and each camera's column hull is formed; the planes come last.
     int4 *ment = ment_all + (size_t)f * nm_cap * 2;
-    const int mg = ft_margin;
-    auto load_mask = [&](int k, int &cam, int4 &bb, int4 &rc) {      // bb: bounds of the eroded pixels; rc: the stored rectangle (xw0, y0, wc, rows)
+    auto fetch_mask = [&](int k, int &cam, int4 &bb, int4 &rc) {      // bb: bounds of the eroded pixels; rc: the stored rectangle (xw0, y0, wc, rows)
         cam = -1;
         bb = make_int4(0, 0, -1, -1);
         rc = make_int4(0, 0, 0, 0);
@@ -405,22 +416,75 @@ __global__ __launch_bounds__(64) void k_frame_tables(const PhSweepIn sw, int fus
             cam = mask_cam[m0 + k];
             bb = bbox[2 * (m0 + k)];
             rc = bbox[2 * (m0 + k) + 1];
+        }
+    };
+    auto vet_mask = [&](int k, int &cam, const int4 &bb) {
+        if (k < nm) {
             if (cam < 0 || cam >= n_cams) { atomicOr(&status[0], 4); cam = -1; }         // such a mask gets no points
             else if (!(bb.z >= bb.x && bb.w >= bb.y)) cam = -1;                          // empty after the erosion
         }
     };
+    auto load_mask = [&](int k, int &cam, int4 &bb, int4 &rc) { fetch_mask(k, cam, bb, rc); vet_mask(k, cam, bb); };
     int cam0;
     int4 bb0, rc0;
-    load_mask(lane, cam0, bb0, rc0);                 // the first 64 masks stay in registers for both passes
+    fetch_mask(lane, cam0, bb0, rc0);                // the first 64 masks stay in registers for both passes
+    // column hull of every camera's non-empty entries: [c] smallest bb.x, [CM3D_MAX_CAMS + c] largest bb.z (integer min / max in LDS)
+    __shared__ int s_hull[2 * CM3D_MAX_CAMS];
+    if (lane < 2 * CM3D_MAX_CAMS) s_hull[lane] = lane < CM3D_MAX_CAMS ? 0x7FFFFFFF : (int)0x80000000;
+    int ft_margin = 0;
+    WedgeCam wc;
+    wc.planes = false;
+    wc.pad = -1;
+    {
+        int mg = 0;
+        bool ok = false;
+        float zmin = INFINITY;
+        if (lane < CM3D_MAX_CAMS) {
+            float *wedge = reinterpret_cast<float *>(ft + FT_WEDGE) + 8 * lane, *apx = reinterpret_cast<float *>(ft + FT_APX) + 16 * lane;
+            if (lane < n_cams) wedge_compose(cams + ((size_t)f * n_cams + lane) * CM3D_CAM_STRIDE, W, min_dist, &wc, apx, &mg, &ok, &zmin);
+            else                             // a slot without a camera: a wedge nothing is inside of (the projection kernel tests whole groups)
+                for (int q = 0; q < 8; ++q) wedge[q] = (q & 3) == 3 ? -1.f : 0.f;
+        }
+        const uint64_t okm = __ballot(ok);
+        mg = cm3d_wave_max(mg);
+        // the frame's smallest (the cameras' differ by 1e-4 of their distance from the origin).  As a float: the int reduction this
+        // used to go through truncated it towards zero (2.105 -> 2, 0.11 -> 0: still below every camera's own, so no result ever
+        // depended on it, but not the bound wedge_compose derived)
+        zmin = cm3d_wave_reduce_t(zmin, [](float a, float b) { return fminf(a, b); });
+        ft_margin = mg;
+        if (lane == 0) { ft[FT_MARGIN] = mg; ft[FT_APXOK] = (int)(uint32_t)okm; ft[FT_ZMIN] = __float_as_int(zmin); }
+    }
+    // the frame's masks sorted by camera: count per camera (lane c = masks of camera c), exclusive prefix, placement by
+    // ballot rank.  Every mask is loaded once per pass (twice when the frame has more than 64 masks).
+    const int mg = ft_margin;
+    vet_mask(lane, cam0, bb0);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // (one wave: the hull's initial values stand before the first min / max)
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     int cnt = 0;                                     // lane c: masks of camera c
     for (int k0 = 0; k0 < nm; k0 += 64) {
         int cam = cam0;
         int4 bb = bb0, rc = rc0;
         if (k0) load_mask(k0 + lane, cam, bb, rc);
+        if (cam >= 0) {                              // (vetted: 0 <= cam < n_cams <= CM3D_MAX_CAMS, a non-empty box)
+            atomicMin(&s_hull[cam], bb.x);
+            atomicMax(&s_hull[CM3D_MAX_CAMS + cam], bb.z);
+        }
         for (int c = 0; c < n_cams; ++c) {
             const int x = (int)__popcll(__ballot(cam == c));
             cnt += lane == c ? x : 0;
         }
+    }
+    // The planes: on the hull of the camera's mask columns grown by its pad and clamped to the image, [min bb.x - pad, max bb.z + 1 +
+    // pad] (wedge_compose has the argument); on the image's [0, W] where the camera has no pad or no non-empty entry.
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane < n_cams && lane < CM3D_MAX_CAMS) {
+        const int lo = s_hull[lane], hi = s_hull[CM3D_MAX_CAMS + lane];
+        int u_lo = 0, u_hi = W;
+        if (wc.pad >= 0 && hi >= lo) { u_lo = max(lo - wc.pad, 0); u_hi = min(min(hi, W) + 1 + wc.pad, W); }
+        wedge_setup(wc, (double)u_lo, (double)u_hi, reinterpret_cast<float *>(ft + FT_WEDGE) + 8 * lane);
     }
     int first = cm3d_wave_incl_scan(lane < n_cams ? cnt : 0) - (lane < n_cams ? cnt : 0);       // lane c: first entry of camera c
     const int run = __builtin_amdgcn_readlane(first, CM3D_MAX_CAMS - 1) + __builtin_amdgcn_readlane(lane < n_cams ? cnt : 0, CM3D_MAX_CAMS - 1);
@@ -1374,6 +1438,26 @@ extern "C" int cm3d_project_culling(const void *workspace, int64_t workspace_byt
             o[0] = t[FT_APXOK]; o[1] = t[FT_CAMHAS]; o[2] = t[FT_MARGIN]; o[3] = t[FT_ZMIN]; o[4] = wedges;
             o[5] = o[6] = o[7] = 0;
         }
+    } catch (...) { return CM3D_ERR_ARG; }
+    return CM3D_OK;
+}
+
+// Accounting aid (the tests of the column hulls; nothing on the path calls it): the view wedges k_frame_tables wrote for every frame
+// of the last launch -- out[f][c][0..7] = the two planes of camera slot c as wedge_setup describes them.  Synchronous, like
+// cm3d_project_culling.
+extern "C" int cm3d_project_wedges(const void *workspace, int64_t workspace_bytes, int32_t n_frames, int32_t max_pts_per_frame,
+                                   int32_t planes, float *out, cm3d_stream_t stream)
+{
+    if (!workspace || !out || n_frames <= 0 || max_pts_per_frame <= 0 || planes <= 0) return CM3D_ERR_ARG;
+    if (workspace_bytes < cm3d_project_workspace_bytes(n_frames, max_pts_per_frame, planes) || ((uintptr_t)workspace & 15)) return CM3D_ERR_WORKSPACE;
+    try {
+        PhWs ws;
+        ph_ws_layout(n_frames, max_pts_per_frame, planes, const_cast<void *>(workspace), &ws);
+        std::vector<float> ft((size_t)n_frames * FT_WORDS);            // (the planes are the tables' float words)
+        if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return CM3D_ERR_LAUNCH;
+        if (hipMemcpy(ft.data(), ws.ft, ft.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) return CM3D_ERR_LAUNCH;
+        for (int f = 0; f < n_frames; ++f)
+            std::copy_n(ft.data() + (size_t)f * FT_WORDS + FT_WEDGE, CM3D_MAX_CAMS * 8, out + (size_t)f * CM3D_MAX_CAMS * 8);
     } catch (...) { return CM3D_ERR_ARG; }
     return CM3D_OK;
 }

@@ -1089,6 +1089,16 @@ class LiftEngine:
         return dict(apx_ok=out[:, 0].copy(), cam_has=out[:, 1].copy(), margin_px=out[:, 2].copy(),
                     zmin=out[:, 3].copy().view(np.float32), wedge=out[:, 4].copy())
 
+    def wedges(self):
+        """The view wedges the projection's per-frame tables hold for the resident batch after the last pass (cm3d_project_wedges; an
+        aid of the tests, synchronises the stream): float32 [F, CM3D_MAX_CAMS, 8] -- unit normal and offset of the left plane, then
+        of the right one; a global point p is looked at for camera c while min(n_L . p + d_L, n_R . p + d_R) >= 0."""
+        b = self.b
+        out = np.zeros((b.F, 8, 8), np.float32)
+        check(self.lib.cm3d_project_wedges(_ptr(b.pg_ws), b.pg_ws_bytes, b.F, b.max_pts, b.planes, out.ctypes.data,
+                                           torch.cuda.current_stream(self.dev).cuda_stream), "cm3d_project_wedges")
+        return out
+
     # -- results
     def check_status(self):
         s = self.b.status.cpu().numpy()

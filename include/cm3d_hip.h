@@ -210,6 +210,19 @@ int cm3d_project_hit_rows(const void *workspace, int64_t workspace_bytes, int32_
  *       [5..7] zero. */
 int cm3d_project_culling(const void *workspace, int64_t workspace_bytes, int32_t n_frames, int32_t max_pts_per_frame,
                          int32_t planes, int32_t *out, cm3d_stream_t stream);
+/* Accounting aid for the tests of the view wedges (added within ABI v5: a new symbol, no existing call changes; nothing on the
+ * path calls it; synchronous): the planes the per-frame table kernel of the last cm3d_(sweep_)project_hits on `stream` wrote.
+ * A camera's wedge is two planes through its centre; a point p (global) is looked at for that camera only while
+ * min(n_L . p + d_L, n_R . p + d_R) >= 0.  The planes stand on a pixel-column interval [u_lo, u_hi]: the hull of the columns of
+ * the camera's non-empty eroded masks in this frame, [min bb.x - pad, max bb.z + 1 + pad] clamped to [0, W], where pad is the
+ * camera's pixel bound on the exact chain's column (at least 1 + ceil(2 max(fx, fy) delta / zmin)); the whole image, [0, W], for
+ * a camera without such a bound (zmin <= 0.1, a composition that is not a rotation to 1e-5) or without a non-empty mask.  The
+ * wedge only ever culls work: no point outside the columns of a camera's masks can land in one of them.
+ *  out  float[n_frames][CM3D_MAX_CAMS][8]: n_L (unit, 3), d_L + margin, n_R (3), d_R + margin.  A record the derivation does not
+ *       cover (skew, a non-trivial last row of K', stages that are not rigid) reads (0, 0, 0, 1) twice -- every point is inside --,
+ *       a slot beyond n_cams (0, 0, 0, -1) twice -- none is. */
+int cm3d_project_wedges(const void *workspace, int64_t workspace_bytes, int32_t n_frames, int32_t max_pts_per_frame,
+                        int32_t planes, float *out, cm3d_stream_t stream);
 int cm3d_project_hits(const float *points, const int32_t *pt_off, int32_t n_frames, int32_t max_pts_per_frame,
                       int32_t n_points_total, const float *cams, int32_t n_cams, const int32_t *mask_off,
                       const int32_t *mask_cam, const int32_t *bbox, const uint32_t *packed, int32_t n_masks,
