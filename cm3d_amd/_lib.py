@@ -119,6 +119,8 @@ SIGNATURES = {
                                  _i64, _p]),
     "cm3d_box_tracks_workspace_bytes": (_i64, [_i32]),
     "cm3d_box_tracks": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "cm3d_box_place": (_i32, [_p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32, C.c_double, _i32, _p, _p, _p]),
+    "cm3d_lift_pass_placed": (_i32, [_p, _p, _p, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order
@@ -174,6 +176,11 @@ class RotatedNmsDesc(C.Structure):
 class LiftPassOptions(C.Structure):
     """cm3d_lift_pass_options of include/cm3d_hip.h, field for field: pointers to the descriptors above, NULL for a stage that is off."""
     _fields_ = [("size", _i64)] + [(n, _p) for n in ("cluster", "filter", "yaw", "nms")]
+
+
+class BoxPlaceDesc(C.Structure):
+    """cm3d_box_place_desc of include/cm3d_hip.h, field for field."""
+    _fields_ = [("size", _i64), ("place_src", _p), ("place_pushed", _p), ("ev", _p * 2), ("thin", C.c_double)]
 
 
 class Cm3dError(RuntimeError):

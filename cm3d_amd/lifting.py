@@ -25,6 +25,7 @@ from ._lib import Cm3dError, check
 from .drivable import Stage2Filters  # noqa: F401  (LiftEngine(filters=Stage2Filters(...)))
 from .cluster import DepthCluster  # noqa: F401  (LiftEngine(cluster=DepthCluster(...)))
 from .bevfit import YawFit, angle_table  # noqa: F401  (LiftEngine(yaw=YawFit(...)))
+from .boxplace import BoxPlace  # noqa: F401  (LiftEngine(yaw=YawFit(...), place=BoxPlace(...)))
 from .nms import RotatedNms  # noqa: F401  (LiftEngine(nms=RotatedNms(...)))
 from .velocity import Velocity, link_table  # noqa: F401  (LiftEngine(velocity=Velocity(...)))
 from .tracks import Tracks  # noqa: F401  (LiftEngine(velocity=Velocity(...), tracks=Tracks(...)))
@@ -451,7 +452,7 @@ class LiftEngine:
     def __init__(self, device="cuda:0", classes: Optional[ClassTable] = None, min_dist=MIN_DIST,
                  hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
                  cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None,
-                 velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None):
+                 velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None, place: Optional[BoxPlace] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -470,6 +471,10 @@ class LiftEngine:
         yaw: the yaw fit (bevfit.YawFit; nuScenes and Waymo batches -- KITTI's yaw comes from cm3d_obb), on the clustered lists and the
         kept positions where the engine has those.  download() adds `yaw_src`, `fit_status`, `fit_k` and `fit_rect`, and column 5 of
         `box` holds the yaw that was used.
+        place: the placement from the fitted rectangle (boxplace.BoxPlace; needs `yaw`): columns 0 and 1 of the boxes whose yaw was
+        fitted come from the rectangle's sensor-side corner and faces instead of the view-ray push, and the circle NMS is decided again
+        on the new centres (cm3d_box_place, enqueued by cm3d_lift_pass_placed in front of the rotated NMS).  download() adds `place_src`
+        and `place_pushed`.  None: no buffer, no launch.
         velocity: the box velocity stage (velocity.Velocity; nuScenes batches, whose boxes are in the global frame): a call of its own
         behind the pass (cm3d_box_velocity) associates the kept boxes of consecutive frames.  It needs batches with `frame_next` and
         `frame_time`; download() adds `vel`, `vel_src`, `next_match` and `prev_match`.  None: no buffer, no call.
@@ -496,6 +501,9 @@ class LiftEngine:
         self.tracks = tracks if tracks is not None and tracks.active else None
         if self.tracks is not None and self.velocity is None:
             raise ValueError("tracks=Tracks(...) follows the matches of the velocity stage: it needs velocity=Velocity(...)")
+        self.place = place if place is not None and place.active else None
+        if self.place is not None and self.yaw is None:
+            raise ValueError("place=BoxPlace(...) places boxes from the rectangles of the yaw fit: it needs yaw=YawFit(...)")
         _verify_matrix_pipe(self.lib, self.dev)
         self.b = None
         self._lane = None                                    # the lane tables on the device and their spatial index (upload)
@@ -629,6 +637,8 @@ class LiftEngine:
             b.fit_k = e(M); b.fit_status = e(M); b.fit_rect = e(M, _lib.MATCH_BOX_STRIDE, dtype=torch.float64)
             b.yaw_tab = e(M, 3, dtype=torch.float32); b.yaw_idx = e(M); b.yaw_src = e(M)
             b.yaw_tab_off = t(np.array([0, M], np.int32)); b.yaw_tab_frame = torch.zeros(F, dtype=torch.int32, device=d)
+        if self.place is not None:
+            b.place_src = e(M); b.place_pushed = e(M, 2, dtype=torch.float64)
         if self.velocity is not None:
             if hb.frame_next is None or hb.frame_time is None:
                 raise ValueError("the velocity stage needs HostBatch.frame_next and frame_time (the batch was assembled without the "
@@ -671,6 +681,8 @@ class LiftEngine:
             setattr(b, name + "_desc", desc)
             setattr(b.opts, name, ctypes.addressof(desc))
         b.timed = {name: desc for name, desc in stages.items() if name != "nms"}
+        if self.place is not None:             # (no member of the options: cm3d_lift_pass_placed takes it beside them; its events come last)
+            b.place_desc = b.timed["place"] = self._place_descriptor(b)
         b.opts_ref = ctypes.byref(b.opts) if stages else None
         b.plain_pass = not stages and self.velocity is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
         self.b = b
@@ -733,6 +745,13 @@ class LiftEngine:
         y.K, y.min_points = self.yaw.angles, self.yaw.min_points
         y.d0, y.min_length, y.lane_min_dist = self.yaw.d0, self.yaw.min_length, self.yaw.lane_min_dist
         return y
+
+    def _place_descriptor(self, b):
+        """cm3d_box_place_desc of the resident batch (refresh_pass_descriptor sets its events)."""
+        p = _lib.BoxPlaceDesc()
+        p.size = ctypes.sizeof(_lib.BoxPlaceDesc)
+        p.place_src, p.place_pushed, p.thin = _ptr(b.place_src), _ptr(b.place_pushed), self.place.thin
+        return p
 
     def _nms_descriptor(self):
         """cm3d_rotated_nms_desc of the engine: what cm3d_box_rotated_nms takes beyond the pass descriptor."""
@@ -1010,6 +1029,14 @@ class LiftEngine:
                                             int(b.pose_inv is not None), min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), st),
               "cm3d_box_rotated_nms")
 
+    def stage_place(self, st):
+        """cm3d_box_place alone, on the box rows, flags and rectangles the yaw-fitted pass left resident."""
+        b, p = self.b, self.b.place_desc
+        check(self.lib.cm3d_box_place(_ptr(b.box), _ptr(b.flags), _ptr(b.mask_off), b.F, b.M, _ptr(b.fit_rect), _ptr(b.yaw_src),
+                                      _ptr(self.prior_wlh), _ptr(self.nms_group), _ptr(self.nms_thr), len(self.classes.names), _ptr(b.ego_xyz),
+                                      int(b.pose_inv is not None), p.thin, min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), p.place_src,
+                                      p.place_pushed, st), "cm3d_box_place")
+
     def stage_velocity(self, st):
         """The opt-in velocity stage on the box rows and flags the pass (its rotated NMS included) left (cm3d_box_velocity)."""
         b, v = self.b, self.velocity
@@ -1036,8 +1063,9 @@ class LiftEngine:
         the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them.
         Each opt-in stage the engine has appends two more behind those, in this order: around the filter launch (the "drivable"
         bucket), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
-        the yaw fit's two launches (the "yawfit" bucket; behind the fifth event).  One library call enqueues the pass, opt-in stages
-        included (cm3d_lift_pass_opt; include/cm3d_hip.h states the order); no allocation, no synchronisation."""
+        the yaw fit's two launches (the "yawfit" bucket; behind the fifth event), around the placement's launch (the "place" bucket;
+        behind the yaw fit's boxes).  One library call enqueues the pass, opt-in stages included (cm3d_lift_pass_opt, or
+        cm3d_lift_pass_placed with a placement; include/cm3d_hip.h states the order); no allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
             self.start_lane_grid()
@@ -1047,8 +1075,11 @@ class LiftEngine:
             omarks = {name: [torch.cuda.Event(enable_timing=True) for _ in range(2)] for name in self.b.timed}
             stage_events.extend(marks + [ev for pair in omarks.values() for ev in pair])
         st = torch.cuda.current_stream(self.dev).cuda_stream
-        check(self.lib.cm3d_lift_pass_opt(self.refresh_pass_descriptor(dense, project_events, marks, omarks), self.b.opts_ref, st),
-              "cm3d_lift_pass_opt")
+        desc = self.refresh_pass_descriptor(dense, project_events, marks, omarks)
+        if self.place is None:
+            check(self.lib.cm3d_lift_pass_opt(desc, self.b.opts_ref, st), "cm3d_lift_pass_opt")
+        else:                                            # the same pass, the placement in front of its rotated NMS
+            check(self.lib.cm3d_lift_pass_placed(desc, self.b.opts_ref, ctypes.byref(self.b.place_desc), st), "cm3d_lift_pass_placed")
         if self.velocity is not None:                    # behind the pass, on its final kept set: one more library call
             self.stage_velocity(st)
         if self.tracks is not None:                      # behind the velocity stage, on its matches: one more
@@ -1213,8 +1244,11 @@ class LiftEngine:
 
     def _yaw_results(self):
         b = self.b
-        return dict(yaw_src=b.yaw_src.cpu().numpy(), fit_status=b.fit_status.cpu().numpy(), fit_k=b.fit_k.cpu().numpy(),
-                    fit_rect=b.fit_rect.cpu().numpy())
+        out = dict(yaw_src=b.yaw_src.cpu().numpy(), fit_status=b.fit_status.cpu().numpy(), fit_k=b.fit_k.cpu().numpy(),
+                   fit_rect=b.fit_rect.cpu().numpy())
+        if self.place is not None:
+            out.update(place_src=b.place_src.cpu().numpy(), place_pushed=b.place_pushed.cpu().numpy())
+        return out
 
 
 class LiftPipeline:

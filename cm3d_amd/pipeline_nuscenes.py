@@ -20,6 +20,7 @@ import torch
 from . import cluster as clmod
 from . import nms as nmsmod
 from . import bevfit
+from . import boxplace
 from . import dist as cdist
 from . import lifting, nusc_io
 from . import velocity as velmod
@@ -224,7 +225,7 @@ def _token_batches(batches, index, host_s):
 
 
 def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                  velocity=None, vel_out=None, tracks=None):
+                  velocity=None, vel_out=None, tracks=None, place=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
@@ -237,8 +238,11 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
     (velocity.Velocity), one call behind every pass; the (k, 2) velocities of the returned records (lifting.kept_box_velocities, same
     order) are appended to the list `vel_out` as ONE device tensor, and on_records gets a batch's share as a fourth argument.  tracks: the
     opt-in track stage (tracks.Tracks; with `velocity` only), one more call behind the velocity stage's: the records and velocities
-    collected here are already what it left."""
+    collected here are already what it left.  place: the opt-in placement (boxplace.BoxPlace; with `yaw` only); its two events come
+    behind the yaw fit's, and the time between them goes into a "place" bucket."""
     kw = {} if yaw is None else {"yaw": yaw}
+    if place is not None:
+        kw["place"] = place
     if velocity is not None:
         kw["velocity"] = velocity
     if tracks is not None:
@@ -246,7 +250,8 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
     vels = []
     pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms, **kw)
     n_f, n_c, n_y = (2 if filters is not None and filters.active else 0), (2 if cluster is not None else 0), (2 if yaw is not None else 0)
-    n_evs = 5 + n_f + n_c + n_y
+    n_p = 2 if place is not None else 0
+    n_evs = 5 + n_f + n_c + n_y + n_p
     records, pending, segments = [], [], []                            # pending: (slot, frame ids, stage events) in flight, oldest first
 
     def spent(key, since):
@@ -277,8 +282,10 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
                     dt = evs[5 + n_f].elapsed_time(evs[6 + n_f]) * 1e-3
                     timer["cluster"] = timer.get("cluster", 0.0) + dt
                     timer["medoid"] -= dt
-                if yaw is not None:                                    # the last two events, behind the pass
-                    timer["yawfit"] = timer.get("yawfit", 0.0) + evs[-2].elapsed_time(evs[-1]) * 1e-3
+                if yaw is not None:                                    # behind the pass
+                    timer["yawfit"] = timer.get("yawfit", 0.0) + evs[5 + n_f + n_c].elapsed_time(evs[6 + n_f + n_c]) * 1e-3
+                if place is not None:                                  # the last two events, behind the yaw fit's boxes
+                    timer["place"] = timer.get("place", 0.0) + evs[-2].elapsed_time(evs[-1]) * 1e-3
 
     try:
         for hb, ids, host_s in prepared:
@@ -310,7 +317,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
 
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                 scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None,
-                cluster=None, nms=None, yaw=None, velocity=None, vel_out=None, tracks=None):
+                cluster=None, nms=None, yaw=None, velocity=None, vel_out=None, tracks=None, place=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -344,7 +351,7 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
                 pool.join()
     with contextlib.closing(prepared()) as batches:
         return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms, yaw=yaw, velocity=velocity,
-                             vel_out=vel_out, tracks=tracks)
+                             vel_out=vel_out, tracks=tracks, place=place)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -422,7 +429,7 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
 
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                        scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                       velocity=None, vel_out=None, tracks=None):
+                       velocity=None, vel_out=None, tracks=None, place=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -465,7 +472,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 hb, rows = got
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
-        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw, velocity, vel_out, tracks)
+        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw, velocity, vel_out, tracks, place)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -499,12 +506,14 @@ def main(argv=None):
     clmod.add_arguments(ap)
     nmsmod.add_arguments(ap)
     bevfit.add_arguments(ap)
+    boxplace.add_arguments(ap)
     velmod.add_arguments(ap)
     trmod.add_arguments(ap)
     args = ap.parse_args(argv)
     cluster = clmod.from_namespace(args)
     nms = nmsmod.from_args(args)
     yaw = bevfit.from_namespace(args)
+    place = boxplace.from_namespace(args, ap)       # (--place fit without --yaw fit: an error of the command line)
     velocity = velmod.from_args(args)
     tracks = trmod.from_args(args, ap)              # (a track flag without --velocity track: an error of the command line)
     vel_mine = []                                  # with --velocity track: the velocities of this rank's records, one device tensor
@@ -582,7 +591,7 @@ def main(argv=None):
         mine = lift_scenes_native(nt, names[lo:hi], args.mask_dir, classes, device, row_to_out, args.n_sweeps, args.ratio, args.masks, timer,
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
                                   on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
-                                  velocity=velocity, vel_out=vel_mine, tracks=tracks)
+                                  velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
@@ -591,7 +600,7 @@ def main(argv=None):
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
                            token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
-                           velocity=velocity, vel_out=vel_mine, tracks=tracks)
+                           velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.

@@ -28,6 +28,7 @@ import torch
 from . import cluster as clmod
 from . import nms as nmsmod
 from . import bevfit
+from . import boxplace
 from . import dist as cdist
 from . import lifting
 from . import waymo as wm
@@ -130,7 +131,9 @@ def main(argv=None):
     clmod.add_arguments(ap)
     nmsmod.add_arguments(ap)
     bevfit.add_arguments(ap)
+    boxplace.add_arguments(ap)
     args = ap.parse_args(argv)
+    place = boxplace.from_namespace(args, ap)       # (--place fit without --yaw fit: an error of the command line)
     filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
     rank, world, local_rank = cdist.init_from_env()
@@ -142,7 +145,7 @@ def main(argv=None):
     pri = json.load(open(args.priors)) if os.path.exists(args.priors) else None
     classes = lifting.ClassTable.waymo(pri)
     eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args),
-                             nms=nmsmod.from_args(args), yaw=bevfit.from_namespace(args))
+                             nms=nmsmod.from_args(args), yaw=bevfit.from_namespace(args), place=place)
     lo, hi = cdist.shard_range(len(scenes), rank, world)
     mine, meta = [], {}
     for si in range(lo, hi):

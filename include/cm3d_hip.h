@@ -1028,6 +1028,67 @@ int cm3d_box_tracks(double *box, int32_t *flags, const int32_t *mask_frame, cons
                     int32_t smooth_window, int32_t *track_id, int32_t *track_pos, int32_t *track_len, double *track_stat,
                     double *vel_smooth, int32_t *status, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
 
+/* ---- box centre from the fitted rectangle instead of the view-ray push (opt-in; behind the yaw fit) -------------------
+ * Added within ABI v5: new symbols only, so CM3D_ABI_VERSION stays.  The box launch puts a vehicle's centre at the medoid pushed
+ * along the view ray by min(|w / 2 sin|, |l / 2 cos|) (push_centroid, src/nuscenes/2d_to_3d.py:164-198): a guess that never looks
+ * at where the faces are.  cm3d_bev_fit leaves the bounding rectangle of a mask's points at the fitted angle; its sensor-side corner
+ * is a corner of the object and its sensor-side edges are faces.  This stage hangs the class's length and width on them.  What it
+ * does to label quality has not been measured, and `thin` is not tuned.  Host statement to the bit, NMS included:
+ * cm3d_amd.boxplace.box_place_host.  All float64, every product, sum and difference rounded on its own, no fma, no library call.
+ *
+ *  Placed.  Mask m of frame f is placed iff flags[m] & 1, yaw_src[m] == 1, and the sensor and the six record values are finite.
+ *           cx, cy, a, b, hc, hs = fit_rect[m];  c = box[m][8] >= 0 && box[m][8] < n_classes ? (int)box[m][8] : 0 (as
+ *           cm3d_box_rotated_nms reads it);  len = prior_wlh[3 c + 1], wid = prior_wlh[3 c + 0] (length along the heading);
+ *           sensor (sx, sy) = ego_xyz[3 f], ego_xyz[3 f + 1] (nuScenes: lists, rectangles and boxes are global), or (0, 0) when
+ *           waymo != 0 (all three in the vehicle frame; ego_xyz is not read and may be NULL).
+ *             ex = sx - cx;  ey = sy - cy;  pu = (ex*hc) + (ey*hs);  pv = (ey*hc) - (ex*hs)
+ *             su = pu >= 0 ? 1.0 : -1.0;  sv = pv >= 0 ? 1.0 : -1.0
+ *             au = b >= thin   (two faces seen: the corner fixes the box along the heading);   av = a >= thin
+ *             du = au ? su * ((a - len) * 0.5) : 0.0   (not anchored: centred on the face);    dv = av ? sv * ((b - wid) * 0.5) : 0.0
+ *             x = ((du*hc) - (dv*hs)) + cx;  y = ((du*hs) + (dv*hc)) + cy
+ *           The rule is the same under (hc, hs) -> (-hc, -hs): the axis sign cm3d_yaw_select resolved is not needed.
+ *           box[m][0] = x, box[m][1] = y; columns 2..8 are untouched (z stays the medoid's).  place_src[m]: 1 both axes anchored,
+ *           2 one, 3 none.  A mask that is not placed keeps columns 0..8 bit for bit and gets place_src 0.
+ *  place_pushed double[n_masks][2] OUT: box[m][0], box[m][1] as they were on entry, for every mask
+ *  place_src    int32[n_masks] OUT, written whole
+ *  thin         finite, >= 0 (0: both axes always anchored); NaN, negative or infinite: CM3D_ERR_ARG
+ *  NMS.     The circle NMS of the box launch ran on the pushed centres; it is decided again here, in the same launch, on the
+ *           centres as they now are: descending score, ties by descending index, group nms_group[c], dist^2 <= nms_thr[group],
+ *           only masks with flags & 1 (cm3d_box_nms's rule and code).  Bit 1 of flags and column 9 of box are rewritten for
+ *           EVERY mask of the batch; bit 0 stays.  max_masks_per_frame as in cm3d_box_nms_bounded: the launch's LDS is sized by
+ *           it (none up to 64), and the masks of a frame beyond it are not placed and not kept.
+ *  mask_off int32[F+1]; a frame's start is clamped to [0, n_masks] and its end to [start, n_masks] before use
+ * CM3D_ERR_ARG and no launch: a NULL array (ego_xyz only when waymo == 0), a non-positive n_frames, n_masks, n_classes or
+ * max_masks_per_frame, a bad thin.  One launch, k_box_place<WAYMO>, one wave per frame; plain stores, no atomics, no workspace. */
+int cm3d_box_place(double *box, int32_t *flags, const int32_t *mask_off, int32_t n_frames, int32_t n_masks, const double *fit_rect,
+                   const int32_t *yaw_src, const double *prior_wlh, const int32_t *nms_group, const double *nms_thr, int32_t n_classes,
+                   const double *ego_xyz, int32_t waymo, double thin, int32_t max_masks_per_frame, int32_t *place_src,
+                   double *place_pushed, cm3d_stream_t stream);
+
+typedef struct cm3d_box_place_desc {       /* what the placed pass needs beyond the pass descriptor and the options */
+    int64_t size;                          /* sizeof(cm3d_box_place_desc); another value: CM3D_ERR_ARG */
+    int32_t *place_src; double *place_pushed;
+    void *ev[2];                           /* optional hipEvent_t, recorded in front of and behind cm3d_box_place */
+    double thin;
+} cm3d_box_place_desc;
+
+/* The composed pass with the placement (host code, csrc/pass_place.cpp; cm3d_lift_pass_options has no member for it and
+ * csrc/pass_options.cpp does not know it).  Enqueues on `stream`, stopping at and returning the first error; no descriptor of the
+ * caller's is written:
+ *
+ *   checked first, CM3D_ERR_ARG and NO call at all: desc, opt or place NULL or of a wrong `size`; opt->yaw NULL, of a wrong size or
+ *   without fit_rect or yaw_src; place_src or place_pushed NULL; a bad thin; opt->nms given but of a wrong size or without thr
+ *   cm3d_lift_pass_opt(desc, opt')        opt' = a copy of opt with nms = NULL: cluster, filter and yaw as stated there (it checks
+ *                                         their descriptors before its first call)
+ *   record place->ev[0]
+ *   cm3d_box_place                        box, flags, mask_off, prior_wlh, nms_group, nms_thr, ego_xyz ... of desc; fit_rect, yaw_src of
+ *                                         opt->yaw; waymo = pose_inv != NULL; bound as the box launch's
+ *   record place->ev[1]
+ *   opt->nms ?  cm3d_box_rotated_nms      as in cm3d_lift_pass_opt: it judges the placed boxes and overwrites the circle NMS's verdict
+ *   behind the pass, calls of the caller's own as before: cm3d_box_velocity (its centres are the placed ones), cm3d_box_tracks */
+int cm3d_lift_pass_placed(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, const cm3d_box_place_desc *place,
+                          cm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
