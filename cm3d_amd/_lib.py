@@ -121,6 +121,9 @@ SIGNATURES = {
     "cm3d_box_tracks": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "cm3d_box_place": (_i32, [_p, _p, _p, _i32, _i32, _p, _p, _p, _p, _p, _i32, _p, _i32, C.c_double, _i32, _p, _p, _p]),
     "cm3d_lift_pass_placed": (_i32, [_p, _p, _p, _p]),
+    "cm3d_box_size_workspace_bytes": (_i64, [_i32]),
+    "cm3d_box_size": (_i32, [_p, _p, _p, _p, _p, _p, _i32, _p, _i32, C.c_double, _p, _p, _p, _p, _p, _p, _i32, _i32, C.c_double, _i32,
+                             C.c_double, _i32, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order

@@ -5,6 +5,7 @@
 // Plain C++17 + pthreads; no HIP, no Python.
 #include "../../include/cm3d_reader.h"
 #include "../../include/cm3d_reader_velocity.h"
+#include "../../include/cm3d_reader_size.h"
 
 #include <atomic>
 #include <limits>
@@ -1207,8 +1208,9 @@ void py_float_repr(double x, std::string &out)
     }
 }
 
-// cm3d_write_results_json (vel == NULL) and cm3d_write_results_json_vel, whose comments state the arguments
-int64_t write_results_json(const double *records, const double *vel, int64_t n, const char *tokens, int32_t n_tokens,
+// cm3d_write_results_json (vel == NULL), cm3d_write_results_json_vel and cm3d_write_results_json_sized (size != NULL), whose comments
+// state the arguments
+int64_t write_results_json(const double *records, const double *vel, const double *size, int64_t n, const char *tokens, int32_t n_tokens,
                            const char *const *cls_mid, const char *const *cls_score, const char *const *cls_tail, int32_t n_classes,
                            const char *prefix, char *out, int64_t cap);
 
@@ -1225,7 +1227,7 @@ extern "C" int64_t cm3d_write_results_json(const double *records, int64_t n, con
                                            const char *const *cls_score, const char *const *cls_tail, int32_t n_classes, const char *prefix,
                                            char *out, int64_t cap)
 {
-    return write_results_json(records, nullptr, n, tokens, n_tokens, cls_mid, cls_score, cls_tail, n_classes, prefix, out, cap);
+    return write_results_json(records, nullptr, nullptr, n, tokens, n_tokens, cls_mid, cls_score, cls_tail, n_classes, prefix, out, cap);
 }
 
 // The same with a velocity per record (include/cm3d_reader_velocity.h): vel double[n][2], row i beside records row i.  Behind the
@@ -1237,12 +1239,24 @@ extern "C" int64_t cm3d_write_results_json_vel(const double *records, const doub
 {
     static const double none[2] = {0.0, 0.0};                   // (n == 0: nothing reads it)
     if (!vel && n) return 0;
-    return write_results_json(records, vel ? vel : none, n, tokens, n_tokens, cls_mid, cls_score, cls_tail, n_classes, prefix, out, cap);
+    return write_results_json(records, vel ? vel : none, nullptr, n, tokens, n_tokens, cls_mid, cls_score, cls_tail, n_classes, prefix, out, cap);
+}
+
+// The same with a size per record (include/cm3d_reader_size.h): size double[n][3], row i beside records row i.  Behind the translation
+// it writes '], "size": [w, l, h], "rotation": [' itself in place of cls_mid[class]; vel as above, or NULL with the cls_score of
+// cm3d_write_results_json.
+extern "C" int64_t cm3d_write_results_json_sized(const double *records, const double *vel, const double *size, int64_t n, const char *tokens,
+                                                 int32_t n_tokens, const char *const *cls_mid, const char *const *cls_score,
+                                                 const char *const *cls_tail, int32_t n_classes, const char *prefix, char *out, int64_t cap)
+{
+    static const double none[3] = {0.0, 0.0, 0.0};              // (n == 0: nothing reads it)
+    if (!size && n) return 0;
+    return write_results_json(records, vel, size ? size : none, n, tokens, n_tokens, cls_mid, cls_score, cls_tail, n_classes, prefix, out, cap);
 }
 
 namespace {
 
-int64_t write_results_json(const double *records, const double *vel, int64_t n, const char *tokens, int32_t n_tokens,
+int64_t write_results_json(const double *records, const double *vel, const double *size, int64_t n, const char *tokens, int32_t n_tokens,
                            const char *const *cls_mid, const char *const *cls_score, const char *const *cls_tail, int32_t n_classes,
                            const char *prefix, char *out, int64_t cap)
 {
@@ -1264,7 +1278,7 @@ int64_t write_results_json(const double *records, const double *vel, int64_t n, 
         std::vector<int64_t> cur(first.begin(), first.end() - 1);
         for (int64_t i = 0; i < n; ++i) order[cur[(int64_t)records[10 * i + 5]]++] = i;
         std::string s;
-        s.reserve((size_t)(n * 330 + n_tokens * 48 + 256));
+        s.reserve((size_t)(n * 400 + n_tokens * 48 + 256));
         if (prefix) s += prefix;
         for (int ti = 0; ti < n_tokens; ++ti) {
             if (ti) s += ", ";
@@ -1275,7 +1289,13 @@ int64_t write_results_json(const double *records, const double *vel, int64_t n, 
                 if (q > first[ti]) s += ", ";
                 s += "{\"sample_token\": "; s += tok[ti]; s += ", \"translation\": [";
                 py_float_repr(r[0], s); s += ", "; py_float_repr(r[1], s); s += ", "; py_float_repr(r[2], s);
-                s += cls_mid[ci];
+                if (size) {
+                    const double *z = size + 3 * order[q];
+                    s += "], \"size\": ["; py_float_repr(z[0], s); s += ", "; py_float_repr(z[1], s); s += ", "; py_float_repr(z[2], s);
+                    s += "], \"rotation\": [";
+                } else {
+                    s += cls_mid[ci];
+                }
                 py_float_repr(r[3], s); s += ", 0.0, 0.0, "; py_float_repr(r[4], s);
                 if (vel) {
                     const double *v = vel + 2 * order[q];

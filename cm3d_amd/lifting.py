@@ -29,6 +29,7 @@ from .boxplace import BoxPlace  # noqa: F401  (LiftEngine(yaw=YawFit(...), place
 from .nms import RotatedNms  # noqa: F401  (LiftEngine(nms=RotatedNms(...)))
 from .velocity import Velocity, link_table  # noqa: F401  (LiftEngine(velocity=Velocity(...)))
 from .tracks import Tracks  # noqa: F401  (LiftEngine(velocity=Velocity(...), tracks=Tracks(...)))
+from .boxsize import BoxSize  # noqa: F401  (LiftEngine(yaw=..., place=..., velocity=..., size=BoxSize(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -452,7 +453,8 @@ class LiftEngine:
     def __init__(self, device="cuda:0", classes: Optional[ClassTable] = None, min_dist=MIN_DIST,
                  hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
                  cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None,
-                 velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None, place: Optional[BoxPlace] = None):
+                 velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None, place: Optional[BoxPlace] = None,
+                 size: Optional[BoxSize] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -481,7 +483,13 @@ class LiftEngine:
         tracks: the track stage (tracks.Tracks; needs `velocity`): one more call behind the velocity stage's (cm3d_box_tracks) follows
         the matches -- bit 1 of `flags`, columns 7 and 9 of `box` are what it leaves, download() adds `track_id`, `track_pos`,
         `track_len`, `track_stat` and, with a smoothing window, `vel_smooth`, which kept_box_velocities then returns.  None or at its
-        defaults: no buffer, no call."""
+        defaults: no buffer, no call.
+        size: the size stage (boxsize.BoxSize; needs `yaw`, `place` and `velocity`): one more call behind the track stage's
+        (cm3d_box_size) pools the fitted extents over every track, hangs the pooled length and width on the rectangle by the
+        placement's rule -- columns 0 and 1 of `box` are what it leaves -- and takes the velocity again on the new centres.  The track
+        stage then runs even at its defaults (`tracks=None` means Tracks()).  download() adds `size_wlh`, `size_src`, `size_ratio`,
+        `size_obs`, `size_placed` and `size_vel`; kept_box_sizes returns the rows of the kept boxes and kept_box_velocities those of
+        `size_vel`.  None: no buffer, no call.  Its four parameters are untuned."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -498,7 +506,15 @@ class LiftEngine:
         self.nms = nms if nms is not None and nms.active else None
         self.yaw = yaw if yaw is not None and yaw.active else None
         self.velocity = velocity if velocity is not None and velocity.active else None
-        self.tracks = tracks if tracks is not None and tracks.active else None
+        self.size = size if size is not None and size.active else None
+        if self.size is not None:
+            missing = [n for n, v in (("yaw=YawFit(...)", yaw), ("place=BoxPlace(...)", place), ("velocity=Velocity(...)", velocity))
+                       if v is None or not v.active]
+            if missing:
+                raise ValueError(f"size=BoxSize(...) pools the fitted extents over the tracks and places the boxes again: it needs {', '.join(missing)}")
+            self.tracks = tracks if tracks is not None else Tracks()        # the stage runs at its defaults too: the size stage reads its arrays
+        else:
+            self.tracks = tracks if tracks is not None and tracks.active else None
         if self.tracks is not None and self.velocity is None:
             raise ValueError("tracks=Tracks(...) follows the matches of the velocity stage: it needs velocity=Velocity(...)")
         self.place = place if place is not None and place.active else None
@@ -660,6 +676,12 @@ class LiftEngine:
             b.track_status = torch.zeros(1, dtype=torch.int32, device=d)
             b.track_ws_bytes = int(L.cm3d_box_tracks_workspace_bytes(M))
             b.track_ws = torch.empty(max(b.track_ws_bytes, 16), dtype=torch.uint8, device=d)
+        if self.size is not None:
+            b.size_wlh = e(M, 3, dtype=torch.float64); b.size_src = e(M); b.size_ratio = e(M, 2, dtype=torch.float64); b.size_obs = e(M, 2)
+            b.size_placed = e(M, 2, dtype=torch.float64); b.size_vel = e(M, 2, dtype=torch.float64)
+            b.size_status = torch.zeros(1, dtype=torch.int32, device=d)
+            b.size_ws_bytes = int(L.cm3d_box_size_workspace_bytes(M))
+            b.size_ws = torch.empty(max(b.size_ws_bytes, 16), dtype=torch.uint8, device=d)
         b.dense = dense_masks
         # The bulk data LAST: sweeps and run lengths come from page-locked staging buffers (cm3d_amd.reader) and copy
         # asynchronously; the small arrays above are pageable, their copies block the host until everything queued before them on
@@ -1054,6 +1076,17 @@ class LiftEngine:
                                        _ptr(b.track_pos), _ptr(b.track_len), _ptr(b.track_stat), _ptr(b.vel_smooth), _ptr(b.track_status),
                                        _ptr(b.track_ws), b.track_ws_bytes, st), "cm3d_box_tracks")
 
+    def stage_size(self, st):
+        """The opt-in size stage on the rectangles of the yaw fit, the placement's sources and the track stage's arrays; rewrites the
+        centres of the sized boxes in place (cm3d_box_size)."""
+        b, sz = self.b, self.size
+        check(self.lib.cm3d_box_size(_ptr(b.box), _ptr(b.flags), _ptr(b.mask_frame), _ptr(b.fit_rect), _ptr(b.place_src), _ptr(self.prior_wlh),
+                                     len(self.classes.names), _ptr(b.ego_xyz), 0, self.place.thin, _ptr(b.next_match), _ptr(b.prev_match),
+                                     _ptr(b.track_id), _ptr(b.track_pos), _ptr(b.track_len), _ptr(b.frame_time), b.M, b.F, self.velocity.max_dt,
+                                     self.tracks.smooth_window, sz.q, sz.min_obs, sz.lo, sz.hi, _ptr(b.size_wlh), _ptr(b.size_src),
+                                     _ptr(b.size_ratio), _ptr(b.size_obs), _ptr(b.size_placed), _ptr(b.size_vel), _ptr(b.size_status),
+                                     _ptr(b.size_ws), b.size_ws_bytes, st), "cm3d_box_size")
+
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
     def run(self, masks="dense", project_events=None, stage_events=None):
@@ -1084,6 +1117,8 @@ class LiftEngine:
             self.stage_velocity(st)
         if self.tracks is not None:                      # behind the velocity stage, on its matches: one more
             self.stage_tracks(st)
+        if self.size is not None:                        # behind the track stage, on its tracks: one more
+            self.stage_size(st)
 
     def capture_graph(self, masks="rle"):
         """Captures one pass over the resident batch into a HIP graph and returns it (`g.replay()` re-runs the pass
@@ -1158,6 +1193,12 @@ class LiftEngine:
                 raise Cm3dError("tracks: a next_match / prev_match lies outside the batch's masks")
             if v & 4:
                 raise Cm3dError("tracks: a match is not mutual, not kept or not forward in time")
+        if self.size is not None:
+            v = int(self.b.size_status.item())
+            if v & 1:
+                raise Cm3dError("size: a track array or a match is not what the track stage writes")
+            if v & 2:
+                raise Cm3dError("size: a track is longer than the batch has frames")
         return s
 
     def removed_rows(self):
@@ -1240,6 +1281,8 @@ class LiftEngine:
                        track_stat=b.track_stat.cpu().numpy())
             if b.vel_smooth is not None:
                 out["vel_smooth"] = b.vel_smooth.cpu().numpy()
+        if self.size is not None:
+            out.update({k: getattr(b, k).cpu().numpy() for k in ("size_wlh", "size_src", "size_ratio", "size_obs", "size_placed", "size_vel")})
         return out
 
     def _yaw_results(self):
@@ -1419,9 +1462,27 @@ def kept_box_records(b, frame_ids, device=None):
 
 def kept_box_velocities(b):
     """(k, 2) float64 velocities of the masks kept_box_records ships, in its order (an engine with Velocity(...); a device tensor).
-    With Tracks(smooth_window > 0): the rows of `vel_smooth`, the slope over the track's window, in place of the neighbours' difference."""
-    vel = getattr(b, "vel_smooth", None)
+    With Tracks(smooth_window > 0): the rows of `vel_smooth`, the slope over the track's window, in place of the neighbours' difference.
+    With BoxSize(...): the rows of `size_vel`, the same rule on the sized centres."""
+    vel = getattr(b, "size_vel", None)
+    if vel is None:
+        vel = getattr(b, "vel_smooth", None)
     return (b.vel if vel is None else vel)[(b.flags & 3) == 3].clone()
+
+
+def kept_box_sizes(b):
+    """(k, 3) float64 [w, l, h] of the masks kept_box_records ships, in its order (an engine with BoxSize(...); a device tensor)."""
+    return b.size_wlh[(b.flags & 3) == 3].clone()
+
+
+def _size_rows(size, n):
+    """The optional `size` of the writers: None, or (n, 3) float64 [w, l, h] rows beside the n records (kept_box_sizes)."""
+    if size is None:
+        return None
+    size = np.ascontiguousarray(size, np.float64).reshape(-1, 3)
+    if size.shape[0] != n:
+        raise ValueError(f"size: {size.shape[0]} rows for {n} records")
+    return size
 
 
 def _velocity_rows(vel, n):
@@ -1434,16 +1495,19 @@ def _velocity_rows(vel, n):
     return vel
 
 
-def nuscenes_boxes_from_records(rec, tokens, classes: Optional[ClassTable] = None, vel=None):
+def nuscenes_boxes_from_records(rec, tokens, classes: Optional[ClassTable] = None, vel=None, size=None):
     """Gathered records (numpy (k, 10), see kept_box_records) -> the reference's per-sample box dict lists (:808-817 after NMS
     :913-924): {sample_token: [box, ...]} with every token of `tokens` present ([] when a sample has no box, :845).
-    vel: None -- "velocity": [0, 0], the reference's constant --, or the records' (k, 2) velocities (kept_box_velocities): [vx, vy]."""
+    vel: None -- "velocity": [0, 0], the reference's constant --, or the records' (k, 2) velocities (kept_box_velocities): [vx, vy].
+    size: None -- "size": the class's prior --, or the records' (k, 3) [w, l, h] rows (kept_box_sizes)."""
     classes = classes or ClassTable.nuscenes()
     results = {t: [] for t in tokens}
     # plain Python floats / ints in one go (tolist), per-class constants built once: the loop below only assembles dicts
     rows = np.asarray(rec, np.float64).reshape(-1, _lib.BOX_STRIDE).tolist()
     vel = _velocity_rows(vel, len(rows))
     vels = vel.tolist() if vel is not None else None
+    size = _size_rows(size, len(rows))
+    own = size.tolist() if size is not None else None
     sizes = [[float(v) for v in wlh] for wlh in classes.prior_wlh]
     for k, r in enumerate(rows):
         token, ci = tokens[int(r[REC_FRAME_A])], int(r[8])
@@ -1451,7 +1515,7 @@ def nuscenes_boxes_from_records(rec, tokens, classes: Optional[ClassTable] = Non
         results[token].append({
             "sample_token": token,
             "translation": [r[0], r[1], r[2]],
-            "size": list(sizes[ci]),
+            "size": list(sizes[ci]) if own is None else own[k],
             "rotation": [r[3], 0.0, 0.0, r[4]],
             "velocity": [0, 0] if vels is None else vels[k],
             "detection_name": name,
@@ -1461,8 +1525,8 @@ def nuscenes_boxes_from_records(rec, tokens, classes: Optional[ClassTable] = Non
     return results
 
 
-def nuscenes_results_json(rec, tokens, classes: Optional[ClassTable] = None, meta=None, vel=None):
-    """The text json.dumps({"meta": meta, "results": nuscenes_boxes_from_records(rec, tokens, classes, vel)}) produces, written out
+def nuscenes_results_json(rec, tokens, classes: Optional[ClassTable] = None, meta=None, vel=None, size=None):
+    """The text json.dumps({"meta": meta, "results": nuscenes_boxes_from_records(rec, tokens, classes, vel, size)}) produces, written out
     directly from the records: same keys, key order, separators and float repr -- the writer of the reference (:929-930) without
     60 000 dicts and a generic encoder in between (tests/test_host_logic.py holds the two against each other)."""
     import json
@@ -1470,6 +1534,8 @@ def nuscenes_results_json(rec, tokens, classes: Optional[ClassTable] = None, met
     rows = np.asarray(rec, np.float64).reshape(-1, _lib.BOX_STRIDE).tolist()
     vel = _velocity_rows(vel, len(rows))
     vels = vel.tolist() if vel is not None else None
+    own = _size_rows(size, len(rows))
+    own = own.tolist() if own is not None else None
     tok_js = [json.dumps(t) for t in tokens]
     # everything of a box that only depends on its class, rendered once
     tail = []
@@ -1485,6 +1551,8 @@ def nuscenes_results_json(rec, tokens, classes: Optional[ClassTable] = None, met
     for k, r in enumerate(rows):
         ti, ci = int(r[REC_FRAME_A]), int(r[8])
         size, mid, end = tail[ci]
+        if own is not None:
+            size = f'[{fr(own[k][0])}, {fr(own[k][1])}, {fr(own[k][2])}]'
         x, y, z, qw, qz, sc = r[0], r[1], r[2], r[3], r[4], r[7]
         velocity = '"velocity": [0, 0], ' if vels is None else f'"velocity": [{fr(vels[k][0])}, {fr(vels[k][1])}], '
         if isfinite(x + y + z + qw + qz + sc):          # (a sum that overflows only sends a finite row down the careful branch)
@@ -1497,22 +1565,25 @@ def nuscenes_results_json(rec, tokens, classes: Optional[ClassTable] = None, met
     return f'{{"meta": {json.dumps(meta if meta is not None else {})}, "results": {{{body}}}}}', sum(len(b) for b in per)
 
 
-def nuscenes_results_json_native(rec, tokens, classes: Optional[ClassTable] = None, meta=None, part=None, vel=None) -> bytes:
+def nuscenes_results_json_native(rec, tokens, classes: Optional[ClassTable] = None, meta=None, part=None, vel=None, size=None) -> bytes:
     """nuscenes_results_json through the native writer (libcm3d_reader.so, cm3d_write_results_json): the same bytes
     (tests/test_reader.py), without a Python statement per box -- 60 000 boxes take milliseconds instead of a third of a second.
     part = (first, count): only the entries of tokens[first:first+count] (records whose column 5 lies in that range), without the
     file's head and tail -- the entry point formats every batch's share while the later batches are still on the GPU and joins
     the parts with ", " between nuscenes_results_json_head(meta) and b"}}".
     vel: None, or the (k, 2) velocities of the k records (of the part's records, with `part`): written by the entry point beside
-    cm3d_write_results_json that takes them (cm3d_write_results_json_vel)."""
+    cm3d_write_results_json that takes them (cm3d_write_results_json_vel).
+    size: None, or the (k, 3) [w, l, h] rows of the k records (of the part's records, with `part`): written by
+    cm3d_write_results_json_sized (include/cm3d_reader_size.h) in place of the class's prior."""
     import json
     from . import reader as rdmod
     classes = classes or ClassTable.nuscenes()
     vel = _velocity_rows(vel, np.asarray(rec).reshape(-1, _lib.BOX_STRIDE).shape[0])
+    size = _size_rows(size, np.asarray(rec).reshape(-1, _lib.BOX_STRIDE).shape[0])
     mid, score, tail = [], [], []
     for ci, name in enumerate(classes.names):
-        size = json.dumps([float(v) for v in classes.prior_wlh[ci]])
-        mid.append(f'], "size": {size}, "rotation": [')
+        prior = json.dumps([float(v) for v in classes.prior_wlh[ci]])
+        mid.append(f'], "size": {prior}, "rotation": [')
         # (with velocities the writer itself puts '], "velocity": [vx, vy' in front of this piece)
         score.append(('], "velocity": [0, 0' if vel is None else '') + f'], "detection_name": {json.dumps(name)}, "detection_score": ')
         tail.append(f', "attribute_name": {json.dumps(ATTRIBUTE_NAMES[name])}}}')
@@ -1522,7 +1593,7 @@ def nuscenes_results_json_native(rec, tokens, classes: Optional[ClassTable] = No
         rec = np.array(rec, np.float64).reshape(-1, _lib.BOX_STRIDE)
         rec[:, REC_FRAME_A] -= first
         tokens, prefix = tokens[first:first + count], None
-    return rdmod.write_results_json(rec, [json.dumps(t) for t in tokens], mid, score, tail, prefix, vel=vel)
+    return rdmod.write_results_json(rec, [json.dumps(t) for t in tokens], mid, score, tail, prefix, vel=vel, size=size)
 
 
 def nuscenes_results_json_head(meta=None) -> bytes:

@@ -549,6 +549,42 @@ def box_tracks(box, flags, mask_frame, next_match, prev_match, frame_time, min_l
     return res
 
 
+def box_size(box, flags, mask_frame, fit_rect, place_src, prior_wlh, ego_xyz, next_match, prev_match, track_id, track_pos, track_len,
+             frame_time, thin=0.5, max_dt=1.5, smooth_window=0, q=0.75, min_obs=2, lo=0.6, hi=1.5):
+    """The opt-in size stage on arrays (cm3d_box_size; boxsize.box_size_host states it and takes the same arguments): box, flags as the
+    placed pass and the track stage left them, fit_rect (M, 6), place_src (M,), prior_wlh (C, 3), ego_xyz (F, 3) or None (Waymo), the
+    match arrays of box_velocity, the track arrays of box_tracks, frame_time (F,).  Returns a dict of numpy arrays: size_wlh (M, 3),
+    size_src (M,), size_ratio (M, 2), size_obs (M, 2), size_placed (M, 2), size_vel (M, 2), the new `box`, `flags`, and `status` (int;
+    the bits of the header, not raised: a caller decides).  The four parameters' defaults are untuned."""
+    L = _lib.lib()
+    box = np.asarray(box, np.float64).reshape(-1, _lib.BOX_STRIDE)
+    M = box.shape[0]
+    tim = np.asarray(frame_time, np.float64).reshape(-1)
+    prior = np.asarray(prior_wlh, np.float64).reshape(-1, 3)
+    n = max(M, 1)
+    i32 = lambda a: _t(np.asarray(a, np.int32).reshape(M) if M else np.zeros(1, np.int32))
+    d_box, d_flags = _t(box if M else np.zeros((1, _lib.BOX_STRIDE))), i32(flags)
+    d_rect = _t(np.asarray(fit_rect, np.float64).reshape(M, _lib.MATCH_BOX_STRIDE) if M else np.zeros((1, _lib.MATCH_BOX_STRIDE)))
+    d_int = [i32(a) for a in (mask_frame, place_src, next_match, prev_match, track_id, track_pos, track_len)]
+    d_frm, d_src, d_nm, d_pm, d_tid, d_pos, d_len = d_int
+    d_prior, d_tim = _t(prior), _t(tim if tim.size else np.zeros(1))
+    d_ego = None if ego_xyz is None else _t(np.asarray(ego_xyz, np.float64).reshape(-1, 3))
+    wlh, ratio, placed, vel = (_e(n, w, dtype=torch.float64) for w in (3, 2, 2, 2))
+    src, obs = _e(n), _e(n, 2)
+    status = torch.zeros(1, dtype=torch.int32, device=_dev())
+    ws = _ws(L.cm3d_box_size_workspace_bytes(M))
+    check(L.cm3d_box_size(d_box.data_ptr(), d_flags.data_ptr(), d_frm.data_ptr(), d_rect.data_ptr(), d_src.data_ptr(), d_prior.data_ptr(),
+                          prior.shape[0], d_ego.data_ptr() if d_ego is not None else None, int(d_ego is None), float(thin), d_nm.data_ptr(),
+                          d_pm.data_ptr(), d_tid.data_ptr(), d_pos.data_ptr(), d_len.data_ptr(), d_tim.data_ptr(), M, tim.size, float(max_dt),
+                          int(smooth_window), float(q), int(min_obs), float(lo), float(hi), wlh.data_ptr(), src.data_ptr(), ratio.data_ptr(),
+                          obs.data_ptr(), placed.data_ptr(), vel.data_ptr(), status.data_ptr(), ws.data_ptr(), ws.numel(), _st()),
+          "cm3d_box_size")
+    f64 = lambda a, w: a.cpu().numpy().reshape(-1, w)[:M]
+    return dict(size_wlh=f64(wlh, 3), size_src=src.cpu().numpy().reshape(-1)[:M], size_ratio=f64(ratio, 2),
+                size_obs=obs.cpu().numpy().reshape(-1, 2)[:M], size_placed=f64(placed, 2), size_vel=f64(vel, 2),
+                box=f64(d_box, _lib.BOX_STRIDE), flags=d_flags.cpu().numpy().reshape(-1)[:M], status=int(status.item()))
+
+
 # ----------------------------------------------------------------------------- f4: SAM3D fusion matching
 def match_records(boxes7):
     """(n,7) [center_x, center_y, bottom_z, length, width, height, heading] -> (n,6) float64 records of

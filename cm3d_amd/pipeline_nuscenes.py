@@ -25,6 +25,7 @@ from . import dist as cdist
 from . import lifting, nusc_io
 from . import velocity as velmod
 from . import tracks as trmod
+from . import boxsize as szmod
 
 # module constants of the reference (:55-59)
 VER_NAME = "v1.0-trainval"
@@ -225,7 +226,7 @@ def _token_batches(batches, index, host_s):
 
 
 def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                  velocity=None, vel_out=None, tracks=None, place=None):
+                  velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
@@ -239,7 +240,10 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
     order) are appended to the list `vel_out` as ONE device tensor, and on_records gets a batch's share as a fourth argument.  tracks: the
     opt-in track stage (tracks.Tracks; with `velocity` only), one more call behind the velocity stage's: the records and velocities
     collected here are already what it left.  place: the opt-in placement (boxplace.BoxPlace; with `yaw` only); its two events come
-    behind the yaw fit's, and the time between them goes into a "place" bucket."""
+    behind the yaw fit's, and the time between them goes into a "place" bucket.  size: the opt-in size stage (boxsize.BoxSize; with `yaw`,
+    `place` and `velocity` only), one more call behind the track stage's: the (k, 3) sizes of the returned records (lifting.kept_box_sizes)
+    are appended to `size_out` as ONE device tensor the way the velocities are, on_records gets a batch's share as a fifth argument, and
+    the velocities are those on the sized centres."""
     kw = {} if yaw is None else {"yaw": yaw}
     if place is not None:
         kw["place"] = place
@@ -247,7 +251,9 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
         kw["velocity"] = velocity
     if tracks is not None:
         kw["tracks"] = tracks
-    vels = []
+    if size is not None:
+        kw["size"] = size
+    vels, sizes = [], []
     pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms, **kw)
     n_f, n_c, n_y = (2 if filters is not None and filters.active else 0), (2 if cluster is not None else 0), (2 if yaw is not None else 0)
     n_p = 2 if place is not None else 0
@@ -264,10 +270,14 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
             records.append(pipe.collect_records(slot, ids))           # stays on the device until the one gather at the end
             if velocity is not None:                                   # (the slot's stream has been synchronised)
                 vels.append(lifting.kept_box_velocities(pipe.engines[slot].b))
+            if size is not None:
+                sizes.append(lifting.kept_box_sizes(pipe.engines[slot].b))
             spent("gpu lifting", t1)
             if on_records is not None:
                 first = int(ids[0, 0]) if len(ids) else 0
                 extra = () if velocity is None else (vels[-1].cpu().numpy(),)
+                if size is not None:
+                    extra += (sizes[-1].cpu().numpy(),)
                 if len(ids) and np.array_equal(ids[:, 0], np.arange(first, first + len(ids))):
                     on_records(records[-1].cpu().numpy(), first, len(ids), *extra)
                 else:
@@ -310,6 +320,8 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
         _release(segments)
     if vel_out is not None and velocity is not None:
         vel_out.append(torch.cat(vels, 0) if vels else torch.zeros(0, 2, dtype=torch.float64, device=device))
+    if size_out is not None and size is not None:
+        size_out.append(torch.cat(sizes, 0) if sizes else torch.zeros(0, 3, dtype=torch.float64, device=device))
     if records:
         return torch.cat(records, 0)
     return torch.zeros(0, 10, dtype=torch.float64, device=device)
@@ -317,7 +329,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
 
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                 scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None,
-                cluster=None, nms=None, yaw=None, velocity=None, vel_out=None, tracks=None, place=None):
+                cluster=None, nms=None, yaw=None, velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -351,7 +363,7 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
                 pool.join()
     with contextlib.closing(prepared()) as batches:
         return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms, yaw=yaw, velocity=velocity,
-                             vel_out=vel_out, tracks=tracks, place=place)
+                             vel_out=vel_out, tracks=tracks, place=place, size=size, size_out=size_out)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -429,7 +441,7 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
 
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                        scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                       velocity=None, vel_out=None, tracks=None, place=None):
+                       velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -472,7 +484,8 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 hb, rows = got
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
-        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw, velocity, vel_out, tracks, place)
+        return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw, velocity, vel_out, tracks, place,
+                             size, size_out)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -509,6 +522,7 @@ def main(argv=None):
     boxplace.add_arguments(ap)
     velmod.add_arguments(ap)
     trmod.add_arguments(ap)
+    szmod.add_arguments(ap)
     args = ap.parse_args(argv)
     cluster = clmod.from_namespace(args)
     nms = nmsmod.from_args(args)
@@ -516,6 +530,8 @@ def main(argv=None):
     place = boxplace.from_namespace(args, ap)       # (--place fit without --yaw fit: an error of the command line)
     velocity = velmod.from_args(args)
     tracks = trmod.from_args(args, ap)              # (a track flag without --velocity track: an error of the command line)
+    size = szmod.from_args(args, ap)                # (--size track without --yaw fit --place fit --velocity track, or a --size-* flag alone: the same)
+    size_mine = []                                 # with --size track: the sizes of this rank's records, one device tensor
     vel_mine = []                                  # with --velocity track: the velocities of this rank's records, one device tensor
     filters = lifting.Stage2Filters.from_args(args.drivable_filter, args.lane_max_dist, args.vehicle_lane_max_dist)
 
@@ -575,23 +591,23 @@ def main(argv=None):
                 item = write_q.get()
                 if item is None:
                     return
-                rec_np, first, count, vel_np = item
+                rec_np, first, count, vel_np, size_np = item
                 t0 = time.time()
                 if rec_np is None or first != next_first[0]:
                     streamed[0] = False
                 elif streamed[0]:
-                    parts.append(lifting.nuscenes_results_json_native(rec_np, tokens, classes, None, part=(first, count), vel=vel_np))
+                    parts.append(lifting.nuscenes_results_json_native(rec_np, tokens, classes, None, part=(first, count), vel=vel_np, size=size_np))
                     next_first[0] = first + count
                 timer["write"] += time.time() - t0
         writer = threading.Thread(target=write_worker, daemon=True)
         writer.start()
 
-        def on_records(rec_np, first, count, vel_np=None):
-            write_q.put((rec_np, first, count, vel_np))
+        def on_records(rec_np, first, count, vel_np=None, size_np=None):
+            write_q.put((rec_np, first, count, vel_np, size_np))
         mine = lift_scenes_native(nt, names[lo:hi], args.mask_dir, classes, device, row_to_out, args.n_sweeps, args.ratio, args.masks, timer,
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
                                   on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
-                                  velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place)
+                                  velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
@@ -600,13 +616,14 @@ def main(argv=None):
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
                            token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
-                           velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place)
+                           velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.
     t0 = time.time()
     gathered = cdist.gather_records(mine, dst=0)
     gathered_vel = cdist.gather_records(vel_mine[0], dst=0) if velocity is not None else None      # rank order is sample order here too
+    gathered_size = cdist.gather_records(size_mine[0], dst=0) if size is not None else None
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
@@ -614,6 +631,7 @@ def main(argv=None):
         return 0
     rec = torch.cat([g.cpu() for g in gathered], 0).numpy()
     vel = torch.cat([g.cpu() for g in gathered_vel], 0).numpy() if velocity is not None else None
+    sizes = torch.cat([g.cpu() for g in gathered_size], 0).numpy() if size is not None else None
     timer["gather"] = time.time() - t0
 
     # the writer (:929-930): the records straight to the text json.dump would produce for the reference's dict of box lists
@@ -624,9 +642,9 @@ def main(argv=None):
             if streamed[0]:
                 f.write(lifting.nuscenes_results_json_head(dict(META)) + b", ".join(parts) + b"}}")
             else:
-                f.write(lifting.nuscenes_results_json_native(rec, tokens, classes, dict(META), vel=vel))
+                f.write(lifting.nuscenes_results_json_native(rec, tokens, classes, dict(META), vel=vel, size=sizes))
     else:
-        text, _ = lifting.nuscenes_results_json(rec, tokens, classes, dict(META), vel=vel)
+        text, _ = lifting.nuscenes_results_json(rec, tokens, classes, dict(META), vel=vel, size=sizes)
         with open(os.path.join(args.output_dir, args.output_name), "w") as f:
             f.write(text)
     timer["write"] += time.time() - t0

@@ -60,6 +60,9 @@ def lib():
         h.cm3d_tables_sample_links.restype, h.cm3d_tables_sample_links.argtypes = C.c_int, [p, p, i32, p, p]
         h.cm3d_write_results_json_vel.restype = i64
         h.cm3d_write_results_json_vel.argtypes = [p, p, i64, C.c_char_p, i32, p, p, p, i32, C.c_char_p, p, i64]
+        # include/cm3d_reader_size.h
+        h.cm3d_write_results_json_sized.restype = i64
+        h.cm3d_write_results_json_sized.argtypes = [p, p, p, i64, C.c_char_p, i32, p, p, p, i32, C.c_char_p, p, i64]
         _lib = h
     return _lib
 
@@ -443,22 +446,31 @@ class Manifest:
         raise ReaderError(rc, "cm3d_manifest_load_masks")
 
 
-def write_results_json(rec, tokens_json, cls_mid, cls_score, cls_tail, prefix, vel=None):
+def write_results_json(rec, tokens_json, cls_mid, cls_score, cls_tail, prefix, vel=None, size=None):
     """The text of the reference's result file (json.dump of the dict of box lists, :929-930) from the gathered box records,
     written natively (cm3d_write_results_json); see lifting.nuscenes_results_json for the Python form it must equal.
-    vel: (n, 2) float64 velocities beside the records -- cm3d_write_results_json_vel, with cls_score as that entry point takes it."""
+    vel: (n, 2) float64 velocities beside the records -- cm3d_write_results_json_vel, with cls_score as that entry point takes it.
+    size: (n, 3) float64 [w, l, h] beside the records -- cm3d_write_results_json_sized, which writes them in place of cls_mid."""
     L = lib()
     rec = np.ascontiguousarray(rec, np.float64).reshape(-1, 10)
     if vel is not None:
         vel = np.ascontiguousarray(vel, np.float64).reshape(-1, 2)
         if vel.shape[0] != rec.shape[0]:
             raise ReaderError(ERR_ARG, "cm3d_write_results_json_vel: one velocity per record")
+    if size is not None:
+        size = np.ascontiguousarray(size, np.float64).reshape(-1, 3)
+        if size.shape[0] != rec.shape[0]:
+            raise ReaderError(ERR_ARG, "cm3d_write_results_json_sized: one size per record")
     blob = b"".join(t.encode() + b"\0" for t in tokens_json)
     a, b, c = _paths(cls_mid), _paths(cls_score), _paths(cls_tail)
-    cap = int(rec.shape[0]) * (360 if vel is None else 410) + len(blob) * 2 + len(prefix or "") + 256
+    cap = int(rec.shape[0]) * ((360 if vel is None else 410) + (0 if size is None else 70)) + len(blob) * 2 + len(prefix or "") + 256
     for _ in range(2):
         out = C.create_string_buffer(cap)
-        if vel is None:
+        if size is not None:
+            n = L.cm3d_write_results_json_sized(rec.ctypes.data if rec.size else None, vel.ctypes.data if vel is not None and vel.size else None,
+                                                size.ctypes.data if size.size else None, rec.shape[0], blob, len(tokens_json), a, b, c,
+                                                len(cls_mid), None if prefix is None else prefix.encode(), out, cap)
+        elif vel is None:
             n = L.cm3d_write_results_json(rec.ctypes.data if rec.size else None, rec.shape[0], blob, len(tokens_json), a, b, c, len(cls_mid),
                                           None if prefix is None else prefix.encode(), out, cap)
         else:

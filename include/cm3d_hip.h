@@ -1089,6 +1089,77 @@ typedef struct cm3d_box_place_desc {       /* what the placed pass needs beyond 
 int cm3d_lift_pass_placed(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, const cm3d_box_place_desc *place,
                           cm3d_stream_t stream);
 
+/* ---- box size from the fitted extents, pooled over each track (opt-in; a call of its own BEHIND cm3d_box_tracks) ------
+ * Added within ABI v5: new symbols only, so CM3D_ABI_VERSION stays.  Every box has the size of its class prior.  cm3d_bev_fit
+ * leaves the extents of a vehicle's points at the fitted heading; one frame sees one or two faces, often cut short, so one frame's
+ * extent is a lower bound with outliers, but over a track (cm3d_box_tracks) the object is seen from several sides, and an upper
+ * quantile of the extents estimates the object itself.  This stage pools them per track, hangs the pooled size on the rectangle by
+ * cm3d_box_place's rule, and takes the velocity again on the new centres.  The defaults q = 0.75, min_obs = 2, lo = 0.6, hi = 1.5
+ * are UNTUNED, and what the stage does to label quality has not been measured (it cannot be on synthetic scenes).  Host statement to
+ * the bit: cm3d_amd.boxsize.box_size_host.  All float64, every product, quotient, sum and difference rounded on its own, no fma, no
+ * library call.  M = n_masks, F = n_frames.
+ *
+ *  box, flags  double[M][CM3D_BOX_STRIDE], int32[M], IN/OUT: only box[i][0] and box[i][1] are ever written; flags is not read
+ *  mask_frame  int32[M];  frame_time double[F] seconds;  max_dt as cm3d_box_velocity takes them
+ *  fit_rect    double[M][6] as cm3d_bev_fit left it (cx, cy, a, b, hc, hs);  place_src int32[M] as cm3d_box_place left it
+ *  prior_wlh   double[n_classes][3];  ego_xyz double[F][3], waymo, thin: exactly as cm3d_box_place takes them
+ *  next_match, prev_match int32[M] as cm3d_box_velocity left them;  track_id, track_pos, track_len int32[M] as cm3d_box_tracks did
+ *
+ *  Members. Mask i is a member iff track_len[i] > 0, 0 <= track_id[i] < M, 0 <= track_pos[i] < track_len[i] and
+ *           0 <= mask_frame[i] < F.  Its frame time is frame_time[mask_frame[i]].
+ *  Links.   The follower of a member i is j = next_match[i] iff 0 <= j < M, j is a member, track_id[j] == track_id[i] and
+ *           track_pos[j] == track_pos[i] + 1.  The predecessor is p = prev_match[i] iff 0 <= p < M, p is a member of the same track_id
+ *           and track_pos[p] == track_pos[i] - 1.  Any other value but -1 reads as "no link" and sets status bit 0.  A follower raises
+ *           the position by one, so whatever the arrays hold there is no cycle.
+ *  Tracks.  The track of a member i is walked from its head h = track_id[i] along the followers.  h must be a member with
+ *           track_id[h] == h and track_pos[h] == 0, and the walk must reach i within F steps; a member without such a head or
+ *           that the walk does not reach sets status bit 0, is a member WITHOUT A TRACK, observes nothing for others and gets the
+ *           ratios 1.0, not pooled, with size_obs 0.  A track has at most one box per frame: no walk takes more than F steps, and one
+ *           that is cut at F steps with a follower left sets status bit 1.  What cm3d_box_tracks writes sets neither bit.  No index
+ *           outside [0, M) or [0, F) addresses memory.
+ *  Observation of a member.  c = box[i][8] >= 0 && box[i][8] < n_classes ? (int)box[i][8] : 0 (as cm3d_box_place reads it);
+ *           len0 = prior_wlh[3 c + 1], wid0 = prior_wlh[3 c];  a = fit_rect[i][2], b = fit_rect[i][3].  Member i observes the length iff
+ *           place_src[i] != 0, len0 > 0 and lo <= rl <= hi with rl = a / len0 (NaN compares false), the width alike with
+ *           rw = b / wid0.  Ratios are pooled, not metres: a track's members may differ in class inside one NMS group.  An extent far
+ *           below the prior means the face was not seen, one far above it is background in the list; neither is an observation,
+ *           so the pooled value needs no clamp.
+ *  Pooling, per track and per dimension: v_0 .. v_{n-1} the observed ratios of the walk's members in track order.  n < min_obs: the
+ *           ratio is exactly 1.0 and the dimension is not pooled.  Else k = (int)(q * (double)(n - 1)) and the ratio is the v_p that has
+ *           exactly k of the others before it in the order (value, then track position): an order statistic, no interpolation.
+ *  Size.    A member with place_src != 0:  len = r_len * len0, wid = r_wid * wid0, size_wlh[i] = (wid, len, prior_wlh[3 c + 2]) -- the
+ *           height stays the prior's --, size_src[i] bit 0: the length was pooled, bit 1: the width was.  Every other mask of the batch
+ *           (no member, or a member that kept the lane's yaw): its class's prior row bit for bit and size_src 0.
+ *           size_ratio double[M][2] = (r_len, r_wid) and size_obs int32[M][2] = the two n for members, zeros elsewhere.
+ *  Centre.  A member with place_src != 0 whose sensor and six record values are finite (cm3d_box_place places no other mask): the
+ *           rule of cm3d_box_place above, bracket for bracket, with this len and wid for the prior's, the sensor of frame
+ *           mask_frame[i]; box[i][0] = x, box[i][1] = y.  It is computed from fit_rect and the sensor, never from the entry centre: a
+ *           second call on the same arrays gives the same centres.  size_placed double[M][2]: columns 0, 1 as on entry, every mask.
+ *           Columns 2..9 and flags are never written; no NMS is decided again (the tracks stand on the kept set as it is).
+ *  Velocity on the new centres, size_vel double[M][2]; zeros for masks that are no members.
+ *           smooth_window == 0: cm3d_box_velocity's rule with the follower and predecessor above: the first of central, forward,
+ *           backward whose links exist and whose span is <= max_dt, else zeros.
+ *           smooth_window = W > 0: cm3d_box_tracks' least-squares rule.  W' = min(W, F), p = track_pos[i], L = track_len[i]; the window
+ *           starts min(p, W') predecessors back (or where they end) and holds up to min(p, W') + 1 + min(L - 1 - p, W') members along
+ *           the followers (more than F: F, status bit 1); n the members it found; n < 2: zeros; else the six sums and the quotient
+ *           as stated there, with (double)n.
+ *
+ *  CM3D_ERR_ARG before any launch: n_masks < 0, n_frames <= 0, n_classes <= 0, q outside [0, 1] or NaN, min_obs < 1, not
+ *  0 < lo <= hi < inf, thin not finite or < 0, max_dt not > 0, smooth_window < 0, a NULL frame_time, prior_wlh or status, a NULL ego_xyz
+ *  with waymo == 0, a NULL array that M > 0 needs.  CM3D_ERR_WORKSPACE before any launch: workspace NULL or shorter than
+ *  cm3d_box_size_workspace_bytes(n_masks) (five doubles and three int32 per mask).  The first launch initialises the six pure outputs.
+ *  status      int32[1], zero it before the call; bits 0 and 1 above are only ever set
+ *  A NaN that an operation forms (a centre of inf - inf) has the implementation's sign and payload; every other value is the host's bits.
+ *  Launches: k_size_observe, k_size_pool, k_size_apply<WAYMO>, k_size_velocity, one thread per mask each.  Plain stores; the only
+ *  atomic is the status word's OR; no allocation, no read-back. */
+int64_t cm3d_box_size_workspace_bytes(int32_t n_masks);
+int cm3d_box_size(double *box, int32_t *flags, const int32_t *mask_frame, const double *fit_rect, const int32_t *place_src,
+                  const double *prior_wlh, int32_t n_classes, const double *ego_xyz, int32_t waymo, double thin,
+                  const int32_t *next_match, const int32_t *prev_match, const int32_t *track_id, const int32_t *track_pos,
+                  const int32_t *track_len, const double *frame_time, int32_t n_masks, int32_t n_frames, double max_dt,
+                  int32_t smooth_window, double q, int32_t min_obs, double lo, double hi, double *size_wlh, int32_t *size_src,
+                  double *size_ratio, int32_t *size_obs, double *size_placed, double *size_vel, int32_t *status, void *workspace,
+                  int64_t workspace_bytes, cm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
