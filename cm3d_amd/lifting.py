@@ -30,6 +30,7 @@ from .nms import RotatedNms  # noqa: F401  (LiftEngine(nms=RotatedNms(...)))
 from .velocity import Velocity, link_table  # noqa: F401  (LiftEngine(velocity=Velocity(...)))
 from .tracks import Tracks  # noqa: F401  (LiftEngine(velocity=Velocity(...), tracks=Tracks(...)))
 from .boxsize import BoxSize  # noqa: F401  (LiftEngine(yaw=..., place=..., velocity=..., size=BoxSize(...)))
+from .boxvertical import BoxVertical, RESULTS as VERTICAL_RESULTS  # noqa: F401  (LiftEngine(vertical=BoxVertical(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -454,7 +455,7 @@ class LiftEngine:
                  hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
                  cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None,
                  velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None, place: Optional[BoxPlace] = None,
-                 size: Optional[BoxSize] = None):
+                 size: Optional[BoxSize] = None, vertical: Optional[BoxVertical] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -489,7 +490,12 @@ class LiftEngine:
         placement's rule -- columns 0 and 1 of `box` are what it leaves -- and takes the velocity again on the new centres.  The track
         stage then runs even at its defaults (`tracks=None` means Tracks()).  download() adds `size_wlh`, `size_src`, `size_ratio`,
         `size_obs`, `size_placed` and `size_vel`; kept_box_sizes returns the rows of the kept boxes and kept_box_velocities those of
-        `size_vel`.  None: no buffer, no call.  Its four parameters are untuned."""
+        `size_vel`.  None: no buffer, no call.  Its four parameters are untuned.
+        vertical: the vertical stage (boxvertical.BoxVertical; nuScenes and Waymo batches, with any other option or none): one call
+        directly behind the pass (cm3d_box_vertical), in front of the velocity stage's, takes two order statistics of every in-mask
+        list's z -- the clustered lists when the engine clusters -- and rewrites column 2 of `box` where the seen extent agrees with
+        the class's prior height or shows only the top.  download() adds `vert_z`, `vert_h`, `vert_src`, `vert_status` and
+        `vert_entry_z`; column 2 of kept_box_sizes' rows is then `vert_h`.  None: no buffer, no call.  Its five parameters are untuned."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -507,6 +513,10 @@ class LiftEngine:
         self.yaw = yaw if yaw is not None and yaw.active else None
         self.velocity = velocity if velocity is not None and velocity.active else None
         self.size = size if size is not None and size.active else None
+        self.vertical = vertical if vertical is not None and vertical.active else None
+        if self.vertical is not None and self.obb:
+            raise ValueError("vertical=BoxVertical(...) is stated for nuScenes and Waymo boxes (z up); KITTI's rect frame has y down and "
+                             "its own + h / 2: it cannot be enabled with obb=True")
         if self.size is not None:
             missing = [n for n, v in (("yaw=YawFit(...)", yaw), ("place=BoxPlace(...)", place), ("velocity=Velocity(...)", velocity))
                        if v is None or not v.active]
@@ -682,6 +692,10 @@ class LiftEngine:
             b.size_status = torch.zeros(1, dtype=torch.int32, device=d)
             b.size_ws_bytes = int(L.cm3d_box_size_workspace_bytes(M))
             b.size_ws = torch.empty(max(b.size_ws_bytes, 16), dtype=torch.uint8, device=d)
+        if self.vertical is not None:
+            b.vert_z = e(M, 2, dtype=torch.float64); b.vert_h = e(M, dtype=torch.float64); b.vert_entry_z = e(M, dtype=torch.float64)
+            b.vert_src = e(M); b.vert_status = e(M)
+            b.prior_wlh = self.prior_wlh          # (kept_box_sizes: the length and width of a box without a size stage)
         b.dense = dense_masks
         # The bulk data LAST: sweeps and run lengths come from page-locked staging buffers (cm3d_amd.reader) and copy
         # asynchronously; the small arrays above are pageable, their copies block the host until everything queued before them on
@@ -706,7 +720,7 @@ class LiftEngine:
         if self.place is not None:             # (no member of the options: cm3d_lift_pass_placed takes it beside them; its events come last)
             b.place_desc = b.timed["place"] = self._place_descriptor(b)
         b.opts_ref = ctypes.byref(b.opts) if stages else None
-        b.plain_pass = not stages and self.velocity is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
+        b.plain_pass = not stages and self.velocity is None and self.vertical is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
         self.b = b
         return b
 
@@ -1087,6 +1101,15 @@ class LiftEngine:
                                      _ptr(b.size_ratio), _ptr(b.size_obs), _ptr(b.size_placed), _ptr(b.size_vel), _ptr(b.size_status),
                                      _ptr(b.size_ws), b.size_ws_bytes, st), "cm3d_box_size")
 
+    def stage_vertical(self, st):
+        """The opt-in vertical stage alone, on the lists and the box rows the last pass left resident (cm3d_box_vertical): the clustered
+        lists when the engine clusters, the raw ones otherwise -- what stage_bev_fit fits."""
+        b, v = self.b, self.vertical
+        xyz, off = (b.cl_xyz, b.cl_off) if self.cluster is not None else (b.hit_xyz, b.hit_off)
+        check(self.lib.cm3d_box_vertical(_ptr(xyz), _ptr(off), b.M, b.idx_cap, _ptr(b.box), _ptr(b.flags), _ptr(self.prior_wlh),
+                                         len(self.classes.names), v.q_bot, v.q_top, v.min_points, v.lo, v.hi, _ptr(b.vert_z), _ptr(b.vert_h),
+                                         _ptr(b.vert_src), _ptr(b.vert_status), _ptr(b.vert_entry_z), st), "cm3d_box_vertical")
+
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
     def run(self, masks="dense", project_events=None, stage_events=None):
@@ -1097,8 +1120,9 @@ class LiftEngine:
         Each opt-in stage the engine has appends two more behind those, in this order: around the filter launch (the "drivable"
         bucket), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
         the yaw fit's two launches (the "yawfit" bucket; behind the fifth event), around the placement's launch (the "place" bucket;
-        behind the yaw fit's boxes).  One library call enqueues the pass, opt-in stages included (cm3d_lift_pass_opt, or
-        cm3d_lift_pass_placed with a placement; include/cm3d_hip.h states the order); no allocation, no synchronisation."""
+        behind the yaw fit's boxes), around the vertical stage's call (the "vertical" bucket; behind the pass).  One library call enqueues
+        the pass, opt-in stages included (cm3d_lift_pass_opt, or cm3d_lift_pass_placed with a placement; include/cm3d_hip.h states the
+        order); no allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
             self.start_lane_grid()
@@ -1113,6 +1137,15 @@ class LiftEngine:
             check(self.lib.cm3d_lift_pass_opt(desc, self.b.opts_ref, st), "cm3d_lift_pass_opt")
         else:                                            # the same pass, the placement in front of its rotated NMS
             check(self.lib.cm3d_lift_pass_placed(desc, self.b.opts_ref, ctypes.byref(self.b.place_desc), st), "cm3d_lift_pass_placed")
+        if self.vertical is not None:                    # directly behind the pass: column 2 only, so the stages below see what they saw
+            pair = None
+            if stage_events is not None:
+                pair = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                stage_events.extend(pair)
+                pair[0].record(torch.cuda.current_stream(self.dev))
+            self.stage_vertical(st)
+            if pair is not None:
+                pair[1].record(torch.cuda.current_stream(self.dev))
         if self.velocity is not None:                    # behind the pass, on its final kept set: one more library call
             self.stage_velocity(st)
         if self.tracks is not None:                      # behind the velocity stage, on its matches: one more
@@ -1237,6 +1270,8 @@ class LiftEngine:
                 out.update(self._yaw_results())
             if self.velocity is not None:
                 out.update(self._velocity_results())
+            if self.vertical is not None:
+                out.update(self._vertical_results())
             return out
         n_rows, n_idx = int(s[1]), int(s[2])
         pt_off_rows = b.pt_off.cpu().numpy()
@@ -1270,7 +1305,12 @@ class LiftEngine:
             out.update(self._yaw_results())
         if self.velocity is not None:
             out.update(self._velocity_results())
+        if self.vertical is not None:
+            out.update(self._vertical_results())
         return out
+
+    def _vertical_results(self):
+        return {k: getattr(self.b, k).cpu().numpy() for k in VERTICAL_RESULTS}
 
     def _velocity_results(self):
         b = self.b
@@ -1471,8 +1511,21 @@ def kept_box_velocities(b):
 
 
 def kept_box_sizes(b):
-    """(k, 3) float64 [w, l, h] of the masks kept_box_records ships, in its order (an engine with BoxSize(...); a device tensor)."""
-    return b.size_wlh[(b.flags & 3) == 3].clone()
+    """(k, 3) float64 [w, l, h] of the masks kept_box_records ships, in its order (an engine with BoxSize(...) or BoxVertical(...); a
+    device tensor).  With BoxVertical(...) column 2 is `vert_h`, and columns 0 and 1 are the size stage's where the engine has one, else
+    the class's prior (the class as cm3d_box_place reads it from column 8 of the box)."""
+    keep = (b.flags & 3) == 3
+    vert_h, size_wlh = getattr(b, "vert_h", None), getattr(b, "size_wlh", None)
+    if vert_h is None:
+        return size_wlh[keep].clone()
+    if size_wlh is not None:
+        rows = size_wlh[keep].clone()
+    else:
+        b8 = b.box[keep, 8]
+        cls = torch.where((b8 >= 0.0) & (b8 < float(b.prior_wlh.shape[0])), b8, torch.zeros_like(b8)).long()
+        rows = b.prior_wlh[cls].clone()
+    rows[:, 2] = vert_h[keep]
+    return rows
 
 
 def _size_rows(size, n):

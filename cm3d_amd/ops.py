@@ -585,6 +585,35 @@ def box_size(box, flags, mask_frame, fit_rect, place_src, prior_wlh, ego_xyz, ne
                 box=f64(d_box, _lib.BOX_STRIDE), flags=d_flags.cpu().numpy().reshape(-1)[:M], status=int(status.item()))
 
 
+def box_vertical(xyz, off, box, flags, prior_wlh, q_bot=0.02, q_top=0.98, min_points=5, lo=0.7, hi=1.3, idx_cap=None):
+    """The opt-in vertical stage on arrays (cm3d_box_vertical; boxvertical.box_vertical_host states it): xyz (n, 4) float32, the points
+    of all lists; off int32 (M + 1,); idx_cap: the capacity the call is told (default: the rows of xyz) -- offsets beyond it are
+    clamped by the call, nothing at or beyond it is read; box (M, BOX_STRIDE), flags (M,), prior_wlh (C, 3).  Returns a dict of numpy
+    arrays: vert_z (M, 2), vert_h (M,), vert_src (M,), vert_status (M,), vert_entry_z (M,) and the new `box`.  The defaults are untuned."""
+    L = _lib.lib()
+    p = np.asarray(xyz, np.float32).reshape(-1, 4)
+    cap = int(p.shape[0] if idx_cap is None else idx_cap)
+    P4 = np.zeros((max(p.shape[0], cap, 1), 4), np.float32)
+    P4[:p.shape[0]] = p
+    off = np.ascontiguousarray(off, np.int32).reshape(-1)
+    M = off.size - 1
+    box = np.asarray(box, np.float64).reshape(-1, _lib.BOX_STRIDE)
+    prior = np.asarray(prior_wlh, np.float64).reshape(-1, 3)
+    if box.shape[0] != M:
+        raise ValueError("one offset more than boxes")
+    n = max(M, 1)
+    d_xyz, d_off, d_prior = _t(P4), _t(off), _t(prior if prior.size else np.zeros((1, 3)))
+    d_box = _t(box if M else np.zeros((1, _lib.BOX_STRIDE)))
+    d_flags = _t(np.asarray(flags, np.int32).reshape(M) if M else np.zeros(1, np.int32))
+    vz, vh, ez = _e(n, 2, dtype=torch.float64), _e(n, dtype=torch.float64), _e(n, dtype=torch.float64)
+    src, status = _e(n), _e(n)
+    check(L.cm3d_box_vertical(d_xyz.data_ptr(), d_off.data_ptr(), M, cap, d_box.data_ptr(), d_flags.data_ptr(), d_prior.data_ptr(),
+                              prior.shape[0], float(q_bot), float(q_top), int(min_points), float(lo), float(hi), vz.data_ptr(), vh.data_ptr(),
+                              src.data_ptr(), status.data_ptr(), ez.data_ptr(), _st()), "cm3d_box_vertical")
+    return dict(vert_z=vz.cpu().numpy()[:M], vert_h=vh.cpu().numpy()[:M], vert_src=src.cpu().numpy()[:M],
+                vert_status=status.cpu().numpy()[:M], vert_entry_z=ez.cpu().numpy()[:M], box=d_box.cpu().numpy()[:M])
+
+
 # ----------------------------------------------------------------------------- f4: SAM3D fusion matching
 def match_records(boxes7):
     """(n,7) [center_x, center_y, bottom_z, length, width, height, heading] -> (n,6) float64 records of

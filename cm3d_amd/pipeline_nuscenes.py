@@ -26,6 +26,7 @@ from . import lifting, nusc_io
 from . import velocity as velmod
 from . import tracks as trmod
 from . import boxsize as szmod
+from . import boxvertical as vtmod
 
 # module constants of the reference (:55-59)
 VER_NAME = "v1.0-trainval"
@@ -226,7 +227,7 @@ def _token_batches(batches, index, host_s):
 
 
 def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                  velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None):
+                  velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
@@ -243,7 +244,11 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
     behind the yaw fit's, and the time between them goes into a "place" bucket.  size: the opt-in size stage (boxsize.BoxSize; with `yaw`,
     `place` and `velocity` only), one more call behind the track stage's: the (k, 3) sizes of the returned records (lifting.kept_box_sizes)
     are appended to `size_out` as ONE device tensor the way the velocities are, on_records gets a batch's share as a fifth argument, and
-    the velocities are those on the sized centres."""
+    the velocities are those on the sized centres.  vertical: the opt-in vertical stage (boxvertical.BoxVertical; with any option or
+    none), one call directly behind the pass; its two events come last, and the time between them goes into a "vertical" bucket.  The
+    records' (k, 3) sizes then carry its heights in column 2 (lifting.kept_box_sizes) and are shipped exactly as the size stage's are,
+    with or without a size stage."""
+    sized = size is not None or vertical is not None      # the records travel with (k, 3) size rows
     kw = {} if yaw is None else {"yaw": yaw}
     if place is not None:
         kw["place"] = place
@@ -253,11 +258,13 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
         kw["tracks"] = tracks
     if size is not None:
         kw["size"] = size
+    if vertical is not None:
+        kw["vertical"] = vertical
     vels, sizes = [], []
     pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms, **kw)
     n_f, n_c, n_y = (2 if filters is not None and filters.active else 0), (2 if cluster is not None else 0), (2 if yaw is not None else 0)
-    n_p = 2 if place is not None else 0
-    n_evs = 5 + n_f + n_c + n_y + n_p
+    n_p, n_v = (2 if place is not None else 0), (2 if vertical is not None else 0)
+    n_evs = 5 + n_f + n_c + n_y + n_p + n_v
     records, pending, segments = [], [], []                            # pending: (slot, frame ids, stage events) in flight, oldest first
 
     def spent(key, since):
@@ -270,14 +277,14 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
             records.append(pipe.collect_records(slot, ids))           # stays on the device until the one gather at the end
             if velocity is not None:                                   # (the slot's stream has been synchronised)
                 vels.append(lifting.kept_box_velocities(pipe.engines[slot].b))
-            if size is not None:
+            if sized:
                 sizes.append(lifting.kept_box_sizes(pipe.engines[slot].b))
             spent("gpu lifting", t1)
             if on_records is not None:
                 first = int(ids[0, 0]) if len(ids) else 0
                 extra = () if velocity is None else (vels[-1].cpu().numpy(),)
-                if size is not None:
-                    extra += (sizes[-1].cpu().numpy(),)
+                if sized:
+                    extra += (None,) * (1 - len(extra)) + (sizes[-1].cpu().numpy(),)
                 if len(ids) and np.array_equal(ids[:, 0], np.arange(first, first + len(ids))):
                     on_records(records[-1].cpu().numpy(), first, len(ids), *extra)
                 else:
@@ -294,8 +301,11 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
                     timer["medoid"] -= dt
                 if yaw is not None:                                    # behind the pass
                     timer["yawfit"] = timer.get("yawfit", 0.0) + evs[5 + n_f + n_c].elapsed_time(evs[6 + n_f + n_c]) * 1e-3
-                if place is not None:                                  # the last two events, behind the yaw fit's boxes
-                    timer["place"] = timer.get("place", 0.0) + evs[-2].elapsed_time(evs[-1]) * 1e-3
+                if place is not None:                                  # behind the yaw fit's boxes
+                    at = 5 + n_f + n_c + n_y
+                    timer["place"] = timer.get("place", 0.0) + evs[at].elapsed_time(evs[at + 1]) * 1e-3
+                if vertical is not None:                               # the last two events, behind the pass
+                    timer["vertical"] = timer.get("vertical", 0.0) + evs[-2].elapsed_time(evs[-1]) * 1e-3
 
     try:
         for hb, ids, host_s in prepared:
@@ -320,7 +330,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
         _release(segments)
     if vel_out is not None and velocity is not None:
         vel_out.append(torch.cat(vels, 0) if vels else torch.zeros(0, 2, dtype=torch.float64, device=device))
-    if size_out is not None and size is not None:
+    if size_out is not None and sized:
         size_out.append(torch.cat(sizes, 0) if sizes else torch.zeros(0, 3, dtype=torch.float64, device=device))
     if records:
         return torch.cat(records, 0)
@@ -329,7 +339,8 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
 
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                 scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None,
-                cluster=None, nms=None, yaw=None, velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None):
+                cluster=None, nms=None, yaw=None, velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None,
+                vertical=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -363,7 +374,7 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
                 pool.join()
     with contextlib.closing(prepared()) as batches:
         return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms, yaw=yaw, velocity=velocity,
-                             vel_out=vel_out, tracks=tracks, place=place, size=size, size_out=size_out)
+                             vel_out=vel_out, tracks=tracks, place=place, size=size, size_out=size_out, vertical=vertical)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -441,7 +452,7 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
 
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                        scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                       velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None):
+                       velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -485,7 +496,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
         return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw, velocity, vel_out, tracks, place,
-                             size, size_out)
+                             size, size_out, vertical)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -523,6 +534,7 @@ def main(argv=None):
     velmod.add_arguments(ap)
     trmod.add_arguments(ap)
     szmod.add_arguments(ap)
+    vtmod.add_arguments(ap)
     args = ap.parse_args(argv)
     cluster = clmod.from_namespace(args)
     nms = nmsmod.from_args(args)
@@ -531,7 +543,9 @@ def main(argv=None):
     velocity = velmod.from_args(args)
     tracks = trmod.from_args(args, ap)              # (a track flag without --velocity track: an error of the command line)
     size = szmod.from_args(args, ap)                # (--size track without --yaw fit --place fit --velocity track, or a --size-* flag alone: the same)
-    size_mine = []                                 # with --size track: the sizes of this rank's records, one device tensor
+    vertical = vtmod.from_args(args, ap)            # (a --vertical-* flag without --vertical fit: the same)
+    sized = size is not None or vertical is not None
+    size_mine = []                                 # with --size track or --vertical fit: the sizes of this rank's records, one device tensor
     vel_mine = []                                  # with --velocity track: the velocities of this rank's records, one device tensor
     filters = lifting.Stage2Filters.from_args(args.drivable_filter, args.lane_max_dist, args.vehicle_lane_max_dist)
 
@@ -607,7 +621,8 @@ def main(argv=None):
         mine = lift_scenes_native(nt, names[lo:hi], args.mask_dir, classes, device, row_to_out, args.n_sweeps, args.ratio, args.masks, timer,
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
                                   on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
-                                  velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine)
+                                  velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine,
+                                  vertical=vertical)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
@@ -616,14 +631,14 @@ def main(argv=None):
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
                            token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
-                           velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine)
+                           velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine, vertical=vertical)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.
     t0 = time.time()
     gathered = cdist.gather_records(mine, dst=0)
     gathered_vel = cdist.gather_records(vel_mine[0], dst=0) if velocity is not None else None      # rank order is sample order here too
-    gathered_size = cdist.gather_records(size_mine[0], dst=0) if size is not None else None
+    gathered_size = cdist.gather_records(size_mine[0], dst=0) if sized else None
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
@@ -631,7 +646,7 @@ def main(argv=None):
         return 0
     rec = torch.cat([g.cpu() for g in gathered], 0).numpy()
     vel = torch.cat([g.cpu() for g in gathered_vel], 0).numpy() if velocity is not None else None
-    sizes = torch.cat([g.cpu() for g in gathered_size], 0).numpy() if size is not None else None
+    sizes = torch.cat([g.cpu() for g in gathered_size], 0).numpy() if sized else None
     timer["gather"] = time.time() - t0
 
     # the writer (:929-930): the records straight to the text json.dump would produce for the reference's dict of box lists

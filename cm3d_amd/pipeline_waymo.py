@@ -29,6 +29,7 @@ from . import cluster as clmod
 from . import nms as nmsmod
 from . import bevfit
 from . import boxplace
+from . import boxvertical as vtmod
 from . import dist as cdist
 from . import lifting
 from . import waymo as wm
@@ -74,10 +75,11 @@ def load_scene(frames_dir, mask_dir, scene, tfrecord=None):
     return frames, lane_table
 
 
-def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0):
+def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0, heights=None):
     """One scene through the hot path, its frames in one batch; returns its kept-box records as a list of device tensors
     (lifting.kept_box_records with column 5 = scene_index, column 6 = the frame's number inside the scene).  Masks of different image
-    sizes -- Waymo's side cameras, inside every frame -- share the batch (lifting.pack_frames)."""
+    sizes -- Waymo's side cameras, inside every frame -- share the batch (lifting.pack_frames).  heights: a list that, with an engine
+    whose vertical stage is on, gets the (k,) heights of the returned records appended (column 2 of lifting.kept_box_sizes)."""
     hb = lifting.pack_frames(frames, [lane_table], [0] * len(frames), classes)
     if masks == "dense":
         lifting.require_one_mask_size(hb)
@@ -88,17 +90,25 @@ def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0):
     torch.cuda.synchronize()
     eng.check_status()
     ids = np.array([[scene_index, int(f.token.rsplit(":", 1)[1])] for f in frames], np.float64)
+    if heights is not None and eng.vertical is not None:
+        heights.append(lifting.kept_box_sizes(eng.b)[:, 2:3].contiguous())
     return [lifting.kept_box_records(eng.b, ids)]
 
 
-def objects_from_records(rec, scenes, frames_dir, classes, meta=None):
+def objects_from_records(rec, scenes, frames_dir, classes, meta=None, height=None):
     """Gathered records -> encoded metrics_pb2.Object payloads in the reference's order (scenes in order, frames in
     order, kept boxes in mask order; src/waymo/2d_to_3d.py:1034-1065,1262-1297).  The frame's context name and timestamp
-    (:1050-1051) come from its extracted-frame file; the records only carry (scene index, frame number)."""
+    (:1050-1051) come from its extracted-frame file; the records only carry (scene index, frame number).
+    height: None -- every box has its class's prior height --, or the records' (k,) heights (the vertical stage's `vert_h`)."""
     rec = np.asarray(rec, np.float64).reshape(-1, 10)
+    if height is not None:
+        height = np.asarray(height, np.float64).reshape(-1)
+        if height.size != len(rec):
+            raise ValueError(f"height: {height.size} values for {len(rec)} records")
     order = np.lexsort((np.arange(len(rec)), rec[:, lifting.REC_FRAME_B], rec[:, lifting.REC_FRAME_A]))     # stable inside a frame
     meta, out = dict(meta or {}), []           # (scene index, frame number) -> (context name, timestamp): what this rank saw ...
-    for r in rec[order]:
+    for k in order:
+        r = rec[k]
         key = (int(r[lifting.REC_FRAME_A]), int(r[lifting.REC_FRAME_B]))
         if key not in meta:                    # ... and, for the frames of other ranks, the frame's extracted file
             z = np.load(os.path.join(frames_dir, scenes[key[0]], f"{key[1]}_frame.npz"), allow_pickle=False)
@@ -106,7 +116,7 @@ def objects_from_records(rec, scenes, frames_dir, classes, meta=None):
         ctx, ts = meta[key]
         ci = int(r[8])
         pr = classes.prior_wlh[ci]
-        out.append(wm.encode_object(r[0:3], length=pr[1], width=pr[0], height=pr[2], heading=r[3],
+        out.append(wm.encode_object(r[0:3], length=pr[1], width=pr[0], height=pr[2] if height is None else height[k], heading=r[3],
                                     type_id=wm.WAYMO_TYPE[classes.out_names[ci]], score=r[7], context_name=ctx, timestamp_micros=ts))
     return out
 
@@ -132,8 +142,10 @@ def main(argv=None):
     nmsmod.add_arguments(ap)
     bevfit.add_arguments(ap)
     boxplace.add_arguments(ap)
+    vtmod.add_arguments(ap)
     args = ap.parse_args(argv)
     place = boxplace.from_namespace(args, ap)       # (--place fit without --yaw fit: an error of the command line)
+    vertical = vtmod.from_args(args, ap)            # (a --vertical-* flag without --vertical fit: the same)
     filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
     rank, world, local_rank = cdist.init_from_env()
@@ -145,9 +157,10 @@ def main(argv=None):
     pri = json.load(open(args.priors)) if os.path.exists(args.priors) else None
     classes = lifting.ClassTable.waymo(pri)
     eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args),
-                             nms=nmsmod.from_args(args), yaw=bevfit.from_namespace(args), place=place)
+                             nms=nmsmod.from_args(args), yaw=bevfit.from_namespace(args), place=place,
+                             vertical=vertical)
     lo, hi = cdist.shard_range(len(scenes), rank, world)
-    mine, meta = [], {}
+    mine, meta, heights = [], {}, []
     for si in range(lo, hi):
         frames, lanes = load_scene(args.frames_dir, args.mask_dir, scenes[si], os.path.join(args.tfrecords, scenes[si]) if use_tf else None)
         for f in frames:
@@ -155,10 +168,14 @@ def main(argv=None):
         if frames:
             if lanes is None:
                 raise FileNotFoundError(f"{scenes[si]}: no lane polylines (frame 0)")
-            mine.extend(lift_scene(eng, frames, lanes, classes, args.masks, scene_index=si))
+            mine.extend(lift_scene(eng, frames, lanes, classes, args.masks, scene_index=si, heights=heights))
     rec = torch.cat(mine, 0) if mine else torch.zeros(0, 10, dtype=torch.float64, device=eng.dev)
     # the single exchange of the job: fixed-size box records -> rank 0 (also the path of a one-rank run)
     gathered = cdist.gather_records(rec, dst=0)
+    gathered_h = None
+    if vertical is not None:                       # the heights travel beside the records, in their order
+        mine_h = torch.cat(heights, 0) if heights else torch.zeros(0, 1, dtype=torch.float64, device=eng.dev)
+        gathered_h = cdist.gather_records(mine_h, dst=0)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
@@ -169,7 +186,8 @@ def main(argv=None):
         for si in [i for i in range(len(scenes)) if not (lo <= i < hi)]:
             for fnum, z in wm.frame_records_from_tfrecord(os.path.join(args.tfrecords, scenes[si]), lambda k: False):
                 meta[(si, fnum)] = (str(z["context_name"]), int(z["timestamp_micros"]))
-    mine = objects_from_records(torch.cat([g.cpu() for g in gathered], 0).numpy(), scenes, args.frames_dir, classes, meta)
+    height = torch.cat([g.cpu() for g in gathered_h], 0).numpy() if gathered_h is not None else None
+    mine = objects_from_records(torch.cat([g.cpu() for g in gathered], 0).numpy(), scenes, args.frames_dir, classes, meta, height=height)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     with open(args.output, "wb") as f:
         f.write(wm.encode_objects(mine))

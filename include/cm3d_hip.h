@@ -1160,6 +1160,54 @@ int cm3d_box_size(double *box, int32_t *flags, const int32_t *mask_frame, const 
                   double *size_ratio, int32_t *size_obs, double *size_placed, double *size_vel, int32_t *status, void *workspace,
                   int64_t workspace_bytes, cm3d_stream_t stream);
 
+/* ---- opt-in: box height and z from the in-mask points (csrc/vertical.hip) ----------------------------------
+ * box[m][2] of the pass is the medoid's z, a point somewhere on the surface the LiDAR saw, and the height of every box is its class's
+ * prior.  Here two order statistics of every list's z say where the seen surface begins and ends, and the prior says whether both ends
+ * of the object were seen.  Per frame, no track, no yaw fit, every class.  The defaults q_bot = 0.02, q_top = 0.98, min_points = 5,
+ * lo = 0.7, hi = 1.3 are UNTUNED, and what the stage does to label quality has not been measured (it cannot be on synthetic scenes).
+ * Host statement to the bit: cm3d_amd.boxvertical.box_vertical_host.  M = n_masks.
+ *
+ *  xyz, off    float[idx_cap][4], int32[M + 1]: the in-mask lists a pass leaves (hit_xyz / hit_off, or cl_xyz / cl_off behind the depth
+ *              clustering).  The list of mask m is positions lo_m .. hi_m with lo_m = clamp(off[m], 0, idx_cap) and
+ *              hi_m = clamp(off[m + 1], lo_m, idx_cap) (an end below its start: empty), as cm3d_bev_fit and cm3d_depth_cluster clamp
+ *              them: whatever off holds, nothing at or beyond idx_cap is read.  n = hi_m - lo_m, z_i the float32 in column 2.  nuScenes
+ *              lists and boxes are global, Waymo's both in the vehicle frame: list z and box[m][2] share a frame, there is no switch.
+ *  Key.        The order of z is the order of the unsigned key(z) = bits ^ (bits >> 31 ? 0xFFFFFFFF : 0x80000000): a total order on the
+ *              bit patterns, -0.0 before +0.0.  The order statistic k of a list is the value whose key has exactly k keys before it in
+ *              ascending key order; equal keys are equal bits, so the value needs no tie rule.
+ *  Status.     vert_status int32[M], in this order: 2 n == 0;  1 n < min_points;  4 some z_i is not finite (tested before anything is
+ *              selected);  0 otherwise.
+ *  Quantiles.  Status 0: kb = (int)(q_bot * (double)(n - 1)), kt = (int)(q_top * (double)(n - 1)), vert_z double[M][2] =
+ *              ((double)z[kb], (double)z[kt]) = (zb, zt).  Any other status: (0, 0).  Status and vert_z are functions of the lists
+ *              alone and are written for every mask, whatever flags says.
+ *  Apply.      float64, every operation rounded on its own, no fma, no library call.  c = box[m][8] >= 0 && box[m][8] < n_classes ?
+ *              (int)box[m][8] : 0 (as cm3d_box_place reads it), h0 = prior_wlh[3 c + 2].  vert_entry_z double[M] = box[m][2] as on entry,
+ *              every mask.  Mask m is judged iff flags[m] & 1, status 0, and h0 is finite and > 0.  Then ext = zt - zb, r = ext / h0:
+ *                lo <= r <= hi   both ends seen: vert_src 1, h = ext, z = zb + ext * 0.5
+ *                r < lo          the lower part was not seen (a LiDAR above the object and an occluder in front leave it):
+ *                                vert_src 2, h = h0, z = zt - h0 * 0.5 -- the prior's height hung on the top seen
+ *                r > hi (the list holds ground or a wall), or not judged: vert_src 0, h = h0 bit for bit, box[m][2] untouched
+ *              vert_src int32[M], vert_h double[M] = h;  for sources 1 and 2 box[m][2] = z.  Only column 2 of box is ever written, flags is
+ *              only read, no NMS is decided again: the circle and rotated NMS and the velocity use x and y only.  z comes from the list,
+ *              never from the entry value: a second call on the arrays of the first gives the same box.
+ *
+ *  CM3D_ERR_ARG before any launch: q_bot, q_top not 0 <= q_bot <= q_top <= 1 (NaN included), min_points < 1, not 0 < lo <= hi < inf,
+ *  n_masks < 0, idx_cap < 0, n_classes < 0, and with M > 0: n_classes == 0 or a NULL array (xyz may be NULL when idx_cap == 0).
+ *  M == 0: CM3D_OK, nothing is launched.
+ *  One launch, k_box_vertical: workgroups of four waves, four masks each.  A list of up to CM3D_VERT_LANE_MAX (64) points sits one
+ *  point per lane of its mask's wave and is selected by ballots over the key bits, both order statistics in the same 32 steps, no LDS.
+ *  A longer list is selected by all four waves together: a most-significant-digit radix select, four 8-bit digits, integer LDS
+ *  counters (sums of integers: the result does not depend on their order), both order statistics in the same passes; up to
+ *  CM3D_VERT_LDS_KEYS (4096) keys are staged in LDS by the first pass, a longer list is read again from memory in each of the four.  Every
+ *  length up to idx_cap gives the rule's answer.  The apply step is the tail of the same launch, one lane per mask.  Per point one
+ *  4-byte load of column 2.  Plain stores, no global atomic, no workspace, no allocation, no read-back. */
+#define CM3D_VERT_LANE_MAX 64
+#define CM3D_VERT_LDS_KEYS 4096
+int cm3d_box_vertical(const float *xyz, const int32_t *off, int32_t n_masks, int32_t idx_cap, double *box, const int32_t *flags,
+                      const double *prior_wlh, int32_t n_classes, double q_bot, double q_top, int32_t min_points, double lo, double hi,
+                      double *vert_z, double *vert_h, int32_t *vert_src, int32_t *vert_status, double *vert_entry_z,
+                      cm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
