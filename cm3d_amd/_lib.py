@@ -33,6 +33,7 @@ NUSC_MAX_ALPHAS = 1024   # alphas of one cm3d_nusc_match call
 DEPTH_CLUSTER_LDS_POINTS = 4096   # longest list cm3d_depth_cluster sorts in LDS
 BEV_FIT_CHUNK = 512      # points of a list cm3d_bev_fit stages in LDS at a time
 VERT_LANE_MAX, VERT_LDS_KEYS = 64, 4096      # cm3d_box_vertical: the longest list of the lane route, the most keys staged in LDS
+GROUND_BINS = 128        # cm3d_box_ground: the bins of a mask's window
 RAW_QUADS = 3           # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -127,6 +128,9 @@ SIGNATURES = {
                              C.c_double, _i32, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "cm3d_box_vertical": (_i32, [_p, _p, _i32, _i32, _p, _p, _p, _i32, C.c_double, C.c_double, _i32, C.c_double, C.c_double, _p, _p, _p,
                                  _p, _p, _p]),
+    "cm3d_box_ground_chunk": (_i32, [_i32, _i32]),
+    "cm3d_box_ground": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i32, _f32, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _p, _p, _p,
+                               C.c_double, C.c_double, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order

@@ -31,6 +31,7 @@ from .velocity import Velocity, link_table  # noqa: F401  (LiftEngine(velocity=V
 from .tracks import Tracks  # noqa: F401  (LiftEngine(velocity=Velocity(...), tracks=Tracks(...)))
 from .boxsize import BoxSize  # noqa: F401  (LiftEngine(yaw=..., place=..., velocity=..., size=BoxSize(...)))
 from .boxvertical import BoxVertical, RESULTS as VERTICAL_RESULTS  # noqa: F401  (LiftEngine(vertical=BoxVertical(...)))
+from .boxground import BoxGround, RESULTS as GROUND_RESULTS  # noqa: F401  (LiftEngine(ground=BoxGround(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -455,7 +456,7 @@ class LiftEngine:
                  hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
                  cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None,
                  velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None, place: Optional[BoxPlace] = None,
-                 size: Optional[BoxSize] = None, vertical: Optional[BoxVertical] = None):
+                 size: Optional[BoxSize] = None, vertical: Optional[BoxVertical] = None, ground: Optional[BoxGround] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -495,7 +496,13 @@ class LiftEngine:
         directly behind the pass (cm3d_box_vertical), in front of the velocity stage's, takes two order statistics of every in-mask
         list's z -- the clustered lists when the engine clusters -- and rewrites column 2 of `box` where the seen extent agrees with
         the class's prior height or shows only the top.  download() adds `vert_z`, `vert_h`, `vert_src`, `vert_status` and
-        `vert_entry_z`; column 2 of kept_box_sizes' rows is then `vert_h`.  None: no buffer, no call.  Its five parameters are untuned."""
+        `vert_entry_z`; column 2 of kept_box_sizes' rows is then `vert_h`.  None: no buffer, no call.  Its five parameters are untuned.
+        ground: the ground stage (boxground.BoxGround; nuScenes and Waymo batches, with any other option or none): one call directly
+        behind the vertical stage's, or behind the pass where there is none, and in front of the velocity stage's (cm3d_box_ground)
+        streams every frame's sweep rows once more -- the raw rows, or the cloud where the engine has materialised it; it never makes the
+        engine materialise it --, takes a low quantile of the heights around every box as its ground and rewrites column 2 of `box`
+        where the box can be stood on it.  download() adds `ground_z`, `ground_n`, `ground_h`, `ground_src`, `ground_status` and
+        `ground_zref`; column 2 of kept_box_sizes' rows is then `ground_h`.  None: no buffer, no call.  Its seven parameters are untuned."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -514,6 +521,10 @@ class LiftEngine:
         self.velocity = velocity if velocity is not None and velocity.active else None
         self.size = size if size is not None and size.active else None
         self.vertical = vertical if vertical is not None and vertical.active else None
+        self.ground = ground if ground is not None and ground.active else None
+        if self.ground is not None and self.obb:
+            raise ValueError("ground=BoxGround(...) is stated for nuScenes and Waymo boxes (z up); KITTI's rect frame has y down and "
+                             "its own + h / 2: it cannot be enabled with obb=True")
         if self.vertical is not None and self.obb:
             raise ValueError("vertical=BoxVertical(...) is stated for nuScenes and Waymo boxes (z up); KITTI's rect frame has y down and "
                              "its own + h / 2: it cannot be enabled with obb=True")
@@ -696,6 +707,11 @@ class LiftEngine:
             b.vert_z = e(M, 2, dtype=torch.float64); b.vert_h = e(M, dtype=torch.float64); b.vert_entry_z = e(M, dtype=torch.float64)
             b.vert_src = e(M); b.vert_status = e(M)
             b.prior_wlh = self.prior_wlh          # (kept_box_sizes: the length and width of a box without a size stage)
+        if self.ground is not None:
+            b.ground_z = e(M, dtype=torch.float64); b.ground_h = e(M, dtype=torch.float64); b.ground_zref = e(M, dtype=torch.float64)
+            b.ground_n = e(M); b.ground_src = e(M); b.ground_status = e(M)
+            b.nm_max = nm_max
+            b.prior_wlh = self.prior_wlh
         b.dense = dense_masks
         # The bulk data LAST: sweeps and run lengths come from page-locked staging buffers (cm3d_amd.reader) and copy
         # asynchronously; the small arrays above are pageable, their copies block the host until everything queued before them on
@@ -720,7 +736,7 @@ class LiftEngine:
         if self.place is not None:             # (no member of the options: cm3d_lift_pass_placed takes it beside them; its events come last)
             b.place_desc = b.timed["place"] = self._place_descriptor(b)
         b.opts_ref = ctypes.byref(b.opts) if stages else None
-        b.plain_pass = not stages and self.velocity is None and self.vertical is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
+        b.plain_pass = not stages and self.velocity is None and self.vertical is None and self.ground is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
         self.b = b
         return b
 
@@ -1110,6 +1126,22 @@ class LiftEngine:
                                          len(self.classes.names), v.q_bot, v.q_top, v.min_points, v.lo, v.hi, _ptr(b.vert_z), _ptr(b.vert_h),
                                          _ptr(b.vert_src), _ptr(b.vert_status), _ptr(b.vert_entry_z), st), "cm3d_box_vertical")
 
+    def stage_ground(self, st, zref=None):
+        """The opt-in ground stage alone, on the sweep rows and the box rows the last pass left resident (cm3d_box_ground): the cloud where
+        the engine has materialised it, the raw rows otherwise.  zref: None -- the reference heights are `vert_entry_z` with a vertical
+        stage, else column 2 of `box` --, or a device tensor of M doubles (`ground_zref` itself: the stage again on what a pass left)."""
+        b, g, v = self.b, self.ground, self.vertical is not None
+        if zref is None and v:
+            zref = b.vert_entry_z
+        cloud = b.points is not None
+        check(self.lib.cm3d_box_ground(_ptr(b.points) if cloud else None, _ptr(b.pt_off) if cloud else None, None if cloud else _ptr(b.raw),
+                                       b.hb.raw_stride, _ptr(b.sweep_xf), _ptr(b.sweep_row_off), _ptr(b.frame_sweep_off), b.S, b.halfw, b.pt_cap,
+                                       _ptr(b.mask_off), b.F, b.M, b.nm_max, _ptr(b.box), _ptr(b.flags), _ptr(self.prior_wlh),
+                                       len(self.classes.names), None if zref is None else _ptr(zref), _ptr(b.vert_status) if v else None,
+                                       _ptr(b.vert_z) if v else None, _ptr(b.vert_h) if v else None, g.radius, g.quantile, g.min_points,
+                                       g.down, g.up, g.lo, g.hi, _ptr(b.ground_z), _ptr(b.ground_n), _ptr(b.ground_h), _ptr(b.ground_src),
+                                       _ptr(b.ground_status), _ptr(b.ground_zref), st), "cm3d_box_ground")
+
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
     def run(self, masks="dense", project_events=None, stage_events=None):
@@ -1120,7 +1152,8 @@ class LiftEngine:
         Each opt-in stage the engine has appends two more behind those, in this order: around the filter launch (the "drivable"
         bucket), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
         the yaw fit's two launches (the "yawfit" bucket; behind the fifth event), around the placement's launch (the "place" bucket;
-        behind the yaw fit's boxes), around the vertical stage's call (the "vertical" bucket; behind the pass).  One library call enqueues
+        behind the yaw fit's boxes), around the vertical stage's call (the "vertical" bucket; behind the pass), around the ground stage's
+        call (the "ground" bucket; behind the vertical stage's).  One library call enqueues
         the pass, opt-in stages included (cm3d_lift_pass_opt, or cm3d_lift_pass_placed with a placement; include/cm3d_hip.h states the
         order); no allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
@@ -1144,6 +1177,15 @@ class LiftEngine:
                 stage_events.extend(pair)
                 pair[0].record(torch.cuda.current_stream(self.dev))
             self.stage_vertical(st)
+            if pair is not None:
+                pair[1].record(torch.cuda.current_stream(self.dev))
+        if self.ground is not None:                      # behind the vertical stage's call: column 2 only, like it
+            pair = None
+            if stage_events is not None:
+                pair = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                stage_events.extend(pair)
+                pair[0].record(torch.cuda.current_stream(self.dev))
+            self.stage_ground(st)
             if pair is not None:
                 pair[1].record(torch.cuda.current_stream(self.dev))
         if self.velocity is not None:                    # behind the pass, on its final kept set: one more library call
@@ -1272,6 +1314,8 @@ class LiftEngine:
                 out.update(self._velocity_results())
             if self.vertical is not None:
                 out.update(self._vertical_results())
+            if self.ground is not None:
+                out.update(self._ground_results())
             return out
         n_rows, n_idx = int(s[1]), int(s[2])
         pt_off_rows = b.pt_off.cpu().numpy()
@@ -1307,7 +1351,12 @@ class LiftEngine:
             out.update(self._velocity_results())
         if self.vertical is not None:
             out.update(self._vertical_results())
+        if self.ground is not None:
+            out.update(self._ground_results())
         return out
+
+    def _ground_results(self):
+        return {k: getattr(self.b, k).cpu().numpy() for k in GROUND_RESULTS}
 
     def _vertical_results(self):
         return {k: getattr(self.b, k).cpu().numpy() for k in VERTICAL_RESULTS}
@@ -1512,11 +1561,12 @@ def kept_box_velocities(b):
 
 def kept_box_sizes(b):
     """(k, 3) float64 [w, l, h] of the masks kept_box_records ships, in its order (an engine with BoxSize(...) or BoxVertical(...); a
-    device tensor).  With BoxVertical(...) column 2 is `vert_h`, and columns 0 and 1 are the size stage's where the engine has one, else
-    the class's prior (the class as cm3d_box_place reads it from column 8 of the box)."""
+    device tensor).  With BoxVertical(...) column 2 is `vert_h`, with BoxGround(...) it is `ground_h` (which carries `vert_h` where the
+    ground stage left the box alone), and columns 0 and 1 are the size stage's where the engine has one, else the class's prior (the
+    class as cm3d_box_place reads it from column 8 of the box)."""
     keep = (b.flags & 3) == 3
-    vert_h, size_wlh = getattr(b, "vert_h", None), getattr(b, "size_wlh", None)
-    if vert_h is None:
+    height, size_wlh = getattr(b, "ground_h", getattr(b, "vert_h", None)), getattr(b, "size_wlh", None)
+    if height is None:
         return size_wlh[keep].clone()
     if size_wlh is not None:
         rows = size_wlh[keep].clone()
@@ -1524,7 +1574,7 @@ def kept_box_sizes(b):
         b8 = b.box[keep, 8]
         cls = torch.where((b8 >= 0.0) & (b8 < float(b.prior_wlh.shape[0])), b8, torch.zeros_like(b8)).long()
         rows = b.prior_wlh[cls].clone()
-    rows[:, 2] = vert_h[keep]
+    rows[:, 2] = height[keep]
     return rows
 
 

@@ -614,6 +614,64 @@ def box_vertical(xyz, off, box, flags, prior_wlh, q_bot=0.02, q_top=0.98, min_po
                 vert_status=status.cpu().numpy()[:M], vert_entry_z=ez.cpu().numpy()[:M], box=d_box.cpu().numpy()[:M])
 
 
+def box_ground(box, flags, prior_wlh, mask_off, points=None, pt_off=None, raw=None, raw_stride=4, sweep_xf=None, sweep_row_off=None,
+               frame_sweep_off=None, halfw=0.0, zref=None, vert=None, zref_aliases=False, radius=3.0, quantile=0.1, min_points=20, down=5.0,
+               up=0.5, lo=0.7, hi=1.3):
+    """The opt-in ground stage on arrays (cm3d_box_ground; boxground.box_ground_host states it).  The cloud is either points (n, 4)
+    float32 with pt_off (F + 1,), or the raw rows as cm3d_sweep_prep takes them: raw (flat float32), raw_stride (4 and up, or
+    _lib.RAW_QUADS), sweep_xf (S, 24), sweep_row_off (S + 1,), frame_sweep_off (F + 1,), halfw.  box (M, BOX_STRIDE), flags (M,),
+    prior_wlh (C, 3), mask_off (F + 1,); zref (M,) or None (column 2 of box); vert: None or the vertical stage's outputs (vert_status,
+    vert_z, vert_h).  zref_aliases: hand zref in the very array ground_zref is written to.  Returns a dict of numpy arrays: the six
+    boxground.RESULTS and the new `box`.  The defaults are untuned."""
+    L = _lib.lib()
+    box = np.asarray(box, np.float64).reshape(-1, _lib.BOX_STRIDE)
+    M = box.shape[0]
+    prior = np.asarray(prior_wlh, np.float64).reshape(-1, 3)
+    mask_off = np.ascontiguousarray(mask_off, np.int32).reshape(-1)
+    F = mask_off.size - 1
+    n = max(M, 1)
+    d_box = _t(box if M else np.zeros((1, _lib.BOX_STRIDE)))
+    d_flags = _t(np.asarray(flags, np.int32).reshape(M) if M else np.zeros(1, np.int32))
+    d_prior, d_moff = _t(prior if prior.size else np.zeros((1, 3))), _t(mask_off)
+    null = lambda a: None if a is None else a.data_ptr()
+    d_pts = d_poff = d_raw = d_xf = d_roff = d_soff = None
+    n_sweeps = 0
+    if points is not None:
+        p = np.asarray(points, np.float32).reshape(-1, 4)
+        n_rows = p.shape[0]
+        d_pts, d_poff = _t(p if n_rows else np.zeros((1, 4), np.float32)), _t(np.asarray(pt_off, np.int32).reshape(F + 1))
+    else:
+        sweep_row_off = np.ascontiguousarray(sweep_row_off, np.int32).reshape(-1)
+        n_sweeps, n_rows = sweep_row_off.size - 1, int(sweep_row_off[-1])
+        r = np.asarray(raw, np.float32).reshape(-1)
+        need = (n_rows + 3) // 4 * 12 if raw_stride == _lib.RAW_QUADS else n_rows * int(raw_stride)
+        if r.size < need:
+            raise ValueError(f"raw: {r.size} floats for {n_rows} rows")
+        d_raw, d_xf = _t(r if r.size else np.zeros(12, np.float32)), _t(np.asarray(sweep_xf, np.float32).reshape(max(n_sweeps, 0), 24))
+        d_roff, d_soff = _t(sweep_row_off), _t(np.asarray(frame_sweep_off, np.int32).reshape(F + 1))
+    gz, gh, gr = (_e(n, dtype=torch.float64) for _ in range(3))
+    gn, src, status = _e(n), _e(n), _e(n)
+    d_zref = None
+    if zref is not None:
+        d_zref = _t(np.asarray(zref, np.float64).reshape(M) if M else np.zeros(1))
+        if zref_aliases:
+            gr = d_zref
+    d_vs = d_vz = d_vh = None
+    if vert is not None:
+        d_vs = _t(np.asarray(vert["vert_status"], np.int32).reshape(M) if M else np.zeros(1, np.int32))
+        d_vz = _t(np.asarray(vert["vert_z"], np.float64).reshape(M, 2) if M else np.zeros((1, 2)))
+        d_vh = _t(np.asarray(vert["vert_h"], np.float64).reshape(M) if M else np.zeros(1))
+    nm_max = int(np.diff(mask_off).max()) if F > 0 else 0
+    check(L.cm3d_box_ground(null(d_pts), null(d_poff), null(d_raw), int(raw_stride), null(d_xf), null(d_roff), null(d_soff), n_sweeps,
+                            float(halfw), n_rows, d_moff.data_ptr(), F, M, max(nm_max, 0), d_box.data_ptr(), d_flags.data_ptr(),
+                            d_prior.data_ptr(), prior.shape[0], null(d_zref), null(d_vs), null(d_vz), null(d_vh), float(radius),
+                            float(quantile), int(min_points), float(down), float(up), float(lo), float(hi), gz.data_ptr(), gn.data_ptr(),
+                            gh.data_ptr(), src.data_ptr(), status.data_ptr(), gr.data_ptr(), _st()), "cm3d_box_ground")
+    return dict(ground_z=gz.cpu().numpy()[:M], ground_n=gn.cpu().numpy()[:M], ground_h=gh.cpu().numpy()[:M],
+                ground_src=src.cpu().numpy()[:M], ground_status=status.cpu().numpy()[:M], ground_zref=gr.cpu().numpy()[:M],
+                box=d_box.cpu().numpy()[:M])
+
+
 # ----------------------------------------------------------------------------- f4: SAM3D fusion matching
 def match_records(boxes7):
     """(n,7) [center_x, center_y, bottom_z, length, width, height, heading] -> (n,6) float64 records of

@@ -30,6 +30,7 @@ from . import nms as nmsmod
 from . import bevfit
 from . import boxplace
 from . import boxvertical as vtmod
+from . import boxground as grmod
 from . import dist as cdist
 from . import lifting
 from . import waymo as wm
@@ -79,7 +80,7 @@ def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0, hei
     """One scene through the hot path, its frames in one batch; returns its kept-box records as a list of device tensors
     (lifting.kept_box_records with column 5 = scene_index, column 6 = the frame's number inside the scene).  Masks of different image
     sizes -- Waymo's side cameras, inside every frame -- share the batch (lifting.pack_frames).  heights: a list that, with an engine
-    whose vertical stage is on, gets the (k,) heights of the returned records appended (column 2 of lifting.kept_box_sizes)."""
+    whose vertical or ground stage is on, gets the (k,) heights of the returned records appended (column 2 of lifting.kept_box_sizes)."""
     hb = lifting.pack_frames(frames, [lane_table], [0] * len(frames), classes)
     if masks == "dense":
         lifting.require_one_mask_size(hb)
@@ -90,7 +91,7 @@ def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0, hei
     torch.cuda.synchronize()
     eng.check_status()
     ids = np.array([[scene_index, int(f.token.rsplit(":", 1)[1])] for f in frames], np.float64)
-    if heights is not None and eng.vertical is not None:
+    if heights is not None and (eng.vertical is not None or eng.ground is not None):
         heights.append(lifting.kept_box_sizes(eng.b)[:, 2:3].contiguous())
     return [lifting.kept_box_records(eng.b, ids)]
 
@@ -99,7 +100,7 @@ def objects_from_records(rec, scenes, frames_dir, classes, meta=None, height=Non
     """Gathered records -> encoded metrics_pb2.Object payloads in the reference's order (scenes in order, frames in
     order, kept boxes in mask order; src/waymo/2d_to_3d.py:1034-1065,1262-1297).  The frame's context name and timestamp
     (:1050-1051) come from its extracted-frame file; the records only carry (scene index, frame number).
-    height: None -- every box has its class's prior height --, or the records' (k,) heights (the vertical stage's `vert_h`)."""
+    height: None -- every box has its class's prior height --, or the records' (k,) heights (the vertical stage's `vert_h`, the ground stage's `ground_h`)."""
     rec = np.asarray(rec, np.float64).reshape(-1, 10)
     if height is not None:
         height = np.asarray(height, np.float64).reshape(-1)
@@ -143,9 +144,11 @@ def main(argv=None):
     bevfit.add_arguments(ap)
     boxplace.add_arguments(ap)
     vtmod.add_arguments(ap)
+    grmod.add_arguments(ap)
     args = ap.parse_args(argv)
     place = boxplace.from_namespace(args, ap)       # (--place fit without --yaw fit: an error of the command line)
     vertical = vtmod.from_args(args, ap)            # (a --vertical-* flag without --vertical fit: the same)
+    ground = grmod.from_args(args, ap)              # (a --ground-* flag without --ground fit: the same)
     filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
     rank, world, local_rank = cdist.init_from_env()
@@ -158,7 +161,7 @@ def main(argv=None):
     classes = lifting.ClassTable.waymo(pri)
     eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args),
                              nms=nmsmod.from_args(args), yaw=bevfit.from_namespace(args), place=place,
-                             vertical=vertical)
+                             vertical=vertical, ground=ground)
     lo, hi = cdist.shard_range(len(scenes), rank, world)
     mine, meta, heights = [], {}, []
     for si in range(lo, hi):
@@ -173,7 +176,7 @@ def main(argv=None):
     # the single exchange of the job: fixed-size box records -> rank 0 (also the path of a one-rank run)
     gathered = cdist.gather_records(rec, dst=0)
     gathered_h = None
-    if vertical is not None:                       # the heights travel beside the records, in their order
+    if vertical is not None or ground is not None:  # the heights travel beside the records, in their order
         mine_h = torch.cat(heights, 0) if heights else torch.zeros(0, 1, dtype=torch.float64, device=eng.dev)
         gathered_h = cdist.gather_records(mine_h, dst=0)
     if world > 1:

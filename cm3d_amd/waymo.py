@@ -183,10 +183,11 @@ def encode_objects(objs):
 
 def objects_from_results(hb, res, classes, frame_meta):
     """Device results -> list of encoded Objects in the reference's order (frames in order, kept boxes in
-    mask order; :1034-1065, :1262-1297).  frame_meta: per frame (context_name, timestamp_micros).  A result that holds `vert_h` (an
-    engine with the vertical stage) gives every box that height in place of its class's prior."""
+    mask order; :1034-1065, :1262-1297).  frame_meta: per frame (context_name, timestamp_micros).  A result that holds `ground_h` (an
+    engine with the ground stage) or else `vert_h` (one with the vertical stage) gives every box that height in place of its class's
+    prior."""
     out = []
-    vert_h = res.get("vert_h")
+    height = res.get("ground_h", res.get("vert_h"))
     for f in range(hb.n_frames):
         ctx, ts = frame_meta[f]
         for m in range(hb.mask_off[f], hb.mask_off[f + 1]):
@@ -195,7 +196,7 @@ def objects_from_results(hb, res, classes, frame_meta):
             ci = hb.class_id[m]
             pr = classes.prior_wlh[ci]
             b = res["box"][m]
-            out.append(encode_object(b[0:3], length=pr[1], width=pr[0], height=pr[2] if vert_h is None else vert_h[m], heading=b[3],
+            out.append(encode_object(b[0:3], length=pr[1], width=pr[0], height=pr[2] if height is None else height[m], heading=b[3],
                                      type_id=WAYMO_TYPE[classes.out_names[ci]], score=hb.score[m], context_name=ctx,
                                      timestamp_micros=ts))
     return out

@@ -1208,6 +1208,75 @@ int cm3d_box_vertical(const float *xyz, const int32_t *off, int32_t n_masks, int
                       double *vert_z, double *vert_h, int32_t *vert_src, int32_t *vert_status, double *vert_entry_z,
                       cm3d_stream_t stream);
 
+/* ---- opt-in: ground height under each box from the frame's own sweep (csrc/ground.hip) ------------------------
+ * The bottom face of a box is a guess: box[m][2] of the pass is the medoid's z, and the vertical stage sees tops, not bottoms.  Objects
+ * stand on the ground, and the ground around an object is what the sweep measures best.  Here every mask bins the z of the points of
+ * its frame around its centre -- the first stage behind the projection that looks at a point outside a mask -- and takes a low
+ * quantile of the bins as the ground.  Per frame, no track, every class.  The defaults radius R = 3.0 m, quantile Q = 0.1,
+ * min_points = 20, window DOWN, UP = 5.0, 0.5 m, ratio LO, HI = 0.7, 1.3 are UNTUNED, all seven, and what the stage does to label
+ * quality has not been measured (it cannot be on synthetic scenes).  Host statement to the bit: cm3d_amd.boxground.box_ground_host.
+ * M = n_masks, F = n_frames.  All arithmetic of the rule is float64, every operation rounded on its own, no fma, no library call.
+ *
+ *  Points.     The points of frame f are the rows of its sweeps as the sweep preparation transforms them: the very float32 of
+ *              cm3d_sweep_prep's `points`.  Either the cloud is given -- points float[n_rows][4] (16-byte aligned) and pt_off int32[F+1],
+ *              frame f at rows [pt_off[f], pt_off[f+1]) -- or, with points or pt_off NULL, the raw rows: raw, raw_stride (4 and up: rows
+ *              of that many floats; CM3D_RAW_QUADS: the quad layout), sweep_xf float[n_sweeps][24], sweep_row_off int32[n_sweeps+1],
+ *              frame_sweep_off int32[F+1] and halfw as cm3d_sweep_prep takes them, read through its row addressing and fma chains: the
+ *              coordinates are bit-identical to the cloud's.  A row the preparation drops (|x| < halfw && |y| < halfw on the sensor-frame
+ *              x, y; halfw 0: none) is no point -- in the cloud it is NaN --, and a row with a non-finite coordinate is no point, which
+ *              covers the quad layout's padding rows.  Row offsets are clamped into [0, n_rows] and sweep offsets into [0, n_sweeps]
+ *              (an end below its start: empty) before use.  Lists and boxes share a frame (nuScenes global, Waymo vehicle).
+ *  Masks.      mask_off int32[F+1]: frame f holds masks [mask_off[f], mask_off[f+1]), start clamped to [0, M], end to [start, M].
+ *              A mask in no frame's range gets no output.
+ *  zref.       zref[m] = the reference height: the array zref double[M] when given, else box[m][2] as on entry.  With a vertical stage
+ *              in front the caller hands vert_entry_z, so that zref is box[m][2] as the pass left it.  Written out as ground_zref
+ *              double[M]; zref may alias ground_zref, so the stage alone can be run again on what a pass left.
+ *  Members.    cx = box[m][0], cy = box[m][1].  A point p (float32 px, py, pz) of the mask's frame is a member of mask m when
+ *              dx = (double)px - cx, dy = (double)py - cy, dx*dx + dy*dy <= R*R  (a point on the circle is a member), and with
+ *              z0 = zref - DOWN, dz = (DOWN + UP) / 128.0, t = ((double)pz - z0) / dz:  t >= 0 && t < 128.  Its bin is (int)t.
+ *              Masks of other frames never see the point; the object's own points are members like any other; a NaN centre has none.
+ *  Status.     ground_status int32[M], in this order: 4 cx, cy or zref not finite;  2 no member;  1 n < min_points, n = the number of
+ *              members (ground_n int32[M]; 0 with status 4);  0 otherwise.
+ *  Ground.     Status 0: k = (int)(Q * (double)(n - 1)), b* = the smallest bin whose cumulative count exceeds k,
+ *              ground_z double[M] = z0 + ((double)b* + 0.5) * dz.  Any other status: 0.  Status, n and ground_z are functions of the
+ *              cloud, the centre and zref alone and are written for every mask, whatever flags says.  The counts are integers: the
+ *              result does not depend on the order in which points arrive.
+ *  Apply.      c = box[m][8] >= 0 && box[m][8] < n_classes ? (int)box[m][8] : 0 and h0 = prior_wlh[3 c + 2], as cm3d_box_vertical reads
+ *              them.  Mask m is judged iff flags[m] & 1, status 0, and h0 is finite and > 0.  With g = ground_z[m]:
+ *                source 1, ground and top: vert_status / vert_z / vert_h are given (the engine has a vertical stage; all three or none),
+ *                          vert_status[m] == 0, t = vert_z[m][1], and LO <= (t - g) / h0 <= HI.  Then h = t - g, z = g + h * 0.5.
+ *                source 2, the prior stood on the ground: otherwise, if zref - g <= h0 + UP: h = h0, z = g + h0 * 0.5 (the medoid is
+ *                          no higher above the ground than the object is tall plus the window's margin; g - zref <= UP holds by the window).
+ *                source 0: otherwise, or not judged: box[m][2] untouched -- the vertical stage's value where it wrote one --, and h is
+ *                          what it was: vert_h[m] when given, else h0, bit for bit.
+ *              ground_src int32[M], ground_h double[M] = h;  for sources 1 and 2 box[m][2] = z.  Only column 2 of box is ever written;
+ *              flags is only read and no NMS is decided again (both use x and y only).
+ *
+ *  CM3D_ERR_ARG before any launch: R not finite and > 0, Q not in [0, 1] (NaN included), min_points < 1, DOWN or UP not finite,
+ *  DOWN <= 0, UP < 0, not 0 < LO <= HI < inf, a negative count, neither a cloud (points and pt_off) nor raw rows (raw, sweep_xf,
+ *  sweep_row_off, frame_sweep_off; raw_stride 4 and up or CM3D_RAW_QUADS), points not 16-byte aligned, and with M > 0: n_classes == 0,
+ *  F == 0, a NULL array (zref and the three vertical arrays may be NULL; those three only together).  M == 0: CM3D_OK, nothing launched.
+ *  max_masks_per_frame: the caller's knowledge of mask_off (it sizes the grid; a frame with more masks is still computed, by its
+ *  workgroups in turn).
+ *  One launch, k_box_ground: one workgroup of sixteen waves per (frame, chunk of the frame's masks).  A chunk holds at most
+ *  CM3D_GROUND_CHUNK = 64 masks; the launch takes smaller ones, down to 8, while that gives the chip more workgroups
+ *  (cm3d_box_ground_chunk says how many masks for a batch's shape; the result does not depend on it).  The chunk's centres and z0 sit
+ *  in LDS beside a 64 x CM3D_GROUND_BINS table of int32 counters (32 KB); the rectangle around the chunk's circles sits in registers,
+ *  and a point outside it skips the mask loop.  The workgroup streams the frame's rows once, sweep by sweep with the sweep's transform
+ *  uniform; a member does one integer LDS add.  Behind a barrier one wave per mask scans the 128 counters with a wave prefix sum, and the lane that
+ *  holds the ground applies the rule.  Per row 12 bytes (quads), 4 raw_stride, or 16 (the cloud), once per chunk of its frame.  Plain
+ *  stores, no global atomic, no workspace, no allocation, no read-back. */
+#define CM3D_GROUND_BINS 128
+#define CM3D_GROUND_CHUNK 64
+int32_t cm3d_box_ground_chunk(int32_t n_frames, int32_t max_masks_per_frame);
+int cm3d_box_ground(const float *points, const int32_t *pt_off, const float *raw, int32_t raw_stride, const float *sweep_xf,
+                    const int32_t *sweep_row_off, const int32_t *frame_sweep_off, int32_t n_sweeps, float halfw, int32_t n_rows,
+                    const int32_t *mask_off, int32_t n_frames, int32_t n_masks, int32_t max_masks_per_frame, double *box,
+                    const int32_t *flags, const double *prior_wlh, int32_t n_classes, const double *zref, const int32_t *vert_status,
+                    const double *vert_z, const double *vert_h, double radius, double quantile, int32_t min_points, double down, double up,
+                    double lo, double hi, double *ground_z, int32_t *ground_n, double *ground_h, int32_t *ground_src,
+                    int32_t *ground_status, double *ground_zref, cm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
