@@ -374,17 +374,20 @@ def add_ground_sheet(fr, centre_xy, z):
 _BATCHES, _PLAIN = {}, {}
 
 
-def pass_batch(name):
-    """`nusc` or `waymo`: tests/yaw_fit_pass_cases.py's two-frame batch -- parallel lanes, an L vehicle as every frame's last mask --
-    with the ground sheet in every frame (added before the L vehicle, whose mask is kept clear of other rows)."""
-    if name in _BATCHES:
-        return _BATCHES[name]
+def pass_batch(name, first=0, n_frames=2):
+    """`nusc` or `waymo`: tests/yaw_fit_pass_cases.py's batch -- parallel lanes, an L vehicle as every frame's last mask -- with the
+    ground sheet in every frame (added before the L vehicle, whose mask is kept clear of other rows).  Synthetic frames first ..
+    first + n_frames - 1: two frames from 0 unless told otherwise, as yaw_fit_pass_cases.batch takes them."""
+    key = name if (first, n_frames) == (0, 2) else (name, first, n_frames)         # pass_plain knows the default batch by its name
+    if key in _BATCHES:
+        return _BATCHES[key]
     from cm3d_amd import lifting
     from cm3d_amd import synthetic as syn
     from tests import yaw_fit_pass_cases as yc
+    ids = range(first, first + n_frames)
     if name == "nusc":
         cfg = syn.config("tiny", n_points=9000, n_masks=20, width=512, height=288, ratio=0.32, max_area=12000.0)
-        frames = [syn.make_frame(cfg, i) for i in range(2)]
+        frames = [syn.make_frame(cfg, i) for i in ids]
         classes = lifting.ClassTable.nuscenes()
         for f in frames:
             add_ground_sheet(f, (0.0, 0.0), -1.84 - 0.15)
@@ -392,7 +395,7 @@ def pass_batch(name):
         heading = [yc.add_l_vehicle(f, yc.LANE_YAW[name]) for f in frames]
     else:
         cfg = syn.config("tiny", n_cams=5, n_points=9000, n_masks=17, width=512, height=288, ratio=0.32, max_area=12000.0)
-        frames = [syn.make_waymo_frame(cfg, i) for i in range(2)]
+        frames = [syn.make_waymo_frame(cfg, i) for i in ids]
         classes = lifting.ClassTable.waymo()
         for f in frames:                            # the rows are in the vehicle frame: the sensor stands at x = 0.94, the ground at z = 0
             # (no ego box here: the rows on the vehicle itself go, so that a mask without a box -- centre 0, 0 -- has no member)
@@ -401,11 +404,11 @@ def pass_batch(name):
         poses = [np.asarray(f.pose, np.float64).reshape(4, 4) for f in frames]
         lanes = [yc.parallel_lanes(P[:2, 3], yc.LANE_YAW[name]) for P in poses]
         heading = [yc.add_l_vehicle(f, yc.LANE_YAW[name], P) for f, P in zip(frames, poses)]
-    frame_lane = [0, 1]
+    frame_lane = list(range(n_frames))
     hb = lifting.pack_frames(frames, lanes, frame_lane, classes)
-    _BATCHES[name] = SimpleNamespace(name=name, frames=frames, lanes=lanes, frame_lane=frame_lane, hb=hb, classes=classes,
-                                     l_masks=[int(m) - 1 for m in hb.mask_off[1:]], l_heading=heading)
-    return _BATCHES[name]
+    _BATCHES[key] = SimpleNamespace(name=name, frames=frames, lanes=lanes, frame_lane=frame_lane, hb=hb, classes=classes,
+                                    l_masks=[int(m) - 1 for m in hb.mask_off[1:]], l_heading=heading)
+    return _BATCHES[key]
 
 
 def pass_plain(orc, name):

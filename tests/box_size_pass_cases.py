@@ -62,13 +62,15 @@ def host_size(hb, classes, src, tr, place, v, smooth_window=0, s=S):
                                  thin=place.thin, max_dt=v.max_dt, smooth_window=smooth_window, q=s.q, min_obs=s.min_obs, lo=s.lo, hi=s.hi)
 
 
-def composed(orc, front=None, nms=None, tracks=(1, "own", 0), s=S, y=Y, p=P):
+def composed(orc, front=None, nms=None, tracks=(1, "own", 0), s=S, y=Y, p=P, b=None):
     """The whole chain on the CPU, nothing from the device: `front` (the expectation of the pass in front of the fit; the oracle's plain
     pass when None), the yaw fit, the placement with its circle NMS, the rotated NMS when given, the velocity stage, the track stage with
-    `tracks` = (min_length, score, smooth_window), the size stage.  Returns (the arrays in front of the size stage, its outputs)."""
+    `tracks` = (min_length, score, smooth_window), the size stage.  b: a batch built like batch() (frames, lanes, frame_lane, hb,
+    classes); batch() itself when None.  Returns (the arrays in front of the size stage, its outputs)."""
     from tests import optin_pass_cases as oc
     from tests.helpers import oracle_batch
-    b = batch()
+    if b is None:
+        b = batch()
     hb = b.hb
     if front is None:
         front = oracle_batch(orc, b.frames, b.lanes, b.frame_lane, hb)
