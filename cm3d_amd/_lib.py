@@ -34,6 +34,7 @@ DEPTH_CLUSTER_LDS_POINTS = 4096   # longest list cm3d_depth_cluster sorts in LDS
 BEV_FIT_CHUNK = 512      # points of a list cm3d_bev_fit stages in LDS at a time
 VERT_LANE_MAX, VERT_LDS_KEYS = 64, 4096      # cm3d_box_vertical: the longest list of the lane route, the most keys staged in LDS
 GROUND_BINS = 128        # cm3d_box_ground: the bins of a mask's window
+GROUND_GRID_CELLS, GROUND_GRID_BINS = 64, 64      # cm3d_ground_grid: cells per side of a frame's grid, bins of a cell's window
 RAW_QUADS = 3           # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -131,6 +132,13 @@ SIGNATURES = {
     "cm3d_box_ground_chunk": (_i32, [_i32, _i32]),
     "cm3d_box_ground": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i32, _f32, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _i32, _p, _p, _p, _p,
                                C.c_double, C.c_double, _i32, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p]),
+    "cm3d_ground_strip_check": (_i32, [C.c_double, C.c_double, C.c_double, C.c_double, _i32, C.c_double, _i32]),
+    "cm3d_ground_grid": (_i32, [_p, _p, _p, _i32, _p, _p, _p, _i32, _f32, _i32, _p, _i32, C.c_double, C.c_double, C.c_double, C.c_double,
+                                _i32, _p, _p, _p]),
+    "cm3d_ground_strip_workspace_bytes": (_i64, [_i32, _i32]),
+    "cm3d_ground_strip": (_i32, [_p, _p, _p, _p, _i32, _i32, _p, _p, _i32, C.c_double, C.c_double, _i32, _p, _p, _p, _p, _p, _p, _p, _i64,
+                                 _p]),
+    "cm3d_lift_pass_stripped": (_i32, [_p, _p, _p, _p, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order
@@ -191,6 +199,14 @@ class LiftPassOptions(C.Structure):
 class BoxPlaceDesc(C.Structure):
     """cm3d_box_place_desc of include/cm3d_hip.h, field for field."""
     _fields_ = [("size", _i64), ("place_src", _p), ("place_pushed", _p), ("ev", _p * 2), ("thin", C.c_double)]
+
+
+class GroundStripDesc(C.Structure):
+    """cm3d_ground_strip_desc of include/cm3d_hip.h, field for field."""
+    _fields_ = ([("size", _i64)] + [(n, _p) for n in ("origin", "grid_z", "grid_n", "gs_off", "gs_tile_off", "gs_idx", "gs_xyz", "gs_status",
+                                                      "gs_dropped", "ws")]
+                + [("ws_bytes", _i64), ("ev", _p * 2)] + [(n, C.c_double) for n in ("cell", "down", "up", "quantile", "margin")]
+                + [("min_points", _i32), ("min_keep", _i32)])
 
 
 class Cm3dError(RuntimeError):

@@ -4,25 +4,19 @@
 //                            CM3D_DEPTH_CLUSTER_LDS_POINTS points, in the workspace beyond --, then one wave walks the sorted ranges 64 at a
 //                            time (ballot of the boundary flags, the segment that ends at each boundary, a wave-wide choice) and the
 //                            workgroup writes one keep byte per list position and the kept count
-//   k_depth_cluster_scan     one workgroup: cl_off, cl_tile_off
-//   k_depth_cluster_scatter  one workgroup per mask: stable compaction of hit_idx / hit_xyz by the keep bytes (ballot + prefix)
-// Every offset read from hit_off is clamped into [0, idx_cap] first (dc_range), and the scatter checks its destination: nothing at or
+//   k_list_compact_scan      one workgroup: cl_off, cl_tile_off                                                (csrc/list_compact.h,
+//   k_list_compact_scatter   one workgroup per mask: stable compaction of hit_idx / hit_xyz by the keep bytes   shared with groundstrip.hip)
+// Every offset read from hit_off is clamped into [0, idx_cap] first (lc_range), and the scatter checks its destination: nothing at or
 // beyond idx_cap is touched whatever the offsets hold.  The keys are distinct (the position breaks ties), so the sorted order -- and
 // with it every output byte -- is the same on every run.
 #include "common.h"
+#include "list_compact.h"
 
 #define DC_THREADS 256
 #define DC_WAVES (DC_THREADS / CM3D_WAVE)
 #define DC_L CM3D_DEPTH_CLUSTER_LDS_POINTS
 
-struct DcRange { int lo, n; };
-static __device__ __forceinline__ DcRange dc_range(const int32_t *hit_off, int m, int idx_cap)
-{
-    int lo = hit_off[m], hi = hit_off[m + 1];
-    lo = lo < 0 ? 0 : (lo > idx_cap ? idx_cap : lo);
-    hi = hi < lo ? lo : (hi > idx_cap ? idx_cap : hi);
-    return DcRange{lo, hi - lo};
-}
+static_assert(DC_THREADS == LC_THREADS, "the scatter's workgroup is the clustering's");
 
 // non-negative doubles order like their bit patterns
 static __device__ __forceinline__ uint64_t dc_key(const float4 p, double ox, double oy, double oz)
@@ -132,7 +126,7 @@ __global__ __launch_bounds__(DC_THREADS) void k_depth_cluster(const float4 *hit_
     __shared__ uint32_t s_pos[DC_L];
     __shared__ int s_res[2];
     const int m = blockIdx.x;
-    const DcRange r = dc_range(hit_off, m, idx_cap);
+    const LcRange r = lc_range(hit_off, m, idx_cap);
     if (r.n == 0) {
         if (threadIdx.x == 0) {
             count[m] = 0;
@@ -148,62 +142,6 @@ __global__ __launch_bounds__(DC_THREADS) void k_depth_cluster(const float4 *hit_
     else
         dc_mask(g_key + r.lo, g_pos + r.lo, hit_xyz + r.lo, r.n, ox, oy, oz, eps, min_points, pick, keep + r.lo, count + m, cl_status + m,
                 s_res);
-}
-
-__global__ __launch_bounds__(1024) void k_depth_cluster_scan(const int32_t *count, int n_masks, int32_t *cl_off, int32_t *cl_tile_off)
-{
-    __shared__ int s_a[16], s_b[16];
-    int base_o = 0, base_t = 0;
-    for (long long m0 = 0; m0 < n_masks; m0 += 1024) {
-        const long long m = m0 + threadIdx.x;
-        const int c = m < n_masks ? count[m] : 0;
-        int tot_o, tot_t;
-        const int eo = cm3d_block1024_excl_scan(c, s_a, tot_o);
-        const int et = cm3d_block1024_excl_scan((c + CM3D_MEDOID_TILE - 1) / CM3D_MEDOID_TILE, s_b, tot_t);
-        if (m < n_masks) {
-            cl_off[m] = base_o + eo;
-            cl_tile_off[m] = base_t + et;
-        }
-        base_o += tot_o;
-        base_t += tot_t;
-    }
-    if (threadIdx.x == 0) {
-        cl_off[n_masks] = base_o;
-        cl_tile_off[n_masks] = base_t;
-    }
-}
-
-__global__ __launch_bounds__(DC_THREADS) void k_depth_cluster_scatter(const float4 *hit_xyz, const int32_t *hit_idx, const int32_t *hit_off,
-                                                                      int idx_cap, const uint8_t *keep, const int32_t *cl_off,
-                                                                      int32_t *cl_idx, float4 *cl_xyz)
-{
-    __shared__ int s_cnt[DC_WAVES];
-    const int m = blockIdx.x, lane = cm3d_lane(), wave = threadIdx.x >> 6;
-    const DcRange r = dc_range(hit_off, m, idx_cap);
-    long long out = cl_off[m];
-    for (long long base = 0; base < r.n; base += DC_THREADS) {
-        const long long i = base + threadIdx.x;
-        const bool k = i < r.n && keep[r.lo + i] != 0;
-        const uint64_t b = __ballot(k);
-        if (lane == 0) s_cnt[wave] = __popcll(b);
-        __syncthreads();
-        int pre = 0, tot = 0;
-#pragma unroll
-        for (int w = 0; w < DC_WAVES; ++w) {
-            const int c = s_cnt[w];
-            if (w < wave) pre += c;
-            tot += c;
-        }
-        if (k) {
-            const long long d = out + pre + cm3d_mbcnt(b);
-            if (d >= 0 && d < idx_cap) {                 // (offsets that describe more than exists: nothing lands out of range)
-                cl_xyz[d] = hit_xyz[r.lo + i];
-                if (hit_idx) cl_idx[d] = hit_idx[r.lo + i];
-            }
-        }
-        out += tot;
-        __syncthreads();
-    }
 }
 
 extern "C" int64_t cm3d_depth_cluster_workspace_bytes(int32_t n_masks, int32_t idx_cap)
@@ -232,9 +170,9 @@ extern "C" int cm3d_depth_cluster(const float *hit_xyz, const int32_t *hit_idx, 
     hipLaunchKernelGGL(k_depth_cluster, dim3(n_masks), dim3(DC_THREADS), 0, st, (const float4 *)hit_xyz, hit_off, mask_frame, idx_cap, origin,
                        n_frames, eps, min_points, pick, g_key, g_pos, keep, count, cl_status);
     CM3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_depth_cluster_scan, dim3(1), dim3(1024), 0, st, count, n_masks, cl_off, cl_tile_off);
+    hipLaunchKernelGGL(k_list_compact_scan, dim3(1), dim3(1024), 0, st, count, n_masks, cl_off, cl_tile_off);
     CM3D_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_depth_cluster_scatter, dim3(n_masks), dim3(DC_THREADS), 0, st, (const float4 *)hit_xyz, hit_idx, hit_off, idx_cap,
+    hipLaunchKernelGGL(k_list_compact_scatter, dim3(n_masks), dim3(DC_THREADS), 0, st, (const float4 *)hit_xyz, hit_idx, hit_off, idx_cap,
                        keep, cl_off, cl_idx, (float4 *)cl_xyz);
     CM3D_CHECK_LAUNCH();
     return CM3D_OK;

@@ -1,9 +1,11 @@
 // Host side of the opt-in stages of a pass (cm3d_lift_pass_opt, include/cm3d_hip.h): the depth clustering between the halves of the
-// plain pass, and behind it the stage-2 filter, the yaw fit and the rotated-box NMS.  The only statement of a composed pass's order.  No
+// plain pass, and behind it the stage-2 filter, the yaw fit and the rotated-box NMS.  The only statement of a composed pass's order
+// (csrc/pass_strip.cpp enters it behind the seam, on the stripped lists, through cm3d_pass_seam_run below).  No
 // kernel lives here, and csrc/pipeline.cpp knows nothing of this file: the plain pass and cm3d_pipe_submit stay what they are.
 #include <hip/hip_runtime_api.h>
 
 #include "../../include/cm3d_hip.h"
+#include "pass_seam.h"
 
 static int record(void *ev, cm3d_stream_t st)
 {
@@ -61,26 +63,21 @@ extern "C" int cm3d_yaw_fit_boxes(const cm3d_lift_pass_desc *d, const cm3d_yaw_f
                    y->medoid_pos ? y->medoid_pos : d->medoid_pos, st);
 }
 
-extern "C" int cm3d_lift_pass_opt(const cm3d_lift_pass_desc *d, const cm3d_lift_pass_options *o, cm3d_stream_t st)
+// A composed pass behind the seam, on the lists of `l`: `d` itself (nothing has been enqueued yet: the head runs here), or a copy of `d`
+// with other lists in hit_off, tile_off, hit_idx, hit_xyz and no tile_work (the head has run and something stands between it and the
+// clustering: csrc/pass_strip.cpp).  Every descriptor has been checked.
+static int behind(const cm3d_lift_pass_desc *d, const cm3d_lift_pass_desc *l, const cm3d_depth_cluster_desc *c, const cm3d_stage2_filter_desc *f,
+                  const cm3d_yaw_fit_desc *y, const cm3d_rotated_nms_desc *n, cm3d_stream_t st)
 {
-    if (o && o->size != (int64_t)sizeof *o) return CM3D_ERR_ARG;
-    if (!o || (!o->cluster && !o->filter && !o->yaw && !o->nms)) return cm3d_lift_pass(d, st);
-    const auto *c = o->cluster;
-    const auto *f = o->filter;
-    const auto *y = o->yaw;
-    const auto *n = o->nms;
-    if (!usable(d) || (c && !usable(c, d->hit_idx)) || (f && !usable(f)) || (y && !usable(y)) || (n && !usable(n))) return CM3D_ERR_ARG;
     // what the later stages read: the clustered lists when there are any, the positions the filter kept when there is one
-    const float *xyz = c ? c->cl_xyz : d->hit_xyz;
-    const int32_t *off = c ? c->cl_off : d->hit_off;
+    const float *xyz = c ? c->cl_xyz : l->hit_xyz;
+    const int32_t *off = c ? c->cl_off : l->hit_off;
     const int32_t *pos = f ? f->medoid_pos_kept : d->medoid_pos;
-    if (y && ((y->hit_xyz && y->hit_xyz != xyz) || (y->hit_off && y->hit_off != off) || (y->medoid_pos && y->medoid_pos != pos)))
-        return CM3D_ERR_ARG;
     int rc;
     if (c) {
-        if ((rc = cm3d_lift_pass_head(d, st)) != CM3D_OK || (rc = record(c->ev[0], st)) != CM3D_OK) return rc;
-        rc = cm3d_depth_cluster(d->hit_xyz, d->hit_idx, d->hit_off, d->mask_frame, d->n_masks, d->idx_cap, c->origin, d->n_frames, c->eps,
-                                c->min_points, c->pick, c->cl_off, c->cl_tile_off, d->hit_idx ? c->cl_idx : nullptr, c->cl_xyz, c->cl_status,
+        if ((l == d && (rc = cm3d_lift_pass_head(d, st)) != CM3D_OK) || (rc = record(c->ev[0], st)) != CM3D_OK) return rc;
+        rc = cm3d_depth_cluster(l->hit_xyz, l->hit_idx, l->hit_off, d->mask_frame, d->n_masks, d->idx_cap, c->origin, d->n_frames, c->eps,
+                                c->min_points, c->pick, c->cl_off, c->cl_tile_off, l->hit_idx ? c->cl_idx : nullptr, c->cl_xyz, c->cl_status,
                                 c->ws, c->ws_bytes, st);
         if (rc != CM3D_OK || (rc = record(c->ev[1], st)) != CM3D_OK) return rc;
         // the rest of the pass on the clustered lists; their work list is built by the medoid stage (tile_work belongs to the raw lists)
@@ -88,7 +85,7 @@ extern "C" int cm3d_lift_pass_opt(const cm3d_lift_pass_desc *d, const cm3d_lift_
         t.hit_off = c->cl_off, t.tile_off = c->cl_tile_off, t.hit_idx = c->cl_idx, t.hit_xyz = c->cl_xyz, t.tile_work = nullptr;
         rc = cm3d_lift_pass_tail(&t, st);
     } else
-        rc = cm3d_lift_pass(d, st);
+        rc = l == d ? cm3d_lift_pass(d, st) : cm3d_lift_pass_tail(l, st);
     if (rc != CM3D_OK) return rc;
     if (f) {
         if ((rc = record(f->ev[0], st)) != CM3D_OK) return rc;
@@ -104,6 +101,43 @@ extern "C" int cm3d_lift_pass_opt(const cm3d_lift_pass_desc *d, const cm3d_lift_
         rc = cm3d_box_rotated_nms(d->box, d->flags, d->mask_off, d->n_frames, d->n_masks, d->class_id, d->prior_wlh, d->nms_group,
                                   d->n_classes, n->thr, n->n_thr, n->measure, n->class_agnostic, d->pose_inv != nullptr, bound(d), st);
     return rc;
+}
+
+// every present descriptor, and yaw's own statement of its lists and positions: each NULL or what `behind` derives for the lists of `l`
+static bool checked(const cm3d_lift_pass_desc *d, const cm3d_lift_pass_desc *l, const cm3d_lift_pass_options *o)
+{
+    if (!usable(d) || !l || (o && o->size != (int64_t)sizeof *o)) return false;
+    if (!o) return true;
+    const auto *c = o->cluster;
+    const auto *f = o->filter;
+    const auto *y = o->yaw;
+    const auto *n = o->nms;
+    if ((c && !usable(c, l->hit_idx)) || (f && !usable(f)) || (y && !usable(y)) || (n && !usable(n))) return false;
+    const float *xyz = c ? c->cl_xyz : l->hit_xyz;
+    const int32_t *off = c ? c->cl_off : l->hit_off;
+    const int32_t *pos = f ? f->medoid_pos_kept : d->medoid_pos;
+    return !(y && ((y->hit_xyz && y->hit_xyz != xyz) || (y->hit_off && y->hit_off != off) || (y->medoid_pos && y->medoid_pos != pos)));
+}
+
+extern "C" int cm3d_lift_pass_opt(const cm3d_lift_pass_desc *d, const cm3d_lift_pass_options *o, cm3d_stream_t st)
+{
+    if (o && o->size != (int64_t)sizeof *o) return CM3D_ERR_ARG;
+    if (!o || (!o->cluster && !o->filter && !o->yaw && !o->nms)) return cm3d_lift_pass(d, st);
+    if (!checked(d, d, o)) return CM3D_ERR_ARG;
+    return behind(d, d, o->cluster, o->filter, o->yaw, o->nms, st);
+}
+
+// The seam for csrc/pass_strip.cpp (declared in csrc/pass_seam.h, no part of include/cm3d_hip.h): the check of a composed pass's
+// descriptors for the lists of `l`, and the pass behind the seam on them (opt may be NULL: the tail alone).
+extern "C" int cm3d_pass_seam_check(const cm3d_lift_pass_desc *d, const cm3d_lift_pass_desc *l, const cm3d_lift_pass_options *o)
+{
+    return checked(d, l, o) ? CM3D_OK : CM3D_ERR_ARG;
+}
+
+extern "C" int cm3d_pass_seam_run(const cm3d_lift_pass_desc *d, const cm3d_lift_pass_desc *l, const cm3d_lift_pass_options *o, cm3d_stream_t st)
+{
+    if (!checked(d, l, o)) return CM3D_ERR_ARG;
+    return behind(d, l, o ? o->cluster : nullptr, o ? o->filter : nullptr, o ? o->yaw : nullptr, o ? o->nms : nullptr, st);
 }
 
 // the single-option passes: cm3d_lift_pass_opt with that member set (a null member is an error here, not the plain pass)

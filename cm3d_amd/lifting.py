@@ -32,6 +32,7 @@ from .tracks import Tracks  # noqa: F401  (LiftEngine(velocity=Velocity(...), tr
 from .boxsize import BoxSize  # noqa: F401  (LiftEngine(yaw=..., place=..., velocity=..., size=BoxSize(...)))
 from .boxvertical import BoxVertical, RESULTS as VERTICAL_RESULTS  # noqa: F401  (LiftEngine(vertical=BoxVertical(...)))
 from .boxground import BoxGround, RESULTS as GROUND_RESULTS  # noqa: F401  (LiftEngine(ground=BoxGround(...)))
+from .groundstrip import GroundStrip, N_CELLS as GRID_CELLS  # noqa: F401  (LiftEngine(strip=GroundStrip(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -456,7 +457,8 @@ class LiftEngine:
                  hits_per_point=4.0, keep_colsum=False, keep_cloud=None, lane_cache=None, obb=False, filters: Optional[Stage2Filters] = None,
                  cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None,
                  velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None, place: Optional[BoxPlace] = None,
-                 size: Optional[BoxSize] = None, vertical: Optional[BoxVertical] = None, ground: Optional[BoxGround] = None):
+                 size: Optional[BoxSize] = None, vertical: Optional[BoxVertical] = None, ground: Optional[BoxGround] = None,
+                 strip: Optional[GroundStrip] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -502,7 +504,15 @@ class LiftEngine:
         streams every frame's sweep rows once more -- the raw rows, or the cloud where the engine has materialised it; it never makes the
         engine materialise it --, takes a low quantile of the heights around every box as its ground and rewrites column 2 of `box`
         where the box can be stood on it.  download() adds `ground_z`, `ground_n`, `ground_h`, `ground_src`, `ground_status` and
-        `ground_zref`; column 2 of kept_box_sizes' rows is then `ground_h`.  None: no buffer, no call.  Its seven parameters are untuned."""
+        `ground_zref`; column 2 of kept_box_sizes' rows is then `ground_h`.  None: no buffer, no call.  Its seven parameters are untuned.
+        strip: the ground strip (groundstrip.GroundStrip; nuScenes and Waymo batches, with any other option or none): directly behind the
+        compaction a grid of ground heights is taken from every frame's own sweep rows (cm3d_ground_grid; the raw rows, or the cloud where
+        the engine has materialised it -- it never makes the engine materialise it) and every in-mask list loses its ground points
+        (cm3d_ground_strip), both enqueued by cm3d_lift_pass_stripped.  The clustering, the medoid, the yaw fit and the vertical stage then
+        read the stripped lists: `medoid_pos` is a position in the lists the medoid saw -- the clustered ones (`cl_off`) when the engine
+        clusters, else the stripped ones (`gs_off`) --, while `hit_off` / `hit_idx` / `hit_xyz` stay the raw lists.  download() adds
+        `gs_off`, `gs_status`, `gs_dropped` (full=True: `gs_idx`, `gs_xyz`, `grid_z`, `grid_n`).  None: no buffer, no launch.  Its seven
+        parameters are untuned."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -522,6 +532,10 @@ class LiftEngine:
         self.size = size if size is not None and size.active else None
         self.vertical = vertical if vertical is not None and vertical.active else None
         self.ground = ground if ground is not None and ground.active else None
+        self.strip = strip if strip is not None and strip.active else None
+        if self.strip is not None and self.obb:
+            raise ValueError("strip=GroundStrip(...) is stated for nuScenes and Waymo lists (z up); KITTI's rect frame has y down: it cannot be "
+                             "enabled with obb=True")
         if self.ground is not None and self.obb:
             raise ValueError("ground=BoxGround(...) is stated for nuScenes and Waymo boxes (z up); KITTI's rect frame has y down and "
                              "its own + h / 2: it cannot be enabled with obb=True")
@@ -670,6 +684,12 @@ class LiftEngine:
             b.cl_idx = e(b.idx_cap); b.cl_xyz = e(b.idx_cap, 4, dtype=torch.float32)
             b.cl_ws_bytes = int(L.cm3d_depth_cluster_workspace_bytes(M, b.idx_cap))
             b.cl_ws = torch.empty(max(b.cl_ws_bytes, 16), dtype=torch.uint8, device=d)
+        if self.strip is not None:
+            b.gs_off = e(M + 1); b.gs_tile_off = e(M + 1); b.gs_status = e(M); b.gs_dropped = e(M)
+            b.gs_idx = e(b.idx_cap); b.gs_xyz = e(b.idx_cap, 4, dtype=torch.float32)
+            b.grid_z = e(F, GRID_CELLS, dtype=torch.float64); b.grid_n = e(F, GRID_CELLS)
+            b.gs_ws_bytes = int(L.cm3d_ground_strip_workspace_bytes(M, b.idx_cap))
+            b.gs_ws = torch.empty(max(b.gs_ws_bytes, 16), dtype=torch.uint8, device=d)
         if self.yaw is not None:
             b.fit_k = e(M); b.fit_status = e(M); b.fit_rect = e(M, _lib.MATCH_BOX_STRIDE, dtype=torch.float64)
             b.yaw_tab = e(M, 3, dtype=torch.float32); b.yaw_idx = e(M); b.yaw_src = e(M)
@@ -733,10 +753,14 @@ class LiftEngine:
             setattr(b, name + "_desc", desc)
             setattr(b.opts, name, ctypes.addressof(desc))
         b.timed = {name: desc for name, desc in stages.items() if name != "nms"}
+        if self.strip is not None:             # (no member of the options: cm3d_lift_pass_stripped takes it beside them; its events stand in front of the clustering's)
+            b.strip_desc = self._strip_descriptor(b)
+            b.timed = {**{k: v for k, v in b.timed.items() if k == "filter"}, "strip": b.strip_desc,
+                       **{k: v for k, v in b.timed.items() if k != "filter"}}
         if self.place is not None:             # (no member of the options: cm3d_lift_pass_placed takes it beside them; its events come last)
             b.place_desc = b.timed["place"] = self._place_descriptor(b)
         b.opts_ref = ctypes.byref(b.opts) if stages else None
-        b.plain_pass = not stages and self.velocity is None and self.vertical is None and self.ground is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
+        b.plain_pass = not stages and self.velocity is None and self.vertical is None and self.ground is None and self.strip is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
         self.b = b
         return b
 
@@ -780,6 +804,29 @@ class LiftEngine:
         c.eps, c.min_points, c.pick = self.cluster.eps, self.cluster.min_points, self.cluster.pick_index
         return c
 
+    def _strip_descriptor(self, b):
+        """cm3d_ground_strip_desc of the resident batch (refresh_pass_descriptor sets its events).  The origin of frame f is ego_xyz[f], as
+        the clustering's."""
+        s, g = _lib.GroundStripDesc(), self.strip
+        s.size = ctypes.sizeof(_lib.GroundStripDesc)
+        s.origin = _ptr(b.ego_xyz)
+        for name in ("grid_z", "grid_n", "gs_off", "gs_tile_off", "gs_idx", "gs_xyz", "gs_status", "gs_dropped"):
+            setattr(s, name, _ptr(getattr(b, name)))
+        s.ws, s.ws_bytes = _ptr(b.gs_ws), b.gs_ws_bytes
+        s.cell, s.down, s.up, s.quantile, s.margin = g.cell, g.down, g.up, g.quantile, g.margin
+        s.min_points, s.min_keep = g.min_points, g.min_keep
+        return s
+
+    def read_lists(self, b=None):
+        """The lists the stages behind the seam read, as (xyz, off) device tensors of the resident batch (or of `b`): the clustered ones
+        when the engine clusters, else the stripped ones when it strips, else the raw ones.  `medoid_pos` is a position in them."""
+        b = self.b if b is None else b
+        if self.cluster is not None:
+            return b.cl_xyz, b.cl_off
+        if self.strip is not None:
+            return b.gs_xyz, b.gs_off
+        return b.hit_xyz, b.hit_off
+
     def _yaw_descriptor(self, b):
         """cm3d_yaw_fit_desc of the resident batch (refresh_pass_descriptor sets its events).  The lists that are fitted are the clustered
         ones when the engine clusters, the positions that decide about a box the kept ones when it filters: what cm3d_lift_pass_opt
@@ -787,8 +834,9 @@ class LiftEngine:
         y = _lib.YawFitDesc()
         y.size = ctypes.sizeof(_lib.YawFitDesc)
         y.angle_cs = _ptr(self.angle_cs)
-        if self.cluster is not None:
-            y.hit_xyz, y.hit_off = _ptr(b.cl_xyz), _ptr(b.cl_off)
+        if self.cluster is not None or self.strip is not None:
+            xyz, off = self.read_lists(b)
+            y.hit_xyz, y.hit_off = _ptr(xyz), _ptr(off)
         if self.filters is not None:
             y.medoid_pos = _ptr(b.medoid_pos_kept)
         for name in ("fit_k", "fit_rect", "fit_status", "yaw_tab", "yaw_idx", "yaw_src"):
@@ -1055,12 +1103,30 @@ class LiftEngine:
                                 _ptr(b.obb_ws), b.obb_ws_bytes, st), "cm3d_obb")
 
     def stage_cluster(self, st):
-        """The depth clustering alone, on the raw lists the last pass left resident (cm3d_depth_cluster: what the clustered pass
-        enqueues between the compaction and the medoid)."""
+        """The depth clustering alone, on the raw lists the last pass left resident -- the stripped ones when the engine strips --
+        (cm3d_depth_cluster: what the clustered pass enqueues between the compaction, or the strip, and the medoid)."""
         b, c = self.b, self.b.cluster_desc
+        if self.strip is not None:                       # (what the stripped pass clusters)
+            check(self.lib.cm3d_depth_cluster(_ptr(b.gs_xyz), _ptr(b.gs_idx), _ptr(b.gs_off), _ptr(b.mask_frame), b.M, b.idx_cap, c.origin, b.F,
+                                              c.eps, c.min_points, c.pick, c.cl_off, c.cl_tile_off, c.cl_idx, c.cl_xyz, c.cl_status, c.ws,
+                                              c.ws_bytes, st), "cm3d_depth_cluster")
+            return
         check(self.lib.cm3d_depth_cluster(_ptr(b.hit_xyz), _ptr(b.hit_idx), _ptr(b.hit_off), _ptr(b.mask_frame), b.M, b.idx_cap, c.origin, b.F,
                                           c.eps, c.min_points, c.pick, c.cl_off, c.cl_tile_off, c.cl_idx, c.cl_xyz, c.cl_status, c.ws,
                                           c.ws_bytes, st), "cm3d_depth_cluster")
+
+    def stage_ground_strip(self, st):
+        """The ground strip alone, on the sweep rows and the raw lists the last pass left resident (cm3d_ground_grid, cm3d_ground_strip:
+        what the stripped pass enqueues between the compaction and the clustering)."""
+        b, s = self.b, self.b.strip_desc
+        cloud = b.points is not None
+        check(self.lib.cm3d_ground_grid(_ptr(b.points) if cloud else None, _ptr(b.pt_off) if cloud else None, None if cloud else _ptr(b.raw),
+                                        b.hb.raw_stride, _ptr(b.sweep_xf), _ptr(b.sweep_row_off), _ptr(b.frame_sweep_off), b.S, b.halfw, b.pt_cap,
+                                        s.origin, b.F, s.cell, s.down, s.up, s.quantile, s.min_points, s.grid_z, s.grid_n, st),
+              "cm3d_ground_grid")
+        check(self.lib.cm3d_ground_strip(_ptr(b.hit_xyz), _ptr(b.hit_idx), _ptr(b.hit_off), _ptr(b.mask_frame), b.M, b.idx_cap, s.origin,
+                                         s.grid_z, b.F, s.cell, s.margin, s.min_keep, s.gs_off, s.gs_tile_off, s.gs_idx, s.gs_xyz, s.gs_status,
+                                         s.gs_dropped, s.ws, s.ws_bytes, st), "cm3d_ground_strip")
 
     def stage_yaw_fit(self, st):
         """The yaw fit's three launches alone, on what the last pass left resident (cm3d_yaw_fit_boxes: cm3d_bev_fit, cm3d_yaw_select,
@@ -1070,7 +1136,8 @@ class LiftEngine:
     def stage_bev_fit(self, st):
         """cm3d_bev_fit alone, on the lists the yaw-fitted pass fits."""
         b, y = self.b, self.b.yaw_desc
-        check(self.lib.cm3d_bev_fit(y.hit_xyz or _ptr(b.hit_xyz), y.hit_off or _ptr(b.hit_off), b.M, b.idx_cap, y.angle_cs, y.K, y.d0,
+        xyz, off = self.read_lists()
+        check(self.lib.cm3d_bev_fit(_ptr(xyz), _ptr(off), b.M, b.idx_cap, y.angle_cs, y.K, y.d0,
                                     y.min_points, y.min_length, y.fit_k, y.fit_rect, y.fit_status, st), "cm3d_bev_fit")
 
     def stage_rotated_nms(self, st):
@@ -1119,9 +1186,9 @@ class LiftEngine:
 
     def stage_vertical(self, st):
         """The opt-in vertical stage alone, on the lists and the box rows the last pass left resident (cm3d_box_vertical): the clustered
-        lists when the engine clusters, the raw ones otherwise -- what stage_bev_fit fits."""
+        lists when the engine clusters, else the stripped ones when it strips, the raw ones otherwise -- what stage_bev_fit fits."""
         b, v = self.b, self.vertical
-        xyz, off = (b.cl_xyz, b.cl_off) if self.cluster is not None else (b.hit_xyz, b.hit_off)
+        xyz, off = self.read_lists()
         check(self.lib.cm3d_box_vertical(_ptr(xyz), _ptr(off), b.M, b.idx_cap, _ptr(b.box), _ptr(b.flags), _ptr(self.prior_wlh),
                                          len(self.classes.names), v.q_bot, v.q_top, v.min_points, v.lo, v.hi, _ptr(b.vert_z), _ptr(b.vert_h),
                                          _ptr(b.vert_src), _ptr(b.vert_status), _ptr(b.vert_entry_z), st), "cm3d_box_vertical")
@@ -1150,11 +1217,11 @@ class LiftEngine:
         stage_events: optional list; gets five timing events appended -- before the point/mask stages, behind the compaction,
         the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them.
         Each opt-in stage the engine has appends two more behind those, in this order: around the filter launch (the "drivable"
-        bucket), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
+        bucket), around the ground strip's launches (the "strip" bucket; behind the second of the five, in front of the clustering's), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
         the yaw fit's two launches (the "yawfit" bucket; behind the fifth event), around the placement's launch (the "place" bucket;
         behind the yaw fit's boxes), around the vertical stage's call (the "vertical" bucket; behind the pass), around the ground stage's
         call (the "ground" bucket; behind the vertical stage's).  One library call enqueues
-        the pass, opt-in stages included (cm3d_lift_pass_opt, or cm3d_lift_pass_placed with a placement; include/cm3d_hip.h states the
+        the pass, opt-in stages included (cm3d_lift_pass_opt, cm3d_lift_pass_placed with a placement, or cm3d_lift_pass_stripped with a ground strip; include/cm3d_hip.h states the
         order); no allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
@@ -1166,7 +1233,10 @@ class LiftEngine:
             stage_events.extend(marks + [ev for pair in omarks.values() for ev in pair])
         st = torch.cuda.current_stream(self.dev).cuda_stream
         desc = self.refresh_pass_descriptor(dense, project_events, marks, omarks)
-        if self.place is None:
+        if self.strip is not None:                       # the same pass, the strip in front of the clustering (and the placement as below)
+            check(self.lib.cm3d_lift_pass_stripped(desc, self.b.opts_ref, ctypes.byref(self.b.place_desc) if self.place is not None else None,
+                                                   ctypes.byref(self.b.strip_desc), st), "cm3d_lift_pass_stripped")
+        elif self.place is None:
             check(self.lib.cm3d_lift_pass_opt(desc, self.b.opts_ref, st), "cm3d_lift_pass_opt")
         else:                                            # the same pass, the placement in front of its rotated NMS
             check(self.lib.cm3d_lift_pass_placed(desc, self.b.opts_ref, ctypes.byref(self.b.place_desc), st), "cm3d_lift_pass_placed")
@@ -1294,7 +1364,8 @@ class LiftEngine:
 
     def download(self, full=True):
         """Synchronises, checks the status word and returns numpy results.  full=False: only the per-mask results
-        (boxes, flags, medoids, lane matches, list offsets) -- a few hundred KB.  full=True adds the index lists
+        (boxes, flags, medoids, lane matches, list offsets) -- a few hundred KB.  `medoid_pos` is a position in the lists the medoid saw:
+        the clustered ones (`cl_off`) when the engine clusters, else the stripped ones (`gs_off`) when it strips, else the raw ones.  full=True adds the index lists
         (`hit_idx`, the reference's track_points), the coordinates of the listed points (`hit_xyz`), `pt_off` in the
         reference's form (the aggregated cloud without the ego-box rows, :445-465) and -- when the engine keeps the cloud
         (keep_cloud) -- `points` in that form too; on the device the cloud keeps the dropped rows as NaN placeholders."""
@@ -1308,6 +1379,8 @@ class LiftEngine:
                 out.update(obb_yaw=b.obb_yaw.cpu().numpy(), obb_status=b.obb_status.cpu().numpy())
             if self.cluster is not None:
                 out.update(cl_off=b.cl_off.cpu().numpy(), cl_status=b.cl_status.cpu().numpy())
+            if self.strip is not None:
+                out.update(gs_off=b.gs_off.cpu().numpy(), gs_status=b.gs_status.cpu().numpy(), gs_dropped=b.gs_dropped.cpu().numpy())
             if self.yaw is not None:
                 out.update(self._yaw_results())
             if self.velocity is not None:
@@ -1345,6 +1418,12 @@ class LiftEngine:
             n_cl = int(cl_off[-1])
             out.update(cl_off=cl_off, cl_status=b.cl_status.cpu().numpy(), cl_idx=b.cl_idx[:n_cl].cpu().numpy(),
                        cl_xyz=b.cl_xyz[:n_cl].cpu().numpy())
+        if self.strip is not None:
+            gs_off = b.gs_off.cpu().numpy()
+            n_gs = int(gs_off[-1])
+            out.update(gs_off=gs_off, gs_status=b.gs_status.cpu().numpy(), gs_dropped=b.gs_dropped.cpu().numpy(),
+                       gs_idx=b.gs_idx[:n_gs].cpu().numpy(), gs_xyz=b.gs_xyz[:n_gs].cpu().numpy(), grid_z=b.grid_z.cpu().numpy(),
+                       grid_n=b.grid_n.cpu().numpy())
         if self.yaw is not None:
             out.update(self._yaw_results())
         if self.velocity is not None:

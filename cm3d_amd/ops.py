@@ -15,6 +15,8 @@ src/nuscenes/2d_to_3d.py so that parity tests read like calls into the reference
     bev_fit(xyz, off, ...) / yaw_select(...)             the opt-in yaw fit of several lists and the choice of each mask's yaw (bevfit.*_host)
     box_velocity(box, flags, mask_off, ...)              the opt-in association of consecutive frames' boxes (velocity.track_velocity_host)
     box_tracks(box, flags, mask_frame, next_match, ...)  the opt-in tracks behind it: ids, length filter, scores, smoothed velocity (tracks.box_tracks_host)
+    ground_grid(origin, points=... | raw=...)            the opt-in per-frame ground grid from a cloud or from raw rows (groundstrip.ground_grid_host)
+    ground_strip(hit_xyz, hit_off, mask_frame, ...)      the opt-in strip of ground points from in-mask lists (groundstrip.ground_strip_host)
 
 They are conveniences for tests and small jobs; the batched path is lifting.LiftEngine.
 """
@@ -670,6 +672,80 @@ def box_ground(box, flags, prior_wlh, mask_off, points=None, pt_off=None, raw=No
     return dict(ground_z=gz.cpu().numpy()[:M], ground_n=gn.cpu().numpy()[:M], ground_h=gh.cpu().numpy()[:M],
                 ground_src=src.cpu().numpy()[:M], ground_status=status.cpu().numpy()[:M], ground_zref=gr.cpu().numpy()[:M],
                 box=d_box.cpu().numpy()[:M])
+
+
+# ----------------------------------------------------------------------------- ground strip (opt-in)
+def ground_grid(origin, points=None, pt_off=None, raw=None, raw_stride=4, sweep_xf=None, sweep_row_off=None, frame_sweep_off=None, halfw=0.0,
+                cell=2.0, down=4.0, up=4.0, quantile=0.1, min_points=8):
+    """The per-frame ground grid on arrays (cm3d_ground_grid; groundstrip.ground_grid_host states it).  origin (F, 3) float64; the cloud
+    is either points (n, 4) float32 with pt_off (F + 1,), or the raw rows as box_ground takes them.  Returns (grid_z (F, 4096) float64,
+    grid_n (F, 4096) int32).  The defaults are untuned."""
+    from .groundstrip import N_CELLS
+    L = _lib.lib()
+    org = np.ascontiguousarray(origin, np.float64).reshape(-1, 3)
+    F = org.shape[0]
+    null = lambda a: None if a is None else a.data_ptr()
+    d_pts = d_poff = d_raw = d_xf = d_roff = d_soff = None
+    n_sweeps = 0
+    if points is not None:
+        p = np.asarray(points, np.float32).reshape(-1, 4)
+        n_rows = p.shape[0]
+        d_pts, d_poff = _t(p if n_rows else np.zeros((1, 4), np.float32)), _t(np.asarray(pt_off, np.int32).reshape(F + 1))
+    else:
+        sweep_row_off = np.ascontiguousarray(sweep_row_off, np.int32).reshape(-1)
+        n_sweeps, n_rows = sweep_row_off.size - 1, int(sweep_row_off[-1])
+        r = np.asarray(raw, np.float32).reshape(-1)
+        need = (n_rows + 3) // 4 * 12 if raw_stride == _lib.RAW_QUADS else n_rows * int(raw_stride)
+        if r.size < need:
+            raise ValueError(f"raw: {r.size} floats for {n_rows} rows")
+        d_raw, d_xf = _t(r if r.size else np.zeros(12, np.float32)), _t(np.asarray(sweep_xf, np.float32).reshape(max(n_sweeps, 0), 24))
+        d_roff, d_soff = _t(sweep_row_off), _t(np.asarray(frame_sweep_off, np.int32).reshape(F + 1))
+    gz, gn = _e(max(F, 1), N_CELLS, dtype=torch.float64), _e(max(F, 1), N_CELLS)
+    check(L.cm3d_ground_grid(null(d_pts), null(d_poff), null(d_raw), int(raw_stride), null(d_xf), null(d_roff), null(d_soff), n_sweeps,
+                             float(halfw), n_rows, _t(org if F else np.zeros((1, 3))).data_ptr(), F, float(cell), float(down), float(up),
+                             float(quantile), int(min_points), gz.data_ptr(), gn.data_ptr(), _st()), "cm3d_ground_grid")
+    return gz.cpu().numpy()[:F], gn.cpu().numpy()[:F]
+
+
+def ground_strip(hit_xyz, hit_off, mask_frame, origin, grid_z, hit_idx=None, cell=2.0, margin=0.3, min_keep=5, idx_cap=None):
+    """The strip of the in-mask lists on arrays (cm3d_ground_strip; groundstrip.ground_strip_host states it).  hit_xyz (n, 3 or 4)
+    float32, hit_off (M + 1,), mask_frame (M,), origin (F, 3), grid_z (F, 4096) as ground_grid returns it; hit_idx (n,) or None: the call
+    without hit_idx / gs_idx.  idx_cap: the capacity the call is told (default: the number of positions).  Returns a dict of numpy
+    arrays: gs_off, gs_tile_off, gs_status, gs_dropped, gs_xyz (gs_off[-1], 4), gs_idx (or None).  The defaults are untuned."""
+    from .groundstrip import N_CELLS
+    L = _lib.lib()
+    p = np.asarray(hit_xyz, np.float32)
+    p = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 4)
+    tot = p.shape[0]
+    cap = max(tot, 1) if idx_cap is None else int(idx_cap)
+    P4 = np.zeros((max(tot, cap, 1), 4), np.float32)
+    P4[:tot, :min(p.shape[1], 4)] = p[:, :4]
+    hit_off = np.ascontiguousarray(hit_off, np.int32).reshape(-1)
+    M = hit_off.size - 1
+    org, gz = np.ascontiguousarray(origin, np.float64).reshape(-1, 3), np.ascontiguousarray(grid_z, np.float64).reshape(-1, N_CELLS)
+    F = org.shape[0]
+    idx = None
+    if hit_idx is not None:
+        idx = np.zeros(P4.shape[0], np.int32)
+        idx[:tot] = np.asarray(hit_idx, np.int32)
+    n = max(M, 1)
+    d_xyz, d_idx, d_off = _t(P4), None if idx is None else _t(idx), _t(hit_off)
+    d_mf = _t(np.asarray(mask_frame, np.int32).reshape(M) if M else np.zeros(1, np.int32))
+    d_org, d_gz = _t(org if F else np.zeros((1, 3))), _t(gz if F else np.zeros((1, N_CELLS)))
+    gs_off, gs_tile, gs_st, gs_dr = _e(n + 1), _e(n + 1), _e(n), _e(n)
+    gs_idx, gs_xyz = (None if idx is None else _e(P4.shape[0])), _e(P4.shape[0], 4, dtype=torch.float32)
+    ws = _ws(L.cm3d_ground_strip_workspace_bytes(M, cap))
+    check(L.cm3d_ground_strip(d_xyz.data_ptr(), None if d_idx is None else d_idx.data_ptr(), d_off.data_ptr(), d_mf.data_ptr(), M, cap,
+                              d_org.data_ptr(), d_gz.data_ptr(), F, float(cell), float(margin), int(min_keep), gs_off.data_ptr(),
+                              gs_tile.data_ptr(), None if gs_idx is None else gs_idx.data_ptr(), gs_xyz.data_ptr(), gs_st.data_ptr(),
+                              gs_dr.data_ptr(), ws.data_ptr(), ws.numel(), _st()), "cm3d_ground_strip")
+    if M == 0:
+        return dict(gs_off=np.zeros(1, np.int32), gs_tile_off=np.zeros(1, np.int32), gs_status=np.zeros(0, np.int32),
+                    gs_dropped=np.zeros(0, np.int32), gs_xyz=np.zeros((0, 4), np.float32), gs_idx=None if idx is None else np.zeros(0, np.int32))
+    off = gs_off.cpu().numpy()
+    k = int(off[-1])
+    return dict(gs_off=off, gs_tile_off=gs_tile.cpu().numpy(), gs_status=gs_st.cpu().numpy(), gs_dropped=gs_dr.cpu().numpy(),
+                gs_xyz=gs_xyz.cpu().numpy()[:k], gs_idx=None if gs_idx is None else gs_idx.cpu().numpy()[:k])
 
 
 # ----------------------------------------------------------------------------- f4: SAM3D fusion matching

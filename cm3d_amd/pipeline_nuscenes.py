@@ -28,6 +28,7 @@ from . import tracks as trmod
 from . import boxsize as szmod
 from . import boxvertical as vtmod
 from . import boxground as grmod
+from . import groundstrip as gsmod
 
 # module constants of the reference (:55-59)
 VER_NAME = "v1.0-trainval"
@@ -228,7 +229,7 @@ def _token_batches(batches, index, host_s):
 
 
 def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                  velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None):
+                  velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None, strip=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
@@ -250,7 +251,10 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
     records' (k, 3) sizes then carry its heights in column 2 (lifting.kept_box_sizes) and are shipped exactly as the size stage's are,
     with or without a size stage.  ground: the opt-in ground stage (boxground.BoxGround; with any option or none), one call behind the
     vertical stage's; its two events come behind that stage's, and the time between them goes into a "ground" bucket.  The size rows'
-    column 2 then carries its heights (`ground_h`), shipped the same way."""
+    column 2 then carries its heights (`ground_h`), shipped the same way.  strip: the opt-in ground strip (groundstrip.GroundStrip; with
+    any option or none), inside the pass between the compaction and the clustering; its two events come behind the filter's and in front
+    of the clustering's, inside the "medoid" span, and the time between them goes into a "strip" bucket instead.  The records are what
+    they were in form: nothing else changes here."""
     sized = size is not None or vertical is not None or ground is not None      # the records travel with (k, 3) size rows
     kw = {} if yaw is None else {"yaw": yaw}
     if place is not None:
@@ -265,11 +269,14 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
         kw["vertical"] = vertical
     if ground is not None:
         kw["ground"] = ground
+    if strip is not None:
+        kw["strip"] = strip
     vels, sizes = [], []
     pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms, **kw)
     n_f, n_c, n_y = (2 if filters is not None and filters.active else 0), (2 if cluster is not None else 0), (2 if yaw is not None else 0)
     n_p, n_v, n_g = (2 if place is not None else 0), (2 if vertical is not None else 0), (2 if ground is not None else 0)
-    n_evs = 5 + n_f + n_c + n_y + n_p + n_v + n_g
+    n_s = 2 if strip is not None else 0
+    n_evs = 5 + n_f + n_s + n_c + n_y + n_p + n_v + n_g
     records, pending, segments = [], [], []                            # pending: (slot, frame ids, stage events) in flight, oldest first
 
     def spent(key, since):
@@ -300,14 +307,18 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
                     spans.append(("drivable", 5, 6))
                 for key, a, b in spans:
                     timer[key] = timer.get(key, 0.0) + evs[a].elapsed_time(evs[b]) * 1e-3
-                if cluster is not None:                                # the two events behind the filter's, inside the "medoid" span
+                if strip is not None:                                  # the two events behind the filter's, inside the "medoid" span
                     dt = evs[5 + n_f].elapsed_time(evs[6 + n_f]) * 1e-3
+                    timer["strip"] = timer.get("strip", 0.0) + dt
+                    timer["medoid"] -= dt
+                if cluster is not None:                                # the two events behind the strip's, inside the "medoid" span too
+                    dt = evs[5 + n_f + n_s].elapsed_time(evs[6 + n_f + n_s]) * 1e-3
                     timer["cluster"] = timer.get("cluster", 0.0) + dt
                     timer["medoid"] -= dt
                 if yaw is not None:                                    # behind the pass
-                    timer["yawfit"] = timer.get("yawfit", 0.0) + evs[5 + n_f + n_c].elapsed_time(evs[6 + n_f + n_c]) * 1e-3
+                    timer["yawfit"] = timer.get("yawfit", 0.0) + evs[5 + n_f + n_s + n_c].elapsed_time(evs[6 + n_f + n_s + n_c]) * 1e-3
                 if place is not None:                                  # behind the yaw fit's boxes
-                    at = 5 + n_f + n_c + n_y
+                    at = 5 + n_f + n_s + n_c + n_y
                     timer["place"] = timer.get("place", 0.0) + evs[at].elapsed_time(evs[at + 1]) * 1e-3
                 if vertical is not None:                               # behind the pass
                     timer["vertical"] = timer.get("vertical", 0.0) + evs[-2 - n_g].elapsed_time(evs[-1 - n_g]) * 1e-3
@@ -347,7 +358,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                 scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None,
                 cluster=None, nms=None, yaw=None, velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None,
-                vertical=None, ground=None):
+                vertical=None, ground=None, strip=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -381,7 +392,8 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
                 pool.join()
     with contextlib.closing(prepared()) as batches:
         return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms, yaw=yaw, velocity=velocity,
-                             vel_out=vel_out, tracks=tracks, place=place, size=size, size_out=size_out, vertical=vertical, ground=ground)
+                             vel_out=vel_out, tracks=tracks, place=place, size=size, size_out=size_out, vertical=vertical, ground=ground,
+                             strip=strip)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -459,7 +471,7 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
 
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                        scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                       velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None):
+                       velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None, strip=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -503,7 +515,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
         return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw, velocity, vel_out, tracks, place,
-                             size, size_out, vertical, ground)
+                             size, size_out, vertical, ground, strip)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -543,6 +555,7 @@ def main(argv=None):
     szmod.add_arguments(ap)
     vtmod.add_arguments(ap)
     grmod.add_arguments(ap)
+    gsmod.add_arguments(ap)
     args = ap.parse_args(argv)
     cluster = clmod.from_namespace(args)
     nms = nmsmod.from_args(args)
@@ -553,6 +566,7 @@ def main(argv=None):
     size = szmod.from_args(args, ap)                # (--size track without --yaw fit --place fit --velocity track, or a --size-* flag alone: the same)
     vertical = vtmod.from_args(args, ap)            # (a --vertical-* flag without --vertical fit: the same)
     ground = grmod.from_args(args, ap)              # (a --ground-* flag without --ground fit: the same)
+    strip = gsmod.from_namespace(args, ap)          # (a --ground-strip-* flag without --ground-strip grid: the same)
     sized = size is not None or vertical is not None or ground is not None
     size_mine = []                                 # with --size track, --vertical fit or --ground fit: the sizes of this rank's records, one device tensor
     vel_mine = []                                  # with --velocity track: the velocities of this rank's records, one device tensor
@@ -631,7 +645,7 @@ def main(argv=None):
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
                                   on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
                                   velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine,
-                                  vertical=vertical, ground=ground)
+                                  vertical=vertical, ground=ground, strip=strip)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
@@ -640,7 +654,8 @@ def main(argv=None):
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
                            token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
-                           velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine, vertical=vertical, ground=ground)
+                           velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine, vertical=vertical, ground=ground,
+                           strip=strip)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.

@@ -31,6 +31,7 @@ from . import bevfit
 from . import boxplace
 from . import boxvertical as vtmod
 from . import boxground as grmod
+from . import groundstrip as gsmod
 from . import dist as cdist
 from . import lifting
 from . import waymo as wm
@@ -145,10 +146,12 @@ def main(argv=None):
     boxplace.add_arguments(ap)
     vtmod.add_arguments(ap)
     grmod.add_arguments(ap)
+    gsmod.add_arguments(ap)
     args = ap.parse_args(argv)
     place = boxplace.from_namespace(args, ap)       # (--place fit without --yaw fit: an error of the command line)
     vertical = vtmod.from_args(args, ap)            # (a --vertical-* flag without --vertical fit: the same)
     ground = grmod.from_args(args, ap)              # (a --ground-* flag without --ground fit: the same)
+    strip = gsmod.from_namespace(args, ap)          # (a --ground-strip-* flag without --ground-strip grid: the same)
     filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
     rank, world, local_rank = cdist.init_from_env()
@@ -161,7 +164,7 @@ def main(argv=None):
     classes = lifting.ClassTable.waymo(pri)
     eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args),
                              nms=nmsmod.from_args(args), yaw=bevfit.from_namespace(args), place=place,
-                             vertical=vertical, ground=ground)
+                             vertical=vertical, ground=ground, strip=strip)
     lo, hi = cdist.shard_range(len(scenes), rank, world)
     mine, meta, heights = [], {}, []
     for si in range(lo, hi):

@@ -1277,6 +1277,107 @@ int cm3d_box_ground(const float *points, const int32_t *pt_off, const float *raw
                     double lo, double hi, double *ground_z, int32_t *ground_n, double *ground_h, int32_t *ground_src,
                     int32_t *ground_status, double *ground_zref, cm3d_stream_t stream);
 
+/* ---- opt-in: ground points stripped from the in-mask lists; a per-frame ground grid (csrc/groundstrip.hip) -----
+ * Added within ABI v5: new symbols only, so CM3D_ABI_VERSION stays.  A mask drawn around an object covers a strip of road at its foot;
+ * the erosion does not remove it and the depth clustering cannot (the road beside the wheels lies at the object's own range).  Here a
+ * frame's own sweep gives a grid of ground heights around the frame's origin, and every in-mask list loses the points that lie below
+ * its cell's ground plus a margin, between the compaction and the depth clustering: everything behind reads the stripped lists.  The
+ * reference has nothing of the kind.  The defaults C = 2.0 m, DOWN, UP = 4.0, 4.0 m, Q = 0.1, N = 8, MARGIN = 0.3 m, MIN_KEEP = 5 are
+ * UNTUNED, all seven, and what the stage does to label quality has not been measured (it cannot be on synthetic scenes).  Host
+ * statements to the bit: cm3d_amd.groundstrip.ground_grid_host and ground_strip_host.  F = n_frames, M = n_masks.  All arithmetic of
+ * the rule is float64, every operation rounded on its own, no fma; counts are integers, so nothing depends on the order in which
+ * points arrive.
+ *
+ *  Grid of frame f.  o = origin[f] (double[F][3]; the engine hands ego_xyz, as the clustering does: zeros on Waymo).  The points are
+ *              the rows of the frame's sweeps exactly as cm3d_box_ground defines them (above, "Points."): the very float32 of the
+ *              cloud, given as the cloud or as raw rows, without the rows the sweep preparation drops and without rows that have a
+ *              non-finite coordinate; every offset clamped as there.  The grid has CM3D_GROUND_GRID_CELLS = 64 cells of side C per
+ *              side, centred on o, and every cell a window of CM3D_GROUND_GRID_BINS = 64 bins from oz - DOWN to oz + UP.
+ *              For a point p (float32 px, py, pz):  u = ((double)px - ox) / C, iu = floor(u), and iv from py, oy alike.  The point is
+ *              inside the grid iff -32 <= iu < 32 && -32 <= iv < 32; its cell is (iv + 32) * 64 + (iu + 32).  With dz = (DOWN + UP) / 64.0
+ *              and t = ((double)pz - (oz - DOWN)) / dz, the point is a member of its cell iff 0 <= t < 64; its bin is (int)t.
+ *              grid_n int32[F][64*64] = the cell's member count n.  n >= N: k = (int)(Q * (double)(n - 1)), b* = the smallest bin
+ *              whose cumulative count exceeds k (cm3d_box_ground's selection), grid_z double[F][64*64] = (oz - DOWN) + ((double)b* + 0.5) * dz.
+ *              n < N: grid_z = NaN, "no estimate".  A frame with a non-finite origin has no estimate in any cell and every grid_n 0.
+ *  Strip of mask m.  f = mask_frame[m]; the list is positions hit_off[m] .. hit_off[m+1] of hit_xyz (and hit_idx), the offsets clamped
+ *              as cm3d_depth_cluster clamps them.  A list point is GROUND iff it lies inside the grid of frame f (iu, iv as above, from
+ *              origin[f] and C), its cell has an estimate g, its z is finite and (double)z < g + MARGIN (strict).  A point outside the
+ *              grid, in a cell without an estimate, or with a non-finite coordinate is never ground; a frame number outside [0, F) is
+ *              a frame without estimates.  kept = the number of non-ground points, dropped = the number of ground points:
+ *                gs_status 2: empty list, empty result, gs_dropped 0
+ *                gs_status 1: kept < MIN_KEEP: the list is kept whole, gs_dropped 0
+ *                gs_status 0: the non-ground points in the list's own order, gs_dropped = dropped (which may be 0)
+ *              A non-empty list never becomes empty, so the set of masks with a box cannot change.
+ *  gs_off, gs_tile_off int32[M+1], gs_idx int32[idx_cap] (NULL exactly when hit_idx is), gs_xyz float[idx_cap][4], gs_status int32[M]:
+ *              the formats of cm3d_depth_cluster's cl_off, cl_tile_off, cl_idx, cl_xyz, cl_status;  gs_dropped int32[M].
+ *  workspace   cm3d_ground_strip_workspace_bytes(M, idx_cap) = 4 M + idx_cap bytes, 4-byte aligned (the kept counts; one keep byte per
+ *              position).
+ *
+ *  cm3d_ground_strip_check: CM3D_OK iff C is finite and > 0, DOWN and UP finite and > 0, 0 <= Q <= 1, N >= 1, MARGIN finite,
+ *  MIN_KEEP >= 1; anything else, NaN included, is CM3D_ERR_ARG.  Both calls below apply it to the parameters they take, before any
+ *  launch; CM3D_ERR_ARG before any launch as well: a negative count, idx_cap <= 0, neither a cloud nor raw rows (as cm3d_box_ground),
+ *  points, hit_xyz or gs_xyz not 16-byte aligned, hit_idx and gs_idx not NULL together, and with F > 0 (grid) or M > 0 (strip) a NULL
+ *  array (origin and grid_z may be NULL for the strip when F == 0); a workspace too small is CM3D_ERR_WORKSPACE.  cm3d_ground_grid with
+ *  F == 0 and cm3d_ground_strip with M == 0: CM3D_OK, nothing launched, nothing written.
+ *  cm3d_ground_grid is one launch, k_ground_grid: one workgroup of sixteen waves per (frame, tile of 16 x 16 cells); the tile's
+ *  256 x 64 int32 counters are 64 KiB of LDS.  The workgroup streams the whole frame's rows (so a frame's rows are read 16 times, from
+ *  L2 after the first), a point outside the tile's rectangle costs two comparisons, a member does one integer LDS add; behind a barrier one
+ *  wave per cell scans the 64 counters with a wave prefix sum and the lane that owns rank k writes the cell.  The tile seams are cells
+ *  15/16, 31/32 and 47/48 in x and in y.  cm3d_ground_strip is three launches: k_ground_strip, one workgroup per mask (keep bytes, the
+ *  count, the MIN_KEEP rule), then the scan and the stable compaction cm3d_depth_cluster uses (csrc/list_compact.h).  No position
+ *  >= idx_cap is read or written whatever hit_off holds.  Plain stores, no global atomic, no allocation, no read-back: every run gives
+ *  the same bytes, and both calls can be captured in a graph. */
+#define CM3D_GROUND_GRID_CELLS 64
+#define CM3D_GROUND_GRID_BINS 64
+int cm3d_ground_strip_check(double cell, double down, double up, double quantile, int32_t min_points, double margin, int32_t min_keep);
+int cm3d_ground_grid(const float *points, const int32_t *pt_off, const float *raw, int32_t raw_stride, const float *sweep_xf,
+                     const int32_t *sweep_row_off, const int32_t *frame_sweep_off, int32_t n_sweeps, float halfw, int32_t n_rows,
+                     const double *origin, int32_t n_frames, double cell, double down, double up, double quantile, int32_t min_points,
+                     double *grid_z, int32_t *grid_n, cm3d_stream_t stream);
+int64_t cm3d_ground_strip_workspace_bytes(int32_t n_masks, int32_t idx_cap);
+int cm3d_ground_strip(const float *hit_xyz, const int32_t *hit_idx, const int32_t *hit_off, const int32_t *mask_frame, int32_t n_masks,
+                      int32_t idx_cap, const double *origin, const double *grid_z, int32_t n_frames, double cell, double margin,
+                      int32_t min_keep, int32_t *gs_off, int32_t *gs_tile_off, int32_t *gs_idx, float *gs_xyz, int32_t *gs_status,
+                      int32_t *gs_dropped, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
+
+/* What the stripped pass needs beyond cm3d_lift_pass_desc.  `size` is sizeof(cm3d_ground_strip_desc) (another value: CM3D_ERR_ARG);
+ * the other fields as in cm3d_ground_grid and cm3d_ground_strip (origin: double[desc->n_frames][3]). */
+typedef struct cm3d_ground_strip_desc {
+    int64_t size;
+    const double *origin;
+    double *grid_z; int32_t *grid_n;
+    int32_t *gs_off; int32_t *gs_tile_off; int32_t *gs_idx; float *gs_xyz; int32_t *gs_status; int32_t *gs_dropped;
+    void *ws; int64_t ws_bytes;
+    void *ev[2];                 /* optional hipEvent_t, recorded in front of cm3d_ground_grid and behind cm3d_ground_strip */
+    double cell, down, up, quantile, margin;
+    int32_t min_points, min_keep;
+} cm3d_ground_strip_desc;
+
+/* The composed pass with the ground strip (host code, csrc/pass_strip.cpp; behind the strip it enters csrc/pass_options.cpp, which
+ * states the order of every composed pass, on the stripped lists.  No member of cm3d_lift_pass_options: the strip stands in front of
+ * every stage the options name, and pass_options.cpp does not know it).  Enqueues on `stream`, stopping at
+ * and returning the first error; no descriptor of the caller's is written.  opt may be NULL (no other stage), place may be NULL;
+ * a NULL strip is CM3D_ERR_ARG: it does not fall back to the plain pass.
+ *
+ *   every descriptor is checked first, CM3D_ERR_ARG and NO call at all: desc, opt and its members as in cm3d_lift_pass_opt; place as
+ *   in cm3d_lift_pass_placed (it needs opt->yaw); strip's size, its arrays (gs_idx when desc has hit_idx), its workspace pointer and
+ *   cm3d_ground_strip_check of its parameters; yaw's hit_xyz, hit_off, medoid_pos each NULL or what is derived below
+ *   cm3d_lift_pass_head(desc)
+ *   record strip->ev[0]; cm3d_ground_grid (desc's sweep rows: the cloud where desc has points, else the raw rows; origin -> grid_z, grid_n);
+ *   cm3d_ground_strip (desc's lists -> the gs_* arrays); record strip->ev[1]
+ *   cluster ?  record cluster->ev[0]; cm3d_depth_cluster (the gs_* lists -> the cl_* arrays); record cluster->ev[1]
+ *   cm3d_lift_pass_tail(desc')            desc' = desc with hit_off, tile_off, hit_idx, hit_xyz = the cl_* arrays, or the gs_* arrays
+ *                                         without a cluster; tile_work = NULL
+ *   filter  ?  as in cm3d_lift_pass_opt
+ *   yaw     ?  cm3d_yaw_fit_boxes' sequence          lists = cluster ? cl_xyz, cl_off : gs_xyz, gs_off
+ *   place   ?  record place->ev[0]; cm3d_box_place; record place->ev[1]      as in cm3d_lift_pass_placed
+ *   nms     ?  cm3d_box_rotated_nms                  as in cm3d_lift_pass_opt
+ *   medoid_pos is then a position in the lists the medoid saw (the cl_* lists, or the gs_* lists).  Behind the pass the caller's own
+ *   calls as before; cm3d_box_vertical reads the lists the yaw fit reads.  cm3d_box_ground stays what it is: it streams the sweep and
+ *   does not read the grid. */
+int cm3d_lift_pass_stripped(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, const cm3d_box_place_desc *place,
+                            const cm3d_ground_strip_desc *strip, cm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
