@@ -95,6 +95,8 @@ SIGNATURES = {
     "cm3d_lift_pass": (_i32, [_p, _p]),
     "cm3d_pipe_exec_streams_for": (_i32, [_i32, _i32]),
     "cm3d_pipe_create": (_p, [_i32, _i32, _p]),
+    "cm3d_pipe_create2": (_p, [_i32, _i32, _p, _i32]),
+    "cm3d_pipe_null_exec": (_i32, [_p]),
     "cm3d_pipe_destroy": (None, [_p]),
     "cm3d_pipe_exec_streams": (_i32, [_p]),
     "cm3d_pipe_submit": (_i32, [_p, _i32, _p]),

@@ -35,6 +35,27 @@ inline int pipe_exec_streams(int depth, int hw_queues)
     return n < 1 ? 1 : n;
 }
 
+// The executors of a pipeline: streams that execute passes at the same time, the last of which may be the legacy null stream.
+struct PipeExecPlan {
+    int n_exec;
+    bool null_last;   // executor n_exec - 1 is the null stream, not one of the pipeline's own
+};
+
+// The null stream has a queue to itself that carries nothing while passes run ("A fourth batch on the null stream's
+// queue").  Where pipe_exec_streams stops at the queues -- not at the batches in flight or at the four pipes -- that queue takes one
+// more executor; everywhere else the plan is pipe_exec_streams' own.
+inline PipeExecPlan pipe_exec_plan(int depth, int hw_queues)
+{
+    PipeExecPlan plan = {pipe_exec_streams(depth, hw_queues), false};
+    const int by_queues = hw_queues - 1 < 1 ? 1 : hw_queues - 1;
+    const int by_rest = depth < kPipeMaxExecStreams ? (depth < 1 ? 1 : depth) : kPipeMaxExecStreams;
+    if (by_queues < by_rest) {
+        plan.n_exec += 1;
+        plan.null_last = true;
+    }
+    return plan;
+}
+
 struct PipeTicket {
     int stream;   // index into the pipeline's streams
     bool wait;    // the slot's previous pass ran on another stream: order this one behind it first

@@ -117,20 +117,22 @@ namespace {
 
 struct Pipe {
     cm3d::PipeSched sched;
-    hipStream_t streams[cm3d::kPipeMaxDepth];
+    hipStream_t streams[cm3d::kPipeMaxDepth];  // the slots' own (uploads, captures, a pinned pipeline's passes)
+    hipStream_t exec[cm3d::kPipeMaxDepth];     // what a ticket's index means: streams[i], but handle 0 at null_exec
+    int null_exec;                             // the executor that is the legacy null stream, -1: none
     hipEvent_t done[cm3d::kPipeMaxDepth];      // behind the slot's last pass (timing disabled)
     bool recorded[cm3d::kPipeMaxDepth];
-    Pipe(int depth, int n_exec) : sched(depth, n_exec) {}
+    Pipe(int depth, int n_exec) : sched(depth, n_exec), null_exec(-1) {}
 };
 
-// the stream of the slot's next pass, ordered behind the slot's previous pass where that ran elsewhere; < 0: error
+// the executor of the slot's next pass, ordered behind the slot's previous pass where that ran elsewhere; < 0: error
 int pipe_take(Pipe *p, int32_t slot)
 {
     if (!p || slot < 0 || slot >= p->sched.depth) return CM3D_ERR_ARG;
     const cm3d::PipeTicket t = p->sched.next(slot);
     if (t.wait && p->recorded[slot] && hipEventQuery(p->done[slot]) != hipSuccess) {
         (void)hipGetLastError();                // hipErrorNotReady is the expected answer, not a sticky error
-        if (hipStreamWaitEvent(p->streams[t.stream], p->done[slot], 0) != hipSuccess) return CM3D_ERR_LAUNCH;
+        if (hipStreamWaitEvent(p->exec[t.stream], p->done[slot], 0) != hipSuccess) return CM3D_ERR_LAUNCH;
     }
     return t.stream;
 }
@@ -139,30 +141,54 @@ int pipe_mark(Pipe *p, int32_t slot)
 {
     const int s = p->sched.last[slot];
     if (s < 0) return CM3D_ERR_ARG;
-    if (hipEventRecord(p->done[slot], p->streams[s]) != hipSuccess) return CM3D_ERR_LAUNCH;
+    if (hipEventRecord(p->done[slot], p->exec[s]) != hipSuccess) return CM3D_ERR_LAUNCH;
     p->recorded[slot] = true;
     return CM3D_OK;
+}
+
+// CM3D_PIPE_NULL_EXEC=0 in the environment: the plan never takes the null stream
+bool null_exec_allowed()
+{
+    const char *v = std::getenv("CM3D_PIPE_NULL_EXEC");
+    return !(v && v[0] == '0' && v[1] == '\0');
 }
 
 }  // namespace
 
 extern "C" void *cm3d_pipe_create(int32_t depth, int32_t exec_streams, const cm3d_stream_t *streams)
 {
-    if (depth < 1 || depth > cm3d::kPipeMaxDepth || !streams) return nullptr;
-    const int n_exec = exec_streams > 0 ? (exec_streams < depth ? exec_streams : depth) : cm3d_pipe_exec_streams_for(depth, 0);
+    return cm3d_pipe_create2(depth, exec_streams, streams, 0);
+}
+
+extern "C" void *cm3d_pipe_create2(int32_t depth, int32_t exec_streams, const cm3d_stream_t *streams, int32_t null_exec)
+{
+    if (depth < 1 || depth > cm3d::kPipeMaxDepth || !streams || null_exec < -1 || null_exec > 1) return nullptr;
+    int n_exec = exec_streams > 0 ? (exec_streams < depth ? exec_streams : depth) : cm3d_pipe_exec_streams_for(depth, 0);
+    bool null_last = null_exec == 1;
+    // the plan's count where the caller names none: with null_exec = -1 its null executor too, with 1 a null executor in any case
+    if (exec_streams <= 0 && (null_exec == 1 || (null_exec < 0 && null_exec_allowed()))) {
+        const cm3d::PipeExecPlan plan = cm3d::pipe_exec_plan(depth, cm3d::pipe_hw_queues(std::getenv("GPU_MAX_HW_QUEUES")));
+        n_exec = plan.n_exec;
+        null_last = null_last || plan.null_last;
+    }
     Pipe *p = new (std::nothrow) Pipe(depth, n_exec);
     if (!p) return nullptr;
     for (int i = 0; i < cm3d::kPipeMaxDepth; ++i) {
         p->streams[i] = nullptr;
+        p->exec[i] = nullptr;
         p->done[i] = nullptr;
         p->recorded[i] = false;
     }
     for (int i = 0; i < depth; ++i) {
-        p->streams[i] = (hipStream_t)streams[i];
+        p->streams[i] = p->exec[i] = (hipStream_t)streams[i];
         if (hipEventCreateWithFlags(&p->done[i], hipEventDisableTiming) != hipSuccess) {
             cm3d_pipe_destroy(p);
             return nullptr;
         }
+    }
+    if (null_last && p->sched.n_exec >= 2) {
+        p->null_exec = p->sched.n_exec - 1;
+        p->exec[p->null_exec] = nullptr;        // the legacy null stream
     }
     return p;
 }
@@ -187,7 +213,7 @@ extern "C" int cm3d_pipe_submit(void *pipe, int32_t slot, const cm3d_lift_pass_d
     if (!desc) return CM3D_ERR_ARG;
     const int s = pipe_take(p, slot);
     if (s < 0) return s;
-    const int rc = cm3d_lift_pass(desc, (cm3d_stream_t)p->streams[s]);
+    const int rc = cm3d_lift_pass(desc, (cm3d_stream_t)p->exec[s]);
     // (the event also behind a pass that stopped half-way: what it did enqueue is what the slot's next pass must wait for)
     const int rm = pipe_mark(p, slot);
     if (rc != CM3D_OK) return rc;
@@ -213,10 +239,21 @@ extern "C" int cm3d_pipe_wait(void *pipe, int32_t slot)
 
 extern "C" int cm3d_pipe_pin(void *pipe)
 {
-    if (!pipe) return CM3D_ERR_ARG;
-    ((Pipe *)pipe)->sched.pin();
+    Pipe *p = (Pipe *)pipe;
+    if (!p) return CM3D_ERR_ARG;
+    p->sched.pin();
+    // a graph replays on the slot's own stream, so the null executor ends here: its index means streams[index] again, and the slot whose
+    // last pass it ran is ordered behind that pass now (the scheduler sees the same index and would not ask)
+    const int e = p->null_exec;
+    if (e >= 0) {
+        p->null_exec = -1;
+        p->exec[e] = p->streams[e];
+        if (p->sched.last[e] == e && p->recorded[e] && hipStreamWaitEvent(p->streams[e], p->done[e], 0) != hipSuccess) return CM3D_ERR_LAUNCH;
+    }
     return CM3D_OK;
 }
+
+extern "C" int cm3d_pipe_null_exec(const void *pipe) { return pipe ? ((const Pipe *)pipe)->null_exec : -1; }
 
 extern "C" int cm3d_pipe_last_stream(const void *pipe, int32_t slot)
 {

@@ -1473,7 +1473,12 @@ class LiftPipeline:
     variable read, never set; 4 queues when it is unset.  With that many streams or more than slots, slot s runs on `streams[s]` as
     it always did.  With fewer, pass number k runs on `streams[k % n]`, the slots take turns, and a slot's event keeps two passes of
     one slot in order when they land on different streams ("Passes rotate over as many streams as the process has queues
-    for").  `exec_streams` overrides the policy (tests).  Every pass is enqueued by one library call (cm3d_lift_pass[_opt]): `submit`, a
+    for").  Where that count stops at the queues, the plan adds one executor that is no stream of the pipeline's: the legacy null stream,
+    whose queue carries nothing while passes run (cm3d_pipe_create2).  An index from `last_stream` names an
+    executor; `exec_stream` maps it to a torch stream (the null executor: the device's default stream), and `streams` stay the slots' own
+    (uploads by hand, captures).  The null stream waits for every blocking stream of the process, so every stream here is non-blocking
+    (torch's are).  `null_exec` True / False asks for / forbids the null executor; CM3D_PIPE_NULL_EXEC=0 forbids it where nothing is asked.
+    `exec_streams` overrides the policy (tests; no null executor unless asked for).  Every pass is enqueued by one library call (cm3d_lift_pass[_opt]): `submit`, a
     `rerun` that has to start the build of the lane index and every pass of engines with opt-in stages go through `LiftEngine.run` on the
     chosen stream, every other `rerun` hands the slot's descriptor to cm3d_pipe_submit, which picks the stream itself.
 
@@ -1483,7 +1488,7 @@ class LiftPipeline:
     stream it was captured on, so slot s stays on `streams[s]`.  `submit` needs the slot collected (`collect`, `collect_records`,
     `check_status`) before it comes round again: the buffers it replaces may be in use on another stream until then."""
 
-    def __init__(self, device="cuda:0", depth=3, exec_streams=None, **engine_kw):
+    def __init__(self, device="cuda:0", depth=3, exec_streams=None, null_exec=None, **engine_kw):
         if depth < 1:
             raise ValueError("depth >= 1")
         self.dev = torch.device(device)
@@ -1498,10 +1503,11 @@ class LiftPipeline:
         L = self.lib = self.engines[0].lib
         handles = (ctypes.c_void_p * depth)(*[s.cuda_stream for s in self.streams])
         with torch.cuda.device(self.dev):
-            self._h = L.cm3d_pipe_create(depth, int(exec_streams or 0), handles)
+            self._h = L.cm3d_pipe_create2(depth, int(exec_streams or 0), handles, -1 if null_exec is None else int(bool(null_exec)))
         if not self._h:
-            raise Cm3dError("cm3d_pipe_create failed")
+            raise Cm3dError("cm3d_pipe_create2 failed")
         self.exec_streams = int(L.cm3d_pipe_exec_streams(self._h))
+        self._null = torch.cuda.default_stream(self.dev)     # what the null executor's index means (exec_stream)
         # With batches executing side by side the projection launch leaves part of the chip to the other batches' kernels (two workgroups
         # per CU instead of three, one with four streams executing: cm3d_project_workgroups_per_cu -- process-wide, results unaffected):
         # +1-2 % frames/s at three, +4 % at four, while one batch at a time runs fastest with the launch filling the chip.  It follows the
@@ -1522,8 +1528,18 @@ class LiftPipeline:
         return len(self.engines)
 
     def last_stream(self, slot):
-        """Index into `streams` of the stream the slot's last pass went to (-1 before the first)."""
+        """Executor index of the slot's last pass (-1 before the first): `exec_stream` gives the torch stream."""
         return int(self.lib.cm3d_pipe_last_stream(self._h, slot))
+
+    @property
+    def null_exec(self):
+        """The executor index that is the null stream, -1: none (cm3d_pipe_null_exec)."""
+        return int(self.lib.cm3d_pipe_null_exec(self._h))
+
+    def exec_stream(self, idx):
+        """The torch stream of an executor index (`last_stream`, cm3d_pipe_acquire / _submit): `streams[idx]`, but the device's default
+        stream for the null executor."""
+        return self._null if idx == self.null_exec else self.streams[idx]
 
     def _pin_if_captured(self):
         if not self._pinned and any(e.graph_captured for e in self.engines):
@@ -1540,7 +1556,7 @@ class LiftPipeline:
     def _wait(self, slot):
         check(self.lib.cm3d_pipe_wait(self._h, slot), "cm3d_pipe_wait")
         idx = self.last_stream(slot)
-        return self.streams[idx if idx >= 0 else slot]
+        return self.exec_stream(idx if idx >= 0 else slot)
 
     def submit(self, hb: HostBatch, masks="rle", stage_events=None):
         """Uploads `hb` into the next slot and issues one pass over it on the stream chosen for it (asynchronous).
@@ -1549,7 +1565,7 @@ class LiftPipeline:
         self._next = (slot + 1) % self.depth
         eng = self.engines[slot]
         self._pin_if_captured()
-        st = self.streams[self._acquire(slot)]
+        st = self.exec_stream(self._acquire(slot))
         try:
             with torch.cuda.stream(st):
                 eng.upload(hb)
@@ -1575,7 +1591,7 @@ class LiftPipeline:
             if rc < 0:
                 check(rc, "cm3d_pipe_submit")
         else:                                # the pass has to start the build of the lane index first, or has opt-in stages: LiftEngine.run's to do
-            st = self.streams[self._acquire(slot)]
+            st = self.exec_stream(self._acquire(slot))
             try:
                 with torch.cuda.stream(st):
                     eng.run(masks=mode, project_events=project_events)

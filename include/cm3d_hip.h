@@ -677,6 +677,19 @@ int cm3d_pipe_exec_streams_for(int32_t depth, int32_t hw_queues);
  * whose previous pass ran on another stream is ordered behind it by the slot's event (not waited for when it has already fired).
  * With n >= depth slot s always runs on streams[s] and no event is ever waited for.  NULL on a bad argument or a runtime error. */
 void *cm3d_pipe_create(int32_t depth, int32_t exec_streams, const cm3d_stream_t *streams);
+/* The same with a choice of executors (added within ABI v5: new symbols only).  An index the calls below return names an executor:
+ * executor i is streams[i], except the null executor, which is the legacy null stream (handle 0) -- its hardware queue carries
+ * nothing while passes run, so where the policy above stops at the queues (max(1, hw_queues - 1) < min(depth, 4)) the plan is one
+ * executor more, the null stream as the last (csrc/pipe_sched.h, pipe_exec_plan: (4, 4 queues) -> 4 with it, (4, 2) -> 2 with it,
+ * (3, 4), (4, 8), (1, any) -> the policy's own, without).  Every stream of `streams` and every other stream whose work must overlap
+ * the null stream's has to be non-blocking (hipStreamNonBlocking; torch's are).
+ *   null_exec -1: exec_streams <= 0 follows the plan (CM3D_PIPE_NULL_EXEC=0 in the environment: the policy above, no null executor);
+ *                 exec_streams > 0 is that many of the caller's streams, no null executor
+ *   null_exec  0: never: cm3d_pipe_create
+ *   null_exec  1: the last executor is the null stream whenever there are at least two (exec_streams <= 0: the plan's count) */
+void *cm3d_pipe_create2(int32_t depth, int32_t exec_streams, const cm3d_stream_t *streams, int32_t null_exec);
+/* The executor index that is the null stream, -1: none (also once cm3d_pipe_pin has ended it). */
+int cm3d_pipe_null_exec(const void *pipe);
 void cm3d_pipe_destroy(void *pipe);
 int cm3d_pipe_exec_streams(const void *pipe);
 /* Picks the stream of the slot's next pass, orders it behind the slot's previous pass, enqueues cm3d_lift_pass there and records the
@@ -688,7 +701,8 @@ int cm3d_pipe_acquire(void *pipe, int32_t slot);
 int cm3d_pipe_release(void *pipe, int32_t slot);
 /* Blocks the host until the slot's last pass (submit or acquire/release) has completed. */
 int cm3d_pipe_wait(void *pipe, int32_t slot);
-/* From now on slot s stays on streams[s] (something else, a captured graph, runs there).  Returns CM3D_OK. */
+/* From now on slot s stays on streams[s] (something else, a captured graph, runs there): a null executor ends here, and the slot whose
+ * last pass it ran is ordered behind that pass.  Returns CM3D_OK. */
 int cm3d_pipe_pin(void *pipe);
 /* Index of the stream of the slot's last pass, -1 before the first. */
 int cm3d_pipe_last_stream(const void *pipe, int32_t slot);
