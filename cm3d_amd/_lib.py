@@ -35,7 +35,8 @@ BEV_FIT_CHUNK = 512      # points of a list cm3d_bev_fit stages in LDS at a time
 VERT_LANE_MAX, VERT_LDS_KEYS = 64, 4096      # cm3d_box_vertical: the longest list of the lane route, the most keys staged in LDS
 GROUND_BINS = 128        # cm3d_box_ground: the bins of a mask's window
 GROUND_GRID_CELLS, GROUND_GRID_BINS = 64, 64      # cm3d_ground_grid: cells per side of a frame's grid, bins of a cell's window
-RAW_QUADS = 3           # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
+VP_MAX_K, VP_MAX_ROWS, VP_LDS_LIST = 1024, 4096, 256      # cm3d_virtual_points: most points per mask, most image rows, longest list staged in LDS
+RAW_QUADS = 3          # raw_stride value of the quad layout (include/cm3d_hip.h, cm3d_sweep_prep)
 
 _p, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 
@@ -141,6 +142,10 @@ SIGNATURES = {
     "cm3d_ground_strip": (_i32, [_p, _p, _p, _p, _i32, _i32, _p, _p, _i32, C.c_double, C.c_double, _i32, _p, _p, _p, _p, _p, _p, _p, _i64,
                                  _p]),
     "cm3d_lift_pass_stripped": (_i32, [_p, _p, _p, _p, _p]),
+    "cm3d_virtual_points_check": (_i32, [_i32, C.c_double]),
+    "cm3d_hit_project": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
+    "cm3d_virtual_points": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _i32, _i32, C.c_uint32, C.c_double, _i32,
+                                   _p, _p, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order

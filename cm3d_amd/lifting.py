@@ -31,6 +31,7 @@ from .velocity import Velocity, link_table  # noqa: F401  (LiftEngine(velocity=V
 from .tracks import Tracks  # noqa: F401  (LiftEngine(velocity=Velocity(...), tracks=Tracks(...)))
 from .boxsize import BoxSize  # noqa: F401  (LiftEngine(yaw=..., place=..., velocity=..., size=BoxSize(...)))
 from .boxvertical import BoxVertical, RESULTS as VERTICAL_RESULTS  # noqa: F401  (LiftEngine(vertical=BoxVertical(...)))
+from .virtualpoints import VirtualPoints, RESULTS as VIRTUAL_RESULTS  # noqa: F401  (LiftEngine(virtual=VirtualPoints(...)))
 from .boxground import BoxGround, RESULTS as GROUND_RESULTS  # noqa: F401  (LiftEngine(ground=BoxGround(...)))
 from .groundstrip import GroundStrip, N_CELLS as GRID_CELLS  # noqa: F401  (LiftEngine(strip=GroundStrip(...)))
 
@@ -152,6 +153,8 @@ class HostBatch:
     frame_next: Optional[np.ndarray] = None   # (F,) int32 batch index of the same scene's following keyframe, -1 for none; with
     frame_time: Optional[np.ndarray] = None   # (F,) float64 seconds since the batch's first frame (velocity.frame_times): only an engine
                                               # with Velocity(...) reads them; None: that option cannot be enabled for this batch
+    frame_seed: Optional[np.ndarray] = None   # (F,) uint32, one word per frame for the sampling of an engine with VirtualPoints(...): the
+                                              # entry points set the frame's ordinal in the whole job; None: arange(F)
     _lane_crc: Optional[tuple] = field(default=None, init=False, repr=False, compare=False)
 
     def lane_tables_key(self):
@@ -458,7 +461,7 @@ class LiftEngine:
                  cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None,
                  velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None, place: Optional[BoxPlace] = None,
                  size: Optional[BoxSize] = None, vertical: Optional[BoxVertical] = None, ground: Optional[BoxGround] = None,
-                 strip: Optional[GroundStrip] = None):
+                 strip: Optional[GroundStrip] = None, virtual: Optional[VirtualPoints] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -512,7 +515,14 @@ class LiftEngine:
         read the stripped lists: `medoid_pos` is a position in the lists the medoid saw -- the clustered ones (`cl_off`) when the engine
         clusters, else the stripped ones (`gs_off`) --, while `hit_off` / `hit_idx` / `hit_xyz` stay the raw lists.  download() adds
         `gs_off`, `gs_status`, `gs_dropped` (full=True: `gs_idx`, `gs_xyz`, `grid_z`, `grid_n`).  None: no buffer, no launch.  Its seven
-        parameters are untuned."""
+        parameters are untuned.
+        virtual: the virtual points (virtualpoints.VirtualPoints; any batch, KITTI's included, with any other option or none): one call of
+        its own behind everything that writes `flags` -- behind the track stage where that runs, else the rotated NMS, else the pass --
+        re-projects the lists the medoid saw through every mask's own camera (cm3d_hit_project) and lifts pixels sampled inside every
+        eroded mask with the depth of the nearest return in the image (cm3d_virtual_points).  It writes no box, flag or record: every
+        other downloaded array is what it is without it.  The sampling takes HostBatch.frame_seed (None: arange(F)).  download() adds
+        `vp_count`, `vp_status`, `vp_xyz`, `vp_pix`, `vp_src`, `vp_depth`, `vp_d2` (mask m owns rows [m K, m K + vp_count[m])) and, with
+        full=True, `hit_uvd`.  None: no buffer, no call.  Its parameters are untuned."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -533,6 +543,7 @@ class LiftEngine:
         self.vertical = vertical if vertical is not None and vertical.active else None
         self.ground = ground if ground is not None and ground.active else None
         self.strip = strip if strip is not None and strip.active else None
+        self.virtual = virtual if virtual is not None and virtual.active else None
         if self.strip is not None and self.obb:
             raise ValueError("strip=GroundStrip(...) is stated for nuScenes and Waymo lists (z up); KITTI's rect frame has y down: it cannot be "
                              "enabled with obb=True")
@@ -727,6 +738,17 @@ class LiftEngine:
             b.vert_z = e(M, 2, dtype=torch.float64); b.vert_h = e(M, dtype=torch.float64); b.vert_entry_z = e(M, dtype=torch.float64)
             b.vert_src = e(M); b.vert_status = e(M)
             b.prior_wlh = self.prior_wlh          # (kept_box_sizes: the length and width of a box without a size stage)
+        if self.virtual is not None:
+            if H > _lib.VP_MAX_ROWS:
+                raise ValueError(f"virtual=VirtualPoints(...): images of more than {_lib.VP_MAX_ROWS} rows ({H})")
+            K = self.virtual.per_mask
+            seeds = np.arange(F, dtype=np.uint32) if hb.frame_seed is None else np.asarray(hb.frame_seed).astype(np.uint32).reshape(-1)
+            if seeds.size != F:
+                raise ValueError("frame_seed: one word per frame")
+            b.frame_seed = t(seeds.view(np.int32))
+            b.hit_uvd = e(b.idx_cap, 4, dtype=torch.float32)
+            b.vp_count = e(M); b.vp_status = e(M); b.vp_xyz = e(M * K, 3, dtype=torch.float64); b.vp_pix = e(M * K, 2); b.vp_src = e(M * K)
+            b.vp_depth = e(M * K, dtype=torch.float32); b.vp_d2 = e(M * K, dtype=torch.float32)
         if self.ground is not None:
             b.ground_z = e(M, dtype=torch.float64); b.ground_h = e(M, dtype=torch.float64); b.ground_zref = e(M, dtype=torch.float64)
             b.ground_n = e(M); b.ground_src = e(M); b.ground_status = e(M)
@@ -760,7 +782,7 @@ class LiftEngine:
         if self.place is not None:             # (no member of the options: cm3d_lift_pass_placed takes it beside them; its events come last)
             b.place_desc = b.timed["place"] = self._place_descriptor(b)
         b.opts_ref = ctypes.byref(b.opts) if stages else None
-        b.plain_pass = not stages and self.velocity is None and self.vertical is None and self.ground is None and self.strip is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
+        b.plain_pass = not stages and self.velocity is None and self.vertical is None and self.ground is None and self.strip is None and self.virtual is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
         self.b = b
         return b
 
@@ -1193,6 +1215,19 @@ class LiftEngine:
                                          len(self.classes.names), v.q_bot, v.q_top, v.min_points, v.lo, v.hi, _ptr(b.vert_z), _ptr(b.vert_h),
                                          _ptr(b.vert_src), _ptr(b.vert_status), _ptr(b.vert_entry_z), st), "cm3d_box_vertical")
 
+    def stage_virtual(self, st):
+        """The opt-in virtual points alone, on the masks, the lists and the flags the last pass left resident (cm3d_hit_project, then
+        cm3d_virtual_points): the lists stage_vertical reads."""
+        b, v = self.b, self.virtual
+        xyz, off = self.read_lists()
+        check(self.lib.cm3d_hit_project(_ptr(xyz), _ptr(off), _ptr(b.mask_frame), _ptr(b.mask_cam), _ptr(b.cams), b.hb.n_cams, b.F, b.M,
+                                        b.idx_cap, _ptr(b.hit_uvd), st), "cm3d_hit_project")
+        check(self.lib.cm3d_virtual_points(_ptr(b.packed), _ptr(b.bbox), b.W, b.H, _ptr(b.cams), b.hb.n_cams, _ptr(b.mask_off),
+                                           _ptr(b.mask_frame), _ptr(b.mask_cam), _ptr(b.flags), b.F, b.M, _ptr(b.hit_uvd), _ptr(off), b.idx_cap,
+                                           v.per_mask, v.seed, v.max_px, int(v.kept_only), _ptr(b.frame_seed), _ptr(b.vp_count),
+                                           _ptr(b.vp_status), _ptr(b.vp_xyz), _ptr(b.vp_pix), _ptr(b.vp_src), _ptr(b.vp_depth), _ptr(b.vp_d2),
+                                           st), "cm3d_virtual_points")
+
     def stage_ground(self, st, zref=None):
         """The opt-in ground stage alone, on the sweep rows and the box rows the last pass left resident (cm3d_box_ground): the cloud where
         the engine has materialised it, the raw rows otherwise.  zref: None -- the reference heights are `vert_entry_z` with a vertical
@@ -1220,7 +1255,8 @@ class LiftEngine:
         bucket), around the ground strip's launches (the "strip" bucket; behind the second of the five, in front of the clustering's), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
         the yaw fit's two launches (the "yawfit" bucket; behind the fifth event), around the placement's launch (the "place" bucket;
         behind the yaw fit's boxes), around the vertical stage's call (the "vertical" bucket; behind the pass), around the ground stage's
-        call (the "ground" bucket; behind the vertical stage's).  One library call enqueues
+        call (the "ground" bucket; behind the vertical stage's), around the virtual points' call (the "virtual points" bucket; last of
+        all, behind the velocity, track and size stages' calls, which have no events).  One library call enqueues
         the pass, opt-in stages included (cm3d_lift_pass_opt, cm3d_lift_pass_placed with a placement, or cm3d_lift_pass_stripped with a ground strip; include/cm3d_hip.h states the
         order); no allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
@@ -1264,6 +1300,15 @@ class LiftEngine:
             self.stage_tracks(st)
         if self.size is not None:                        # behind the track stage, on its tracks: one more
             self.stage_size(st)
+        if self.virtual is not None:                     # behind everything that writes `flags`; it writes no box, flag or record
+            pair = None
+            if stage_events is not None:
+                pair = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+                stage_events.extend(pair)
+                pair[0].record(torch.cuda.current_stream(self.dev))
+            self.stage_virtual(st)
+            if pair is not None:
+                pair[1].record(torch.cuda.current_stream(self.dev))
 
     def capture_graph(self, masks="rle"):
         """Captures one pass over the resident batch into a HIP graph and returns it (`g.replay()` re-runs the pass
@@ -1389,6 +1434,8 @@ class LiftEngine:
                 out.update(self._vertical_results())
             if self.ground is not None:
                 out.update(self._ground_results())
+            if self.virtual is not None:
+                out.update(self._virtual_results())
             return out
         n_rows, n_idx = int(s[1]), int(s[2])
         pt_off_rows = b.pt_off.cpu().numpy()
@@ -1432,7 +1479,14 @@ class LiftEngine:
             out.update(self._vertical_results())
         if self.ground is not None:
             out.update(self._ground_results())
+        if self.virtual is not None:
+            out.update(self._virtual_results())
+            n_list = int(self.read_lists()[1][-1].item())
+            out["hit_uvd"] = b.hit_uvd[:max(0, min(n_list, b.idx_cap))].cpu().numpy()
         return out
+
+    def _virtual_results(self):
+        return {k: getattr(self.b, k).cpu().numpy() for k in VIRTUAL_RESULTS}
 
     def _ground_results(self):
         return {k: getattr(self.b, k).cpu().numpy() for k in GROUND_RESULTS}
@@ -1652,6 +1706,19 @@ def kept_box_velocities(b):
     if vel is None:
         vel = getattr(b, "vel_smooth", None)
     return (b.vel if vel is None else vel)[(b.flags & 3) == 3].clone()
+
+
+def virtual_point_frames(eng):
+    """The virtual points of the batch resident in `eng` (an engine with VirtualPoints(...), its pass finished), frame by frame: a list
+    of F entries, each the dict virtualpoints.frame_records makes -- xyz, pixel, cam, mask, class_id, src_idx (the winner's index in the
+    frame's cloud, the reference's track_points numbering), score, depth -- or None for a frame without a point."""
+    from . import virtualpoints as vpmod
+    b = eng.b
+    res = eng._virtual_results()
+    off = eng.read_lists()[1].cpu().numpy()
+    idx = (b.cl_idx if eng.cluster is not None else b.gs_idx if eng.strip is not None else b.hit_idx)[:max(0, min(int(off[-1]), b.idx_cap))]
+    idx, hb = idx.cpu().numpy(), b.hb
+    return [vpmod.frame_records(res, f, eng.virtual.per_mask, hb.mask_off, hb.mask_cam, hb.class_id, hb.score, off, idx) for f in range(b.F)]
 
 
 def kept_box_sizes(b):

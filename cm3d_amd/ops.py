@@ -616,6 +616,81 @@ def box_vertical(xyz, off, box, flags, prior_wlh, q_bot=0.02, q_top=0.98, min_po
                 vert_status=status.cpu().numpy()[:M], vert_entry_z=ez.cpu().numpy()[:M], box=d_box.cpu().numpy()[:M])
 
 
+def _filled(fill, *shape, dtype=torch.int32):
+    """An output buffer: uninitialised, or every byte `fill` (the tests' poison)."""
+    t = _e(*shape, dtype=dtype)
+    if fill is not None:
+        t.view(torch.uint8).fill_(int(fill))
+    return t
+
+
+def hit_project(xyz, off, mask_frame, mask_cam, cams, idx_cap=None, fill=None):
+    """Step 1 of the virtual-point stage on arrays (cm3d_hit_project): xyz (n, 4) float32, the points of all lists; off int32 (M + 1,);
+    mask_frame, mask_cam (M,); cams (F, n_cams, CAM_STRIDE) float32; idx_cap: the capacity the call is told (default: the rows of xyz).
+    Returns hit_uvd (max(n, idx_cap), 4) float32: (u, v, depth, 0) of every list position below idx_cap; the other rows keep what the
+    buffer held (`fill`: that byte everywhere before the call)."""
+    L = _lib.lib()
+    p = np.asarray(xyz, np.float32).reshape(-1, 4)
+    cap = int(p.shape[0] if idx_cap is None else idx_cap)
+    rows = max(p.shape[0], cap, 1)
+    P4 = np.zeros((rows, 4), np.float32)
+    P4[:p.shape[0]] = p
+    off = np.ascontiguousarray(off, np.int32).reshape(-1)
+    M = off.size - 1
+    cams = np.ascontiguousarray(cams, np.float32).reshape(-1, np.shape(cams)[-2], _lib.CAM_STRIDE)
+    F, n_cams = cams.shape[0], cams.shape[1]
+    d_frame = _t(np.asarray(mask_frame, np.int32).reshape(M) if M else np.zeros(1, np.int32))
+    d_cam = _t(np.asarray(mask_cam, np.int32).reshape(M) if M else np.zeros(1, np.int32))
+    d_xyz, d_off, d_cams = _t(P4), _t(off), _t(cams)
+    uvd = _filled(fill, rows, 4, dtype=torch.float32)
+    check(L.cm3d_hit_project(d_xyz.data_ptr(), d_off.data_ptr(), d_frame.data_ptr(), d_cam.data_ptr(), d_cams.data_ptr(), n_cams, F, M, cap,
+                             uvd.data_ptr(), _st()), "cm3d_hit_project")
+    return uvd.cpu().numpy()
+
+
+def virtual_points(packed, bbox, W, H, cams, mask_off, mask_frame, mask_cam, flags, hit_uvd, off, per_mask=50, seed=0, max_px=0.0,
+                   kept_only=True, frame_seed=None, idx_cap=None, fill=None):
+    """The virtual-point stage on arrays (cm3d_virtual_points; virtualpoints.virtual_points_host states it): packed, M slots of H * Wp
+    words, and bbox (M, BBOX_STRIDE) as the mask kernels leave them; cams (F, n_cams, CAM_STRIDE) float32; mask_off (F + 1,); mask_frame,
+    mask_cam, flags (M,; flags may be None without kept_only); hit_uvd (n, 4) float32 (hit_project); off int32 (M + 1,); frame_seed (F,)
+    uint32, None: arange(F); idx_cap: the capacity the call is told (default: the rows of hit_uvd).  Returns a dict of the seven whole
+    output arrays: rows behind a mask's count keep what the buffers held (`fill`: that byte everywhere before the call).  The defaults
+    are untuned."""
+    L = _lib.lib()
+    W, H, K = int(W), int(H), int(per_mask)
+    Wp = (W + 31) // 32
+    bbox = np.ascontiguousarray(bbox, np.int32).reshape(-1, _lib.BBOX_STRIDE)
+    M = bbox.shape[0]
+    uvd = np.asarray(hit_uvd, np.float32).reshape(-1, 4)
+    cap = int(uvd.shape[0] if idx_cap is None else idx_cap)
+    U4 = np.zeros((max(uvd.shape[0], cap, 1), 4), np.float32)
+    U4[:uvd.shape[0]] = uvd
+    cams = np.ascontiguousarray(cams, np.float32).reshape(-1, np.shape(cams)[-2], _lib.CAM_STRIDE)
+    F, n_cams = cams.shape[0], cams.shape[1]
+    words = np.ascontiguousarray(packed).view(np.int32).reshape(-1)
+    if words.size != M * H * Wp:
+        raise ValueError("packed: one slot of H * Wp words per mask")
+    fs = np.arange(F, dtype=np.uint32) if frame_seed is None else np.asarray(frame_seed).astype(np.uint32).reshape(F)
+    one = np.zeros(1, np.int32)
+    d_packed, d_bbox = _t(words if M else one), _t(bbox if M else np.zeros((1, _lib.BBOX_STRIDE), np.int32))
+    d_cams, d_moff, d_fs = _t(cams), _t(np.asarray(mask_off, np.int32).reshape(-1)), _t(fs.view(np.int32) if F else one)
+    d_frame = _t(np.asarray(mask_frame, np.int32).reshape(M) if M else one)
+    d_cam = _t(np.asarray(mask_cam, np.int32).reshape(M) if M else one)
+    d_flags = None if flags is None else _t(np.asarray(flags, np.int32).reshape(M) if M else one)
+    d_uvd, d_off = _t(U4), _t(np.ascontiguousarray(off, np.int32).reshape(-1))
+    n, nk = max(M, 1), max(M * max(K, 1), 1)
+    count, status = _filled(fill, n), _filled(fill, n)
+    xyz, pix, src = _filled(fill, nk, 3, dtype=torch.float64), _filled(fill, nk, 2), _filled(fill, nk)
+    depth, d2 = _filled(fill, nk, dtype=torch.float32), _filled(fill, nk, dtype=torch.float32)
+    check(L.cm3d_virtual_points(d_packed.data_ptr(), d_bbox.data_ptr(), W, H, d_cams.data_ptr(), n_cams, d_moff.data_ptr(), d_frame.data_ptr(),
+                                d_cam.data_ptr(), None if d_flags is None else d_flags.data_ptr(), F, M, d_uvd.data_ptr(), d_off.data_ptr(), cap,
+                                K, int(seed) & 0xFFFFFFFF, float(max_px), int(bool(kept_only)), d_fs.data_ptr(), count.data_ptr(),
+                                status.data_ptr(), xyz.data_ptr(), pix.data_ptr(), src.data_ptr(), depth.data_ptr(), d2.data_ptr(), _st()),
+          "cm3d_virtual_points")
+    return dict(vp_count=count.cpu().numpy(), vp_status=status.cpu().numpy(), vp_xyz=xyz.cpu().numpy(), vp_pix=pix.cpu().numpy(),
+                vp_src=src.cpu().numpy(), vp_depth=depth.cpu().numpy(), vp_d2=d2.cpu().numpy())
+
+
 def box_ground(box, flags, prior_wlh, mask_off, points=None, pt_off=None, raw=None, raw_stride=4, sweep_xf=None, sweep_row_off=None,
                frame_sweep_off=None, halfw=0.0, zref=None, vert=None, zref_aliases=False, radius=3.0, quantile=0.1, min_points=20, down=5.0,
                up=0.5, lo=0.7, hi=1.3):

@@ -29,6 +29,7 @@ from . import boxsize as szmod
 from . import boxvertical as vtmod
 from . import boxground as grmod
 from . import groundstrip as gsmod
+from . import virtualpoints as vpmod
 
 # module constants of the reference (:55-59)
 VER_NAME = "v1.0-trainval"
@@ -229,7 +230,8 @@ def _token_batches(batches, index, host_s):
 
 
 def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                  velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None, strip=None):
+                  velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None, strip=None,
+                  virtual=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
@@ -254,7 +256,10 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
     column 2 then carries its heights (`ground_h`), shipped the same way.  strip: the opt-in ground strip (groundstrip.GroundStrip; with
     any option or none), inside the pass between the compaction and the clustering; its two events come behind the filter's and in front
     of the clustering's, inside the "medoid" span, and the time between them goes into a "strip" bucket instead.  The records are what
-    they were in form: nothing else changes here."""
+    they were in form: nothing else changes here.  virtual: the opt-in virtual points (virtualpoints.FrameFiles; with any option or none),
+    one call behind everything else; its two events come last of all, and the time between them goes into a "virtual points" bucket.  Every
+    frame's seed word is its index in the output order, and every finished batch's frames with a point are written to their files here:
+    the records are untouched."""
     sized = size is not None or vertical is not None or ground is not None      # the records travel with (k, 3) size rows
     kw = {} if yaw is None else {"yaw": yaw}
     if place is not None:
@@ -271,12 +276,14 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
         kw["ground"] = ground
     if strip is not None:
         kw["strip"] = strip
+    if virtual is not None:
+        kw["virtual"] = virtual.stage
     vels, sizes = [], []
     pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms, **kw)
     n_f, n_c, n_y = (2 if filters is not None and filters.active else 0), (2 if cluster is not None else 0), (2 if yaw is not None else 0)
     n_p, n_v, n_g = (2 if place is not None else 0), (2 if vertical is not None else 0), (2 if ground is not None else 0)
-    n_s = 2 if strip is not None else 0
-    n_evs = 5 + n_f + n_s + n_c + n_y + n_p + n_v + n_g
+    n_s, n_vp = (2 if strip is not None else 0), (2 if virtual is not None else 0)
+    n_evs = 5 + n_f + n_s + n_c + n_y + n_p + n_v + n_g + n_vp
     records, pending, segments = [], [], []                            # pending: (slot, frame ids, stage events) in flight, oldest first
 
     def spent(key, since):
@@ -292,6 +299,10 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
             if sized:
                 sizes.append(lifting.kept_box_sizes(pipe.engines[slot].b))
             spent("gpu lifting", t1)
+            if virtual is not None:                                    # this batch's files; every rank writes its own frames'
+                t1 = time.time()
+                virtual.write_batch(lifting.virtual_point_frames(pipe.engines[slot]), ids[:, 0])
+                spent("write", t1)
             if on_records is not None:
                 first = int(ids[0, 0]) if len(ids) else 0
                 extra = () if velocity is None else (vels[-1].cpu().numpy(),)
@@ -321,9 +332,11 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
                     at = 5 + n_f + n_s + n_c + n_y
                     timer["place"] = timer.get("place", 0.0) + evs[at].elapsed_time(evs[at + 1]) * 1e-3
                 if vertical is not None:                               # behind the pass
-                    timer["vertical"] = timer.get("vertical", 0.0) + evs[-2 - n_g].elapsed_time(evs[-1 - n_g]) * 1e-3
-                if ground is not None:                                 # the last two events, behind the vertical stage's
-                    timer["ground"] = timer.get("ground", 0.0) + evs[-2].elapsed_time(evs[-1]) * 1e-3
+                    timer["vertical"] = timer.get("vertical", 0.0) + evs[-2 - n_g - n_vp].elapsed_time(evs[-1 - n_g - n_vp]) * 1e-3
+                if ground is not None:                                 # the two events behind the vertical stage's
+                    timer["ground"] = timer.get("ground", 0.0) + evs[-2 - n_vp].elapsed_time(evs[-1 - n_vp]) * 1e-3
+                if virtual is not None:                                # the last two events
+                    timer["virtual points"] = timer.get("virtual points", 0.0) + evs[-2].elapsed_time(evs[-1]) * 1e-3
 
     try:
         for hb, ids, host_s in prepared:
@@ -333,6 +346,8 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
             t1 = time.time()
             _attach_raw(hb, segments)
             drain(pipe.depth - 1)                                      # the slot about to be reused is free
+            if virtual is not None:                                    # a frame's seed word: its index in the job's output order
+                hb.frame_seed = np.asarray(ids[:, 0], np.int64).astype(np.uint32)
             evs = []
             t2 = time.time()
             slot = pipe.submit(hb, masks, stage_events=evs)
@@ -358,7 +373,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                 scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None,
                 cluster=None, nms=None, yaw=None, velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None,
-                vertical=None, ground=None, strip=None):
+                vertical=None, ground=None, strip=None, virtual=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -393,7 +408,7 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
     with contextlib.closing(prepared()) as batches:
         return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms, yaw=yaw, velocity=velocity,
                              vel_out=vel_out, tracks=tracks, place=place, size=size, size_out=size_out, vertical=vertical, ground=ground,
-                             strip=strip)
+                             strip=strip, virtual=virtual)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -471,7 +486,8 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
 
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                        scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
-                       velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None, strip=None):
+                       velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None, strip=None,
+                       virtual=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -515,7 +531,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
         return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw, velocity, vel_out, tracks, place,
-                             size, size_out, vertical, ground, strip)
+                             size, size_out, vertical, ground, strip, virtual)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -556,6 +572,7 @@ def main(argv=None):
     vtmod.add_arguments(ap)
     grmod.add_arguments(ap)
     gsmod.add_arguments(ap)
+    vpmod.add_arguments(ap)
     args = ap.parse_args(argv)
     cluster = clmod.from_namespace(args)
     nms = nmsmod.from_args(args)
@@ -567,6 +584,7 @@ def main(argv=None):
     vertical = vtmod.from_args(args, ap)            # (a --vertical-* flag without --vertical fit: the same)
     ground = grmod.from_args(args, ap)              # (a --ground-* flag without --ground fit: the same)
     strip = gsmod.from_namespace(args, ap)          # (a --ground-strip-* flag without --ground-strip grid: the same)
+    vp_stage = vpmod.from_args(args, ap)            # (a --virtual-points-* flag without --virtual-points DIR: the same)
     sized = size is not None or vertical is not None or ground is not None
     size_mine = []                                 # with --size track, --vertical fit or --ground fit: the sizes of this rank's records, one device tensor
     vel_mine = []                                  # with --velocity track: the velocities of this rank's records, one device tensor
@@ -605,6 +623,7 @@ def main(argv=None):
     lo, hi = cdist.shard_scenes([n_samples(n) for n in names], world)[rank]
     if native:
         tokens, rows = nt.job_tokens(names)                    # the whole job's samples, identical on every rank
+        virtual = None if vp_stage is None else vpmod.FrameFiles(vp_stage, args.virtual_points, list(tokens))
         row_to_out = np.full(int(rows.max()) + 1 if len(rows) else 1, -1, np.int64)
         row_to_out[rows] = np.arange(len(rows))
 
@@ -645,17 +664,18 @@ def main(argv=None):
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
                                   on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
                                   velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine,
-                                  vertical=vertical, ground=ground, strip=strip)
+                                  vertical=vertical, ground=ground, strip=strip, virtual=virtual)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
     else:
         tokens = sample_tokens(tables, names)                  # the whole job's samples, identical on every rank
+        virtual = None if vp_stage is None else vpmod.FrameFiles(vp_stage, args.virtual_points, list(tokens))
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
                            token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
                            velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine, vertical=vertical, ground=ground,
-                           strip=strip)
+                           strip=strip, virtual=virtual)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.

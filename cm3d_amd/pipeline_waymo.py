@@ -32,6 +32,7 @@ from . import boxplace
 from . import boxvertical as vtmod
 from . import boxground as grmod
 from . import groundstrip as gsmod
+from . import virtualpoints as vpmod
 from . import dist as cdist
 from . import lifting
 from . import waymo as wm
@@ -77,21 +78,30 @@ def load_scene(frames_dir, mask_dir, scene, tfrecord=None):
     return frames, lane_table
 
 
-def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0, heights=None):
+def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0, heights=None, virtual_dir=None):
     """One scene through the hot path, its frames in one batch; returns its kept-box records as a list of device tensors
     (lifting.kept_box_records with column 5 = scene_index, column 6 = the frame's number inside the scene).  Masks of different image
     sizes -- Waymo's side cameras, inside every frame -- share the batch (lifting.pack_frames).  heights: a list that, with an engine
-    whose vertical or ground stage is on, gets the (k,) heights of the returned records appended (column 2 of lifting.kept_box_sizes)."""
+    whose vertical or ground stage is on, gets the (k,) heights of the returned records appended (column 2 of lifting.kept_box_sizes).
+    virtual_dir: with an engine whose virtual points are on, the directory that gets <frame file's stem>.npz of every frame with a point
+    (virtualpoints.write_frame); a frame's seed word is scene_index * 65536 + its number in the scene, the same however the job is cut."""
     hb = lifting.pack_frames(frames, [lane_table], [0] * len(frames), classes)
     if masks == "dense":
         lifting.require_one_mask_size(hb)
+    numbers = [int(f.token.rsplit(":", 1)[1]) for f in frames]
+    if eng.virtual is not None:
+        hb.frame_seed = ((np.int64(scene_index) << 16) + np.asarray(numbers, np.int64)).astype(np.uint32)
     eng.upload(hb)
     if masks == "dense":
         eng.decode_masks_dense()
     eng.run(masks=masks)
     torch.cuda.synchronize()
     eng.check_status()
-    ids = np.array([[scene_index, int(f.token.rsplit(":", 1)[1])] for f in frames], np.float64)
+    ids = np.array([[scene_index, k] for k in numbers], np.float64)
+    if eng.virtual is not None and virtual_dir is not None:
+        for rec, k in zip(lifting.virtual_point_frames(eng), numbers):
+            if rec is not None:
+                vpmod.write_frame(virtual_dir, f"{k}_frame", rec)
     if heights is not None and (eng.vertical is not None or eng.ground is not None):
         heights.append(lifting.kept_box_sizes(eng.b)[:, 2:3].contiguous())
     return [lifting.kept_box_records(eng.b, ids)]
@@ -147,11 +157,13 @@ def main(argv=None):
     vtmod.add_arguments(ap)
     grmod.add_arguments(ap)
     gsmod.add_arguments(ap)
+    vpmod.add_arguments(ap)
     args = ap.parse_args(argv)
     place = boxplace.from_namespace(args, ap)       # (--place fit without --yaw fit: an error of the command line)
     vertical = vtmod.from_args(args, ap)            # (a --vertical-* flag without --vertical fit: the same)
     ground = grmod.from_args(args, ap)              # (a --ground-* flag without --ground fit: the same)
     strip = gsmod.from_namespace(args, ap)          # (a --ground-strip-* flag without --ground-strip grid: the same)
+    virtual = vpmod.from_args(args, ap)             # (a --virtual-points-* flag without --virtual-points DIR: the same)
     filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
     rank, world, local_rank = cdist.init_from_env()
@@ -164,7 +176,7 @@ def main(argv=None):
     classes = lifting.ClassTable.waymo(pri)
     eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args),
                              nms=nmsmod.from_args(args), yaw=bevfit.from_namespace(args), place=place,
-                             vertical=vertical, ground=ground, strip=strip)
+                             vertical=vertical, ground=ground, strip=strip, virtual=virtual)
     lo, hi = cdist.shard_range(len(scenes), rank, world)
     mine, meta, heights = [], {}, []
     for si in range(lo, hi):
@@ -174,7 +186,8 @@ def main(argv=None):
         if frames:
             if lanes is None:
                 raise FileNotFoundError(f"{scenes[si]}: no lane polylines (frame 0)")
-            mine.extend(lift_scene(eng, frames, lanes, classes, args.masks, scene_index=si, heights=heights))
+            mine.extend(lift_scene(eng, frames, lanes, classes, args.masks, scene_index=si, heights=heights,
+                                   virtual_dir=None if virtual is None else os.path.join(args.virtual_points, scenes[si])))
     rec = torch.cat(mine, 0) if mine else torch.zeros(0, 10, dtype=torch.float64, device=eng.dev)
     # the single exchange of the job: fixed-size box records -> rank 0 (also the path of a one-rank run)
     gathered = cdist.gather_records(rec, dst=0)

@@ -1392,6 +1392,82 @@ typedef struct cm3d_ground_strip_desc {
 int cm3d_lift_pass_stripped(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, const cm3d_box_place_desc *place,
                             const cm3d_ground_strip_desc *strip, cm3d_stream_t stream);
 
+/* ---- opt-in: virtual points from each mask, nearest-depth lifting (csrc/virtual.hip) ---------------------------
+ * Added within ABI v5: new symbols only, so CM3D_ABI_VERSION stays.  Every stage behind the compaction refines the one box a mask
+ * gets; this one yields the other product of a 2D -> 3D lifter: for every instance mask, pixels sampled inside the eroded mask take the
+ * depth of the nearest LiDAR return that projects into the same mask and are unprojected to 3D.  It writes no box, flag or record.  The
+ * reference's authors left a beginning of it dead (src/kitti/2d_to_3d.py:613-724, never called); the rule below is this project's own.
+ * The defaults K = 50, SEED = 0, MAX_PX = 0 are UNTUNED, and what the points do to a detector has not been measured.  Host statement
+ * to the bit: cm3d_amd.virtualpoints.virtual_points_host (steps 2 to 5; step 1 is held against the oracle's project_points).
+ * F = n_frames, M = n_masks.
+ *
+ * Inputs per mask m of frame f = mask_frame[m], with camera c = mask_cam[m] and kk = m - mask_off[f]: the mask's eroded bits -- the
+ * bits of `packed` inside the eroded bounds bbox[0..3], read through the stored-rectangle layout bbox[4..7] (cm3d_erode_pack above;
+ * both stored forms, the workgroup-per-mask RLE form at the image's row stride included: only words of the eroded bounds are read); the
+ * camera record cams[f][c]; the list the medoid saw, positions off[m] .. off[m+1] of `xyz` (the clustered list, else the stripped
+ * list, else hit_*), n positions, the offsets clamped into [0, idx_cap] as cm3d_box_vertical clamps them.
+ * Parameters: K virtual points per mask, 1 <= K <= CM3D_VP_MAX_K = 1024; SEED uint32; MAX_PX double >= 0, 0 = no limit; KEPT_ONLY:
+ * only masks with (flags & 3) == 3 get points; frame_seed uint32[F], one word per frame (the entry points pass the frame's ordinal in
+ * the whole job, so that a frame's points do not depend on how the job was cut into batches).
+ *
+ *  1. Re-projection (cm3d_hit_project).  For every list position, (u, v, depth) by the exact float32 chain of the mask's own camera
+ *     applied to that position's x, y, z: the stages with optional t_pre / t_post, k-sequential fmaf, then the K' rows with the
+ *     trailing fmaf(0, 1, acc), then IEEE division -- the arithmetic orc_project_points states and the projection kernels implement;
+ *     depth is the z behind the last stage.  hit_uvd float[idx_cap][4] = (u, v, depth, 0).  A position of a mask whose frame or camera
+ *     number is out of range, and every position outside the lists, is not written.
+ *  2. Sampling without replacement, integers only.  A = set pixels of the eroded mask, k = min(K, A).  Pixels are ranked by ascending
+ *     y, then ascending x.  For j in [0, k), with uint64 products: lo = j*A / k, hi = (j+1)*A / k, w = hi - lo (always >= 1),
+ *     r_j = lo + (h_j mod w), with h_j = mix(SEED ^ frame_seed[f]*0x9E3779B1 ^ kk*0x85EBCA77 ^ j*0xC2B2AE3D), all uint32 with
+ *     wraparound, and mix(x): x ^= x>>16; x *= 0x7FEB352D; x ^= x>>15; x *= 0x846CA68B; x ^= x>>16.  The sample is the r_j-th set pixel
+ *     (px, py), 0-based; its centre is cx = (float)px + 0.5f, cy = (float)py + 0.5f.  When A <= K every set pixel is drawn exactly once.
+ *  3. Nearest return in the image.  Over list positions i in ascending order: du = u_i - cx; dv = v_i - cy; d2 = fmaf(dv, dv, du*du)
+ *     in float32.  The winner is the first i with the least d2 under strict <; a NaN never wins.  If no position wins, the sample is
+ *     dropped.  If MAX_PX > 0 and (double)d2 > MAX_PX*MAX_PX, the sample is dropped.
+ *  4. Unprojection.  Float64 throughout, every operation rounded on its own, no contraction, brackets as written.  d = (double)depth_i;
+ *     yc = ((cy - K12) * d) / K11;  xc = (((cx - K02) * d) - K01 * yc) / K00;  zc = d.  Then, for stages from the last to the first:
+ *     p -= t_post where the flag says so; p = R^T p with o[r] = (R[0][r]*x + R[1][r]*y) + R[2][r]*z; p -= t_pre where the flag says
+ *     so.  The stages are rotations in all three entry points; the rule uses the transpose whatever they hold.  A camera whose K' has a
+ *     last row other than (0, 0, 1), K10 != 0, or a zero or non-finite K00 / K11 gives the mask status 4 and no points; so does a
+ *     frame or camera number out of range or a stage count outside [0, 3].
+ *  5. Output.  Mask m owns rows [m*K, m*K + vp_count[m]).  Kept samples are in ascending j with no holes.  Rows behind the count are
+ *     never written.
+ *       vp_count  int32[M]       points written for mask m
+ *       vp_status int32[M]       0 ok; 1 skipped by KEPT_ONLY; 2 empty list or empty mask (bounds or a stored rectangle that do not
+ *                                lie inside the image and the mask's slot count as empty); 4 camera not invertible.  Where several
+ *                                hold: 1 before 4 before 2.
+ *       vp_xyz    double[M*K][3] point in the frame of the pass's cloud: global on nuScenes, vehicle on Waymo
+ *       vp_pix    int32[M*K][2]  the sampled pixel
+ *       vp_src    int32[M*K]     the winner's position in the mask's list
+ *       vp_depth  float[M*K]     the winner's depth
+ *       vp_d2     float[M*K]     the winner's squared pixel distance
+ *
+ *  cm3d_virtual_points_check: CM3D_OK iff 1 <= K <= CM3D_VP_MAX_K and MAX_PX is finite and >= 0; anything else, NaN included, is
+ *  CM3D_ERR_ARG.  cm3d_virtual_points applies it before any launch.  CM3D_ERR_ARG before any launch as well, for both calls: a
+ *  negative count, n_cams > CM3D_MAX_CAMS, xyz or hit_uvd not 16-byte aligned, with M > 0 a NULL array (flags may be NULL without
+ *  KEPT_ONLY; xyz and hit_uvd with idx_cap == 0) or F == 0 or n_cams == 0; for cm3d_virtual_points W or H < 1, H > CM3D_VP_MAX_ROWS =
+ *  4096, or M*H*Wp beyond 2^31 - 1.  M == 0: CM3D_OK, nothing launched, nothing written.
+ *  cm3d_hit_project is one launch, k_hit_project: one thread per list position below the last offset, its mask by a search of the
+ *  offsets (which ascend); the grid is bounded (2048 workgroups), so a thread takes several positions where the lists are long.
+ *  cm3d_virtual_points is one launch, k_virtual_points: one workgroup of four waves per mask -- (a) row popcounts of the eroded
+ *  bounds, scanned into LDS, give A; (b) a wave per sample selects rank -> pixel by a search of the row prefix, a wave scan over the
+ *  row's words and the bit within the word; (c) the same wave takes the argmin over the list, the lexicographic (d2, position)
+ *  minimum, (u, v) staged in LDS for lists of up to CM3D_VP_LDS_LIST = 256 positions and read from memory otherwise; then the keep
+ *  flags are scanned in ascending j and the kept samples unprojected, one lane each.  No position >= idx_cap and no word outside a
+ *  mask's slot is read whatever the offsets and bbox hold.  Plain stores, no global atomic, no allocation, no read-back: every run
+ *  gives the same bytes, and both calls can be captured in a graph. */
+#define CM3D_VP_MAX_K 1024
+#define CM3D_VP_MAX_ROWS 4096
+#define CM3D_VP_LDS_LIST 256
+int cm3d_virtual_points_check(int32_t per_mask, double max_px);
+int cm3d_hit_project(const float *xyz, const int32_t *off, const int32_t *mask_frame, const int32_t *mask_cam, const float *cams,
+                     int32_t n_cams, int32_t n_frames, int32_t n_masks, int32_t idx_cap, float *hit_uvd, cm3d_stream_t stream);
+int cm3d_virtual_points(const uint32_t *packed, const int32_t *bbox, int32_t W, int32_t H, const float *cams, int32_t n_cams,
+                        const int32_t *mask_off, const int32_t *mask_frame, const int32_t *mask_cam, const int32_t *flags,
+                        int32_t n_frames, int32_t n_masks, const float *hit_uvd, const int32_t *off, int32_t idx_cap,
+                        int32_t per_mask, uint32_t seed, double max_px, int32_t kept_only, const uint32_t *frame_seed,
+                        int32_t *vp_count, int32_t *vp_status, double *vp_xyz, int32_t *vp_pix, int32_t *vp_src, float *vp_depth,
+                        float *vp_d2, cm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
