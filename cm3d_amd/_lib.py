@@ -146,6 +146,10 @@ SIGNATURES = {
     "cm3d_hit_project": (_i32, [_p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _p]),
     "cm3d_virtual_points": (_i32, [_p, _p, _i32, _i32, _p, _i32, _p, _p, _p, _p, _i32, _i32, _p, _p, _i32, _i32, C.c_uint32, C.c_double, _i32,
                                    _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "cm3d_point_owner_check": (_i32, [_i32, _i32]),
+    "cm3d_point_owner_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "cm3d_point_owner": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
+    "cm3d_lift_pass_owned": (_i32, [_p, _p, _p, _p, _p, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order
@@ -214,6 +218,12 @@ class GroundStripDesc(C.Structure):
                                                       "gs_dropped", "ws")]
                 + [("ws_bytes", _i64), ("ev", _p * 2)] + [(n, C.c_double) for n in ("cell", "down", "up", "quantile", "margin")]
                 + [("min_points", _i32), ("min_keep", _i32)])
+
+
+class PointOwnerDesc(C.Structure):
+    """cm3d_point_owner_desc of include/cm3d_hip.h, field for field."""
+    _fields_ = ([("size", _i64)] + [(n, _p) for n in ("ow_owner", "ow_off", "ow_tile_off", "ow_idx", "ow_xyz", "ow_status", "ow_lost", "ws")]
+                + [("ws_bytes", _i64), ("ev", _p * 2), ("rule", _i32), ("min_keep", _i32)])
 
 
 class Cm3dError(RuntimeError):

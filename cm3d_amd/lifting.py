@@ -34,6 +34,7 @@ from .boxvertical import BoxVertical, RESULTS as VERTICAL_RESULTS  # noqa: F401 
 from .virtualpoints import VirtualPoints, RESULTS as VIRTUAL_RESULTS  # noqa: F401  (LiftEngine(virtual=VirtualPoints(...)))
 from .boxground import BoxGround, RESULTS as GROUND_RESULTS  # noqa: F401  (LiftEngine(ground=BoxGround(...)))
 from .groundstrip import GroundStrip, N_CELLS as GRID_CELLS  # noqa: F401  (LiftEngine(strip=GroundStrip(...)))
+from .pointowner import PointOwner  # noqa: F401  (LiftEngine(owner=PointOwner(...)))
 
 # ---- tables of the reference --------------------------------------------------
 CAM_LIST = ["CAM_FRONT", "CAM_FRONT_RIGHT", "CAM_BACK_RIGHT", "CAM_BACK", "CAM_BACK_LEFT", "CAM_FRONT_LEFT"]  # :62-69
@@ -461,7 +462,7 @@ class LiftEngine:
                  cluster: Optional[DepthCluster] = None, nms: Optional[RotatedNms] = None, yaw: Optional[YawFit] = None,
                  velocity: Optional[Velocity] = None, tracks: Optional[Tracks] = None, place: Optional[BoxPlace] = None,
                  size: Optional[BoxSize] = None, vertical: Optional[BoxVertical] = None, ground: Optional[BoxGround] = None,
-                 strip: Optional[GroundStrip] = None, virtual: Optional[VirtualPoints] = None):
+                 strip: Optional[GroundStrip] = None, virtual: Optional[VirtualPoints] = None, owner: Optional[PointOwner] = None):
         """keep_cloud: also materialise the transformed cloud (`points`, the reference's aggregated `pc`).  The path
         itself does not need it -- the in-mask points are re-derived from the raw rows (hit_xyz) -- so the default is
         off (CM3D_KEEP_CLOUD=1 turns it on); tests and callers that want the cloud back ask for it.
@@ -522,7 +523,14 @@ class LiftEngine:
         eroded mask with the depth of the nearest return in the image (cm3d_virtual_points).  It writes no box, flag or record: every
         other downloaded array is what it is without it.  The sampling takes HostBatch.frame_seed (None: arange(F)).  download() adds
         `vp_count`, `vp_status`, `vp_xyz`, `vp_pix`, `vp_src`, `vp_depth`, `vp_d2` (mask m owns rows [m K, m K + vp_count[m])) and, with
-        full=True, `hit_uvd`.  None: no buffer, no call.  Its parameters are untuned."""
+        full=True, `hit_uvd`.  None: no buffer, no call.  Its parameters are untuned.
+        owner: the point ownership (pointowner.PointOwner; nuScenes and Waymo batches, with any other option or none): directly behind the
+        compaction, in front of the ground strip, every point that several masks of a frame list gets one owner and every list keeps
+        the positions it owns (cm3d_point_owner, enqueued by cm3d_lift_pass_owned).  The strip, the clustering, the medoid, the yaw fit,
+        the vertical stage and the virtual points then read the exclusive lists: `medoid_pos` is a position in the lists the medoid
+        saw -- `cl_off`, else `gs_off`, else `ow_off` --, while `hit_off` / `hit_idx` / `hit_xyz` stay the raw lists.  download() adds
+        `ow_off`, `ow_status`, `ow_lost` (full=True: `ow_owner`, `ow_idx`, `ow_xyz`).  None: no buffer, no launch.  Its two parameters
+        (rule "score", min_keep 5) are untuned."""
         self.lib = _lib.lib()                      # raises when the extension is not built
         if not torch.cuda.is_available():
             raise Cm3dError("no HIP device: the lifting path only runs on the GPU (no CPU fallback)")
@@ -544,6 +552,10 @@ class LiftEngine:
         self.ground = ground if ground is not None and ground.active else None
         self.strip = strip if strip is not None and strip.active else None
         self.virtual = virtual if virtual is not None and virtual.active else None
+        self.owner = owner if owner is not None and owner.active else None
+        if self.owner is not None and self.obb:
+            raise ValueError("owner=PointOwner(...) is stated for nuScenes and Waymo batches; KITTI is out of its scope: it cannot be enabled "
+                             "with obb=True")
         if self.strip is not None and self.obb:
             raise ValueError("strip=GroundStrip(...) is stated for nuScenes and Waymo lists (z up); KITTI's rect frame has y down: it cannot be "
                              "enabled with obb=True")
@@ -701,6 +713,11 @@ class LiftEngine:
             b.grid_z = e(F, GRID_CELLS, dtype=torch.float64); b.grid_n = e(F, GRID_CELLS)
             b.gs_ws_bytes = int(L.cm3d_ground_strip_workspace_bytes(M, b.idx_cap))
             b.gs_ws = torch.empty(max(b.gs_ws_bytes, 16), dtype=torch.uint8, device=d)
+        if self.owner is not None:
+            b.ow_owner = e(b.idx_cap); b.ow_off = e(M + 1); b.ow_tile_off = e(M + 1); b.ow_status = e(M); b.ow_lost = e(M)
+            b.ow_idx = e(b.idx_cap); b.ow_xyz = e(b.idx_cap, 4, dtype=torch.float32)
+            b.ow_ws_bytes = int(L.cm3d_point_owner_workspace_bytes(F, b.max_pts, M, b.idx_cap))
+            b.ow_ws = torch.empty(max(b.ow_ws_bytes, 16), dtype=torch.uint8, device=d)
         if self.yaw is not None:
             b.fit_k = e(M); b.fit_status = e(M); b.fit_rect = e(M, _lib.MATCH_BOX_STRIDE, dtype=torch.float64)
             b.yaw_tab = e(M, 3, dtype=torch.float32); b.yaw_idx = e(M); b.yaw_src = e(M)
@@ -779,10 +796,14 @@ class LiftEngine:
             b.strip_desc = self._strip_descriptor(b)
             b.timed = {**{k: v for k, v in b.timed.items() if k == "filter"}, "strip": b.strip_desc,
                        **{k: v for k, v in b.timed.items() if k != "filter"}}
+        if self.owner is not None:             # (no member of the options either: cm3d_lift_pass_owned takes it; its events stand in front of the strip's)
+            b.owner_desc = self._owner_descriptor(b)
+            front = [k for k in b.timed if k == "filter"]
+            b.timed = {**{k: b.timed[k] for k in front}, "owner": b.owner_desc, **{k: v for k, v in b.timed.items() if k not in front}}
         if self.place is not None:             # (no member of the options: cm3d_lift_pass_placed takes it beside them; its events come last)
             b.place_desc = b.timed["place"] = self._place_descriptor(b)
         b.opts_ref = ctypes.byref(b.opts) if stages else None
-        b.plain_pass = not stages and self.velocity is None and self.vertical is None and self.ground is None and self.strip is None and self.virtual is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
+        b.plain_pass = not stages and self.velocity is None and self.vertical is None and self.ground is None and self.strip is None and self.virtual is None and self.owner is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
         self.b = b
         return b
 
@@ -839,15 +860,32 @@ class LiftEngine:
         s.min_points, s.min_keep = g.min_points, g.min_keep
         return s
 
+    def _owner_descriptor(self, b):
+        """cm3d_point_owner_desc of the resident batch (refresh_pass_descriptor sets its events)."""
+        w = _lib.PointOwnerDesc()
+        w.size = ctypes.sizeof(_lib.PointOwnerDesc)
+        for name in ("ow_owner", "ow_off", "ow_tile_off", "ow_idx", "ow_xyz", "ow_status", "ow_lost"):
+            setattr(w, name, _ptr(getattr(b, name)))
+        w.ws, w.ws_bytes = _ptr(b.ow_ws), b.ow_ws_bytes
+        w.rule, w.min_keep = self.owner.code, self.owner.min_keep
+        return w
+
     def read_lists(self, b=None):
         """The lists the stages behind the seam read, as (xyz, off) device tensors of the resident batch (or of `b`): the clustered ones
-        when the engine clusters, else the stripped ones when it strips, else the raw ones.  `medoid_pos` is a position in them."""
+        when the engine clusters, else the stripped ones when it strips, else the exclusive ones when it decides ownership, else the raw
+        ones.  `medoid_pos` is a position in them."""
+        return self._seen_lists(b)[:2]
+
+    def _seen_lists(self, b=None, behind=None):
+        """(xyz, off, idx) of the lists behind stage `behind` ("owner", "strip"; None: behind the clustering, the lists the medoid saw)."""
         b = self.b if b is None else b
-        if self.cluster is not None:
-            return b.cl_xyz, b.cl_off
-        if self.strip is not None:
-            return b.gs_xyz, b.gs_off
-        return b.hit_xyz, b.hit_off
+        if self.cluster is not None and behind is None:
+            return b.cl_xyz, b.cl_off, b.cl_idx
+        if self.strip is not None and behind != "owner":
+            return b.gs_xyz, b.gs_off, b.gs_idx
+        if self.owner is not None:
+            return b.ow_xyz, b.ow_off, b.ow_idx
+        return b.hit_xyz, b.hit_off, b.hit_idx
 
     def _yaw_descriptor(self, b):
         """cm3d_yaw_fit_desc of the resident batch (refresh_pass_descriptor sets its events).  The lists that are fitted are the clustered
@@ -856,7 +894,7 @@ class LiftEngine:
         y = _lib.YawFitDesc()
         y.size = ctypes.sizeof(_lib.YawFitDesc)
         y.angle_cs = _ptr(self.angle_cs)
-        if self.cluster is not None or self.strip is not None:
+        if self.cluster is not None or self.strip is not None or self.owner is not None:
             xyz, off = self.read_lists(b)
             y.hit_xyz, y.hit_off = _ptr(xyz), _ptr(off)
         if self.filters is not None:
@@ -1128,8 +1166,9 @@ class LiftEngine:
         """The depth clustering alone, on the raw lists the last pass left resident -- the stripped ones when the engine strips --
         (cm3d_depth_cluster: what the clustered pass enqueues between the compaction, or the strip, and the medoid)."""
         b, c = self.b, self.b.cluster_desc
-        if self.strip is not None:                       # (what the stripped pass clusters)
-            check(self.lib.cm3d_depth_cluster(_ptr(b.gs_xyz), _ptr(b.gs_idx), _ptr(b.gs_off), _ptr(b.mask_frame), b.M, b.idx_cap, c.origin, b.F,
+        if self.strip is not None or self.owner is not None:       # (what the stripped pass, or the owned pass, clusters)
+            xyz, off, idx = self._seen_lists(b, "strip")
+            check(self.lib.cm3d_depth_cluster(_ptr(xyz), _ptr(idx), _ptr(off), _ptr(b.mask_frame), b.M, b.idx_cap, c.origin, b.F,
                                               c.eps, c.min_points, c.pick, c.cl_off, c.cl_tile_off, c.cl_idx, c.cl_xyz, c.cl_status, c.ws,
                                               c.ws_bytes, st), "cm3d_depth_cluster")
             return
@@ -1146,9 +1185,18 @@ class LiftEngine:
                                         b.hb.raw_stride, _ptr(b.sweep_xf), _ptr(b.sweep_row_off), _ptr(b.frame_sweep_off), b.S, b.halfw, b.pt_cap,
                                         s.origin, b.F, s.cell, s.down, s.up, s.quantile, s.min_points, s.grid_z, s.grid_n, st),
               "cm3d_ground_grid")
-        check(self.lib.cm3d_ground_strip(_ptr(b.hit_xyz), _ptr(b.hit_idx), _ptr(b.hit_off), _ptr(b.mask_frame), b.M, b.idx_cap, s.origin,
+        xyz, off, idx = self._seen_lists(b, "owner")      # (the exclusive lists when the engine decides ownership, else the raw ones)
+        check(self.lib.cm3d_ground_strip(_ptr(xyz), _ptr(idx), _ptr(off), _ptr(b.mask_frame), b.M, b.idx_cap, s.origin,
                                          s.grid_z, b.F, s.cell, s.margin, s.min_keep, s.gs_off, s.gs_tile_off, s.gs_idx, s.gs_xyz, s.gs_status,
                                          s.gs_dropped, s.ws, s.ws_bytes, st), "cm3d_ground_strip")
+
+    def stage_point_owner(self, st):
+        """The point ownership alone, on the raw lists the last pass left resident (cm3d_point_owner: what the owned pass enqueues
+        between the compaction and the ground strip)."""
+        b, w = self.b, self.b.owner_desc
+        check(self.lib.cm3d_point_owner(_ptr(b.hit_xyz), _ptr(b.hit_idx), _ptr(b.hit_off), _ptr(b.mask_off), b.F, b.M, b.idx_cap, b.max_pts,
+                                        _ptr(b.score), w.rule, w.min_keep, w.ow_owner, w.ow_off, w.ow_tile_off, w.ow_idx, w.ow_xyz, w.ow_status,
+                                        w.ow_lost, w.ws, w.ws_bytes, st), "cm3d_point_owner")
 
     def stage_yaw_fit(self, st):
         """The yaw fit's three launches alone, on what the last pass left resident (cm3d_yaw_fit_boxes: cm3d_bev_fit, cm3d_yaw_select,
@@ -1252,12 +1300,12 @@ class LiftEngine:
         stage_events: optional list; gets five timing events appended -- before the point/mask stages, behind the compaction,
         the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them.
         Each opt-in stage the engine has appends two more behind those, in this order: around the filter launch (the "drivable"
-        bucket), around the ground strip's launches (the "strip" bucket; behind the second of the five, in front of the clustering's), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
+        bucket), around the point ownership's launches (the "owner" bucket; behind the second of the five, in front of the strip's), around the ground strip's launches (the "strip" bucket; behind the second of the five, in front of the clustering's), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
         the yaw fit's two launches (the "yawfit" bucket; behind the fifth event), around the placement's launch (the "place" bucket;
         behind the yaw fit's boxes), around the vertical stage's call (the "vertical" bucket; behind the pass), around the ground stage's
         call (the "ground" bucket; behind the vertical stage's), around the virtual points' call (the "virtual points" bucket; last of
         all, behind the velocity, track and size stages' calls, which have no events).  One library call enqueues
-        the pass, opt-in stages included (cm3d_lift_pass_opt, cm3d_lift_pass_placed with a placement, or cm3d_lift_pass_stripped with a ground strip; include/cm3d_hip.h states the
+        the pass, opt-in stages included (cm3d_lift_pass_opt, cm3d_lift_pass_placed with a placement, cm3d_lift_pass_stripped with a ground strip, or cm3d_lift_pass_owned with the point ownership; include/cm3d_hip.h states the
         order); no allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
@@ -1269,7 +1317,11 @@ class LiftEngine:
             stage_events.extend(marks + [ev for pair in omarks.values() for ev in pair])
         st = torch.cuda.current_stream(self.dev).cuda_stream
         desc = self.refresh_pass_descriptor(dense, project_events, marks, omarks)
-        if self.strip is not None:                       # the same pass, the strip in front of the clustering (and the placement as below)
+        if self.owner is not None:                       # the same pass, the ownership in front of the strip (and the placement as below)
+            check(self.lib.cm3d_lift_pass_owned(desc, self.b.opts_ref, ctypes.byref(self.b.place_desc) if self.place is not None else None,
+                                                ctypes.byref(self.b.strip_desc) if self.strip is not None else None,
+                                                ctypes.byref(self.b.owner_desc), st), "cm3d_lift_pass_owned")
+        elif self.strip is not None:                     # the same pass, the strip in front of the clustering (and the placement as below)
             check(self.lib.cm3d_lift_pass_stripped(desc, self.b.opts_ref, ctypes.byref(self.b.place_desc) if self.place is not None else None,
                                                    ctypes.byref(self.b.strip_desc), st), "cm3d_lift_pass_stripped")
         elif self.place is None:
@@ -1410,7 +1462,7 @@ class LiftEngine:
     def download(self, full=True):
         """Synchronises, checks the status word and returns numpy results.  full=False: only the per-mask results
         (boxes, flags, medoids, lane matches, list offsets) -- a few hundred KB.  `medoid_pos` is a position in the lists the medoid saw:
-        the clustered ones (`cl_off`) when the engine clusters, else the stripped ones (`gs_off`) when it strips, else the raw ones.  full=True adds the index lists
+        the clustered ones (`cl_off`) when the engine clusters, else the stripped ones (`gs_off`) when it strips, else the exclusive ones (`ow_off`) when it decides ownership, else the raw ones.  full=True adds the index lists
         (`hit_idx`, the reference's track_points), the coordinates of the listed points (`hit_xyz`), `pt_off` in the
         reference's form (the aggregated cloud without the ego-box rows, :445-465) and -- when the engine keeps the cloud
         (keep_cloud) -- `points` in that form too; on the device the cloud keeps the dropped rows as NaN placeholders."""
@@ -1426,6 +1478,8 @@ class LiftEngine:
                 out.update(cl_off=b.cl_off.cpu().numpy(), cl_status=b.cl_status.cpu().numpy())
             if self.strip is not None:
                 out.update(gs_off=b.gs_off.cpu().numpy(), gs_status=b.gs_status.cpu().numpy(), gs_dropped=b.gs_dropped.cpu().numpy())
+            if self.owner is not None:
+                out.update(ow_off=b.ow_off.cpu().numpy(), ow_status=b.ow_status.cpu().numpy(), ow_lost=b.ow_lost.cpu().numpy())
             if self.yaw is not None:
                 out.update(self._yaw_results())
             if self.velocity is not None:
@@ -1471,6 +1525,11 @@ class LiftEngine:
             out.update(gs_off=gs_off, gs_status=b.gs_status.cpu().numpy(), gs_dropped=b.gs_dropped.cpu().numpy(),
                        gs_idx=b.gs_idx[:n_gs].cpu().numpy(), gs_xyz=b.gs_xyz[:n_gs].cpu().numpy(), grid_z=b.grid_z.cpu().numpy(),
                        grid_n=b.grid_n.cpu().numpy())
+        if self.owner is not None:
+            ow_off = b.ow_off.cpu().numpy()
+            n_ow = int(ow_off[-1])
+            out.update(ow_off=ow_off, ow_status=b.ow_status.cpu().numpy(), ow_lost=b.ow_lost.cpu().numpy(),
+                       ow_owner=b.ow_owner[:n_idx].cpu().numpy(), ow_idx=b.ow_idx[:n_ow].cpu().numpy(), ow_xyz=b.ow_xyz[:n_ow].cpu().numpy())
         if self.yaw is not None:
             out.update(self._yaw_results())
         if self.velocity is not None:
@@ -1633,12 +1692,13 @@ class LiftPipeline:
         self.masks[slot] = masks
         return slot
 
-    def rerun(self, slot, masks=None, project_events=None):
-        """Another pass over the batch resident in `slot` (benchmarks)."""
+    def rerun(self, slot, masks=None, project_events=None, stage_events=None):
+        """Another pass over the batch resident in `slot` (benchmarks).  stage_events: as LiftEngine.run's; the pass then takes the
+        Python branch, which creates and appends them."""
         eng = self.engines[slot]
         mode = masks or self.masks[slot]
         self._pin_if_captured()
-        if eng._lane["built"] and eng.b.plain_pass:     # (cm3d_pipe_submit knows only the plain pass)
+        if eng._lane["built"] and eng.b.plain_pass and stage_events is None:     # (cm3d_pipe_submit knows only the plain pass)
             # (no stream context, no Python between the launches: what bench.py's headline times.  A pair of events around the
             # projection kernel rides along, so that a timed pass costs the host what an untimed one does)
             rc = self.lib.cm3d_pipe_submit(self._h, slot, eng.refresh_pass_descriptor(eng.resident_masks(mode), project_events))
@@ -1648,7 +1708,7 @@ class LiftPipeline:
             st = self.exec_stream(self._acquire(slot))
             try:
                 with torch.cuda.stream(st):
-                    eng.run(masks=mode, project_events=project_events)
+                    eng.run(masks=mode, project_events=project_events, stage_events=stage_events)
             finally:
                 self.lib.cm3d_pipe_release(self._h, slot)
         self.native_passes += 1
@@ -1716,9 +1776,26 @@ def virtual_point_frames(eng):
     b = eng.b
     res = eng._virtual_results()
     off = eng.read_lists()[1].cpu().numpy()
-    idx = (b.cl_idx if eng.cluster is not None else b.gs_idx if eng.strip is not None else b.hit_idx)[:max(0, min(int(off[-1]), b.idx_cap))]
+    idx = eng._seen_lists()[2][:max(0, min(int(off[-1]), b.idx_cap))]
     idx, hb = idx.cpu().numpy(), b.hb
     return [vpmod.frame_records(res, f, eng.virtual.per_mask, hb.mask_off, hb.mask_cam, hb.class_id, hb.score, off, idx) for f in range(b.F)]
+
+
+def point_label_frames(eng):
+    """The painted cloud of the batch resident in `eng` (an engine with PointOwner(...), its pass and every stage behind it finished),
+    frame by frame: a list of F entries, each the dict pointowner.label_rows makes -- idx, xyz, mask, cam, class_id, score, kept, claims,
+    one row per listed point of the frame -- or None for a frame without a listed point.  From `ow_owner` and the raw lists, on the host."""
+    from . import pointowner as pomod
+    b = eng.b
+    hb = b.hb
+    off = b.hit_off.cpu().numpy()
+    n = max(0, min(int(off[-1]), b.idx_cap))
+    idx, xyz, own, flags = b.hit_idx[:n].cpu().numpy(), b.hit_xyz[:n].cpu().numpy(), b.ow_owner[:n].cpu().numpy(), b.flags.cpu().numpy()
+    out = []
+    for f in range(b.F):
+        rows = pomod.label_rows(f, idx, xyz, off, hb.mask_off, own, hb.mask_cam, hb.class_id, hb.score, flags, b.max_pts)
+        out.append(rows if len(rows["idx"]) else None)
+    return out
 
 
 def kept_box_sizes(b):

@@ -823,6 +823,43 @@ def ground_strip(hit_xyz, hit_off, mask_frame, origin, grid_z, hit_idx=None, cel
                 gs_xyz=gs_xyz.cpu().numpy()[:k], gs_idx=None if gs_idx is None else gs_idx.cpu().numpy()[:k])
 
 
+def point_owner(hit_xyz, hit_idx, hit_off, mask_off, score, max_pts_per_frame, rule="score", min_keep=5, idx_cap=None):
+    """One owner per contested point on arrays (cm3d_point_owner; pointowner.point_owner_host states it).  hit_xyz (n, 3 or 4) float32,
+    hit_idx (n,), hit_off (M + 1,), mask_off (F + 1,), score (M,); rule "score" / "smallest" (or 0 / 1).  idx_cap: the capacity the
+    call is told (default: the number of positions).  Returns a dict of numpy arrays: ow_owner (the clamped end of the last list,),
+    ow_off, ow_tile_off, ow_status, ow_lost, ow_xyz (ow_off[-1], 4), ow_idx.  The defaults are untuned."""
+    from .pointowner import rule_code
+    L = _lib.lib()
+    p = np.asarray(hit_xyz, np.float32)
+    p = p.reshape(-1, p.shape[-1] if p.ndim > 1 else 4)
+    tot = p.shape[0]
+    cap = max(tot, 1) if idx_cap is None else int(idx_cap)
+    P4 = np.zeros((max(tot, cap, 1), 4), np.float32)
+    P4[:tot, :min(p.shape[1], 4)] = p[:, :4]
+    hit_off = np.ascontiguousarray(hit_off, np.int32).reshape(-1)
+    mask_off = np.ascontiguousarray(mask_off, np.int32).reshape(-1)
+    M, F, P = hit_off.size - 1, mask_off.size - 1, int(max_pts_per_frame)
+    idx = np.zeros(P4.shape[0], np.int32)
+    idx[:tot] = np.asarray(hit_idx, np.int32)
+    n = max(M, 1)
+    d_xyz, d_idx, d_off, d_mo = _t(P4), _t(idx), _t(hit_off), _t(mask_off)
+    d_sc = _t(np.asarray(score, np.float64).reshape(M) if M else np.zeros(1))
+    ow_owner, ow_off, ow_tile, ow_st, ow_lost = _e(P4.shape[0]), _e(n + 1), _e(n + 1), _e(n), _e(n)
+    ow_idx, ow_xyz = _e(P4.shape[0]), _e(P4.shape[0], 4, dtype=torch.float32)
+    ws = _ws(L.cm3d_point_owner_workspace_bytes(F, P, M, cap))
+    check(L.cm3d_point_owner(d_xyz.data_ptr(), d_idx.data_ptr(), d_off.data_ptr(), d_mo.data_ptr(), F, M, cap, P, d_sc.data_ptr(),
+                             rule_code(rule), int(min_keep), ow_owner.data_ptr(), ow_off.data_ptr(), ow_tile.data_ptr(), ow_idx.data_ptr(),
+                             ow_xyz.data_ptr(), ow_st.data_ptr(), ow_lost.data_ptr(), ws.data_ptr(), ws.numel(), _st()), "cm3d_point_owner")
+    if M == 0:
+        return dict(ow_owner=np.zeros(0, np.int32), ow_off=np.zeros(1, np.int32), ow_tile_off=np.zeros(1, np.int32),
+                    ow_status=np.zeros(0, np.int32), ow_lost=np.zeros(0, np.int32), ow_xyz=np.zeros((0, 4), np.float32),
+                    ow_idx=np.zeros(0, np.int32))
+    off = ow_off.cpu().numpy()
+    k, end = int(off[-1]), min(max(int(hit_off[-1]), 0), cap)
+    return dict(ow_owner=ow_owner.cpu().numpy()[:end], ow_off=off, ow_tile_off=ow_tile.cpu().numpy(), ow_status=ow_st.cpu().numpy(),
+                ow_lost=ow_lost.cpu().numpy(), ow_xyz=ow_xyz.cpu().numpy()[:k], ow_idx=ow_idx.cpu().numpy()[:k])
+
+
 # ----------------------------------------------------------------------------- f4: SAM3D fusion matching
 def match_records(boxes7):
     """(n,7) [center_x, center_y, bottom_z, length, width, height, heading] -> (n,6) float64 records of

@@ -29,6 +29,7 @@ from . import boxsize as szmod
 from . import boxvertical as vtmod
 from . import boxground as grmod
 from . import groundstrip as gsmod
+from . import pointowner as pomod
 from . import virtualpoints as vpmod
 
 # module constants of the reference (:55-59)
@@ -231,7 +232,7 @@ def _token_batches(batches, index, host_s):
 
 def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
                   velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None, strip=None,
-                  virtual=None):
+                  virtual=None, owner=None, labels=None):
     """The submit / drain loop of both routes.  prepared yields (HostBatch, frame ids (F, 2), seconds the host spent preparing it); two
     batches are in flight on the GPU: batch i+1 is uploaded while batch i runs.  Returns the kept-box records of all batches as ONE
     device tensor (lifting.kept_box_records).  Per-stage GPU times go into `timer` under the reference's bucket names.
@@ -259,7 +260,10 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
     they were in form: nothing else changes here.  virtual: the opt-in virtual points (virtualpoints.FrameFiles; with any option or none),
     one call behind everything else; its two events come last of all, and the time between them goes into a "virtual points" bucket.  Every
     frame's seed word is its index in the output order, and every finished batch's frames with a point are written to their files here:
-    the records are untouched."""
+    the records are untouched.  owner: the opt-in point ownership (pointowner.PointOwner; with any option or none), inside the pass
+    between the compaction and the strip; its two events come behind the filter's and in front of the strip's, inside the "medoid" span,
+    and the time between them goes into an "owner" bucket instead.  labels: with `owner`, the virtualpoints.FrameFiles that names the
+    job's frames under --point-labels' directory: every finished batch's frames with a listed point are written to their files here."""
     sized = size is not None or vertical is not None or ground is not None      # the records travel with (k, 3) size rows
     kw = {} if yaw is None else {"yaw": yaw}
     if place is not None:
@@ -278,11 +282,14 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
         kw["strip"] = strip
     if virtual is not None:
         kw["virtual"] = virtual.stage
+    if owner is not None:
+        kw["owner"] = owner
     vels, sizes = [], []
     pipe = lifting.LiftPipeline(device, depth=2, classes=classes, filters=filters, cluster=cluster, nms=nms, **kw)
     n_f, n_c, n_y = (2 if filters is not None and filters.active else 0), (2 if cluster is not None else 0), (2 if yaw is not None else 0)
     n_p, n_v, n_g = (2 if place is not None else 0), (2 if vertical is not None else 0), (2 if ground is not None else 0)
-    n_s, n_vp = (2 if strip is not None else 0), (2 if virtual is not None else 0)
+    n_s, n_vp, n_o = (2 if strip is not None else 0), (2 if virtual is not None else 0), (2 if owner is not None else 0)
+    n_f, n_own = n_f + n_o, n_f                                        # (the ownership's pair stands directly behind the filter's, at 5 + n_own)
     n_evs = 5 + n_f + n_s + n_c + n_y + n_p + n_v + n_g + n_vp
     records, pending, segments = [], [], []                            # pending: (slot, frame ids, stage events) in flight, oldest first
 
@@ -303,6 +310,10 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
                 t1 = time.time()
                 virtual.write_batch(lifting.virtual_point_frames(pipe.engines[slot]), ids[:, 0])
                 spent("write", t1)
+            if labels is not None and owner is not None:               # this batch's painted cloud; every rank writes its own frames'
+                t1 = time.time()
+                pomod.write_batch(labels, lifting.point_label_frames(pipe.engines[slot]), ids[:, 0])
+                spent("write", t1)
             if on_records is not None:
                 first = int(ids[0, 0]) if len(ids) else 0
                 extra = () if velocity is None else (vels[-1].cpu().numpy(),)
@@ -318,7 +329,11 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
                     spans.append(("drivable", 5, 6))
                 for key, a, b in spans:
                     timer[key] = timer.get(key, 0.0) + evs[a].elapsed_time(evs[b]) * 1e-3
-                if strip is not None:                                  # the two events behind the filter's, inside the "medoid" span
+                if owner is not None:                                  # the two events behind the filter's, inside the "medoid" span
+                    dt = evs[5 + n_own].elapsed_time(evs[6 + n_own]) * 1e-3
+                    timer["owner"] = timer.get("owner", 0.0) + dt
+                    timer["medoid"] -= dt
+                if strip is not None:                                  # the two events behind the filter's (and the ownership's), inside the "medoid" span
                     dt = evs[5 + n_f].elapsed_time(evs[6 + n_f]) * 1e-3
                     timer["strip"] = timer.get("strip", 0.0) + dt
                     timer["medoid"] -= dt
@@ -373,7 +388,7 @@ def _lift_batches(prepared, device, classes, masks, timer, on_records=None, filt
 def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                 scenes_per_batch=4, missing_ok=False, workers=0, priors=None, token_index=None, reader_threads=-1, filters=None,
                 cluster=None, nms=None, yaw=None, velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None,
-                vertical=None, ground=None, strip=None, virtual=None):
+                vertical=None, ground=None, strip=None, virtual=None, owner=None, labels=None):
     """Runs the hot path over the given scenes; returns the kept-box records of all their frames as ONE device tensor
     (lifting.kept_box_records; column 5 = token_index[sample token], default: the index into sample_tokens(scene_names)).
     workers > 0: that many reader processes prepare the batches (prepare_scene_batch: file reads, RLE strings,
@@ -408,7 +423,7 @@ def lift_scenes(tables, scene_names, mask_dir, classes, device, n_sweeps=3, rati
     with contextlib.closing(prepared()) as batches:
         return _lift_batches(batches, device, classes, masks, timer, filters=filters, cluster=cluster, nms=nms, yaw=yaw, velocity=velocity,
                              vel_out=vel_out, tracks=tracks, place=place, size=size, size_out=size_out, vertical=vertical, ground=ground,
-                             strip=strip, virtual=virtual)
+                             strip=strip, virtual=virtual, owner=owner, labels=labels)
 
 
 def _native_batch_lanes(nt, names, lane_cache):
@@ -487,7 +502,7 @@ def _native_batch_tail(nt, head, sub=None, rd=None, drivable=False):
 def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n_sweeps=3, ratio=0.64, masks="rle", timer=None,
                        scenes_per_batch=4, missing_ok=False, python_batch=None, on_records=None, filters=None, cluster=None, nms=None, yaw=None,
                        velocity=None, vel_out=None, tracks=None, place=None, size=None, size_out=None, vertical=None, ground=None, strip=None,
-                       virtual=None):
+                       virtual=None, owner=None, labels=None):
     """lift_scenes with the whole host side in libcm3d_reader.so (reader.Tables): per batch one native table walk, one native read
     of all its files, one upload, one pass.  Three host threads in a row -- the reads of batch k+1 run under the upload and the
     launches of batch k -- and two batches in flight on the GPU.  row_to_out: row in sample.json -> index of the sample in the
@@ -531,7 +546,7 @@ def lift_scenes_native(nt, scene_names, mask_dir, classes, device, row_to_out, n
                 yield hb, np.stack([row_to_out[rows].astype(np.float64), np.zeros(len(rows))], 1), io_s
     try:
         return _lift_batches(prepared(), device, classes, masks, timer, on_records, filters, cluster, nms, yaw, velocity, vel_out, tracks, place,
-                             size, size_out, vertical, ground, strip, virtual)
+                             size, size_out, vertical, ground, strip, virtual, owner=owner, labels=labels)
     finally:
         lane_pool.shutdown(wait=False)
 
@@ -573,6 +588,7 @@ def main(argv=None):
     grmod.add_arguments(ap)
     gsmod.add_arguments(ap)
     vpmod.add_arguments(ap)
+    pomod.add_arguments(ap)
     args = ap.parse_args(argv)
     cluster = clmod.from_namespace(args)
     nms = nmsmod.from_args(args)
@@ -585,6 +601,7 @@ def main(argv=None):
     ground = grmod.from_args(args, ap)              # (a --ground-* flag without --ground fit: the same)
     strip = gsmod.from_namespace(args, ap)          # (a --ground-strip-* flag without --ground-strip grid: the same)
     vp_stage = vpmod.from_args(args, ap)            # (a --virtual-points-* flag without --virtual-points DIR: the same)
+    owner = pomod.from_namespace(args, ap)          # (--point-owner-min-keep or --point-labels without --point-owner: the same)
     sized = size is not None or vertical is not None or ground is not None
     size_mine = []                                 # with --size track, --vertical fit or --ground fit: the sizes of this rank's records, one device tensor
     vel_mine = []                                  # with --velocity track: the velocities of this rank's records, one device tensor
@@ -624,6 +641,7 @@ def main(argv=None):
     if native:
         tokens, rows = nt.job_tokens(names)                    # the whole job's samples, identical on every rank
         virtual = None if vp_stage is None else vpmod.FrameFiles(vp_stage, args.virtual_points, list(tokens))
+        labels = None if args.point_labels is None else vpmod.FrameFiles(None, args.point_labels, list(tokens))
         row_to_out = np.full(int(rows.max()) + 1 if len(rows) else 1, -1, np.int64)
         row_to_out[rows] = np.arange(len(rows))
 
@@ -664,18 +682,19 @@ def main(argv=None):
                                   scenes_per_batch=max(1, args.scenes_per_batch), missing_ok=args.missing_ok, python_batch=python_batch,
                                   on_records=on_records if world == 1 else None, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
                                   velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine,
-                                  vertical=vertical, ground=ground, strip=strip, virtual=virtual)
+                                  vertical=vertical, ground=ground, strip=strip, virtual=virtual, owner=owner, labels=labels)
         write_q.put(None)
         writer.join()
         streamed[0] = streamed[0] and next_first[0] == len(tokens)
     else:
         tokens = sample_tokens(tables, names)                  # the whole job's samples, identical on every rank
         virtual = None if vp_stage is None else vpmod.FrameFiles(vp_stage, args.virtual_points, list(tokens))
+        labels = None if args.point_labels is None else vpmod.FrameFiles(None, args.point_labels, list(tokens))
         mine = lift_scenes(tables, names[lo:hi], args.mask_dir, classes, device, args.n_sweeps, args.ratio, args.masks, timer,
                            missing_ok=args.missing_ok, workers=args.workers, priors=priors, scenes_per_batch=max(1, args.scenes_per_batch),
                            token_index={t: i for i, t in enumerate(tokens)}, reader_threads=args.reader_threads, filters=filters, cluster=cluster, nms=nms, yaw=yaw,
                            velocity=velocity, vel_out=vel_mine, tracks=tracks, place=place, size=size, size_out=size_mine, vertical=vertical, ground=ground,
-                           strip=strip, virtual=virtual)
+                           strip=strip, virtual=virtual, owner=owner, labels=labels)
 
     # the single exchange of the job: fixed-size box records -> rank 0 (one RCCL all_gather of payload; also the path of a
     # one-rank run).  Ranks hold contiguous scene blocks, so rank order is sample order.

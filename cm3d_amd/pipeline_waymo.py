@@ -32,6 +32,7 @@ from . import boxplace
 from . import boxvertical as vtmod
 from . import boxground as grmod
 from . import groundstrip as gsmod
+from . import pointowner as pomod
 from . import virtualpoints as vpmod
 from . import dist as cdist
 from . import lifting
@@ -78,13 +79,15 @@ def load_scene(frames_dir, mask_dir, scene, tfrecord=None):
     return frames, lane_table
 
 
-def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0, heights=None, virtual_dir=None):
+def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0, heights=None, virtual_dir=None, labels_dir=None):
     """One scene through the hot path, its frames in one batch; returns its kept-box records as a list of device tensors
     (lifting.kept_box_records with column 5 = scene_index, column 6 = the frame's number inside the scene).  Masks of different image
     sizes -- Waymo's side cameras, inside every frame -- share the batch (lifting.pack_frames).  heights: a list that, with an engine
     whose vertical or ground stage is on, gets the (k,) heights of the returned records appended (column 2 of lifting.kept_box_sizes).
     virtual_dir: with an engine whose virtual points are on, the directory that gets <frame file's stem>.npz of every frame with a point
-    (virtualpoints.write_frame); a frame's seed word is scene_index * 65536 + its number in the scene, the same however the job is cut."""
+    (virtualpoints.write_frame); a frame's seed word is scene_index * 65536 + its number in the scene, the same however the job is cut.
+    labels_dir: with an engine whose point ownership is on, the directory that gets the painted cloud of every frame with a listed point
+    (pointowner.write_frame), named as the virtual points' files are."""
     hb = lifting.pack_frames(frames, [lane_table], [0] * len(frames), classes)
     if masks == "dense":
         lifting.require_one_mask_size(hb)
@@ -98,10 +101,13 @@ def lift_scene(eng, frames, lane_table, classes, masks="rle", scene_index=0, hei
     torch.cuda.synchronize()
     eng.check_status()
     ids = np.array([[scene_index, k] for k in numbers], np.float64)
+    stems = [f"{k}_frame" for k in numbers]              # the frame files' stems: both products name their files by them
     if eng.virtual is not None and virtual_dir is not None:
-        for rec, k in zip(lifting.virtual_point_frames(eng), numbers):
+        for rec, stem in zip(lifting.virtual_point_frames(eng), stems):
             if rec is not None:
-                vpmod.write_frame(virtual_dir, f"{k}_frame", rec)
+                vpmod.write_frame(virtual_dir, stem, rec)
+    if eng.owner is not None and labels_dir is not None:
+        pomod.write_batch(vpmod.FrameFiles(None, labels_dir, stems), lifting.point_label_frames(eng), range(len(stems)))
     if heights is not None and (eng.vertical is not None or eng.ground is not None):
         heights.append(lifting.kept_box_sizes(eng.b)[:, 2:3].contiguous())
     return [lifting.kept_box_records(eng.b, ids)]
@@ -158,12 +164,14 @@ def main(argv=None):
     grmod.add_arguments(ap)
     gsmod.add_arguments(ap)
     vpmod.add_arguments(ap)
+    pomod.add_arguments(ap)
     args = ap.parse_args(argv)
     place = boxplace.from_namespace(args, ap)       # (--place fit without --yaw fit: an error of the command line)
     vertical = vtmod.from_args(args, ap)            # (a --vertical-* flag without --vertical fit: the same)
     ground = grmod.from_args(args, ap)              # (a --ground-* flag without --ground fit: the same)
     strip = gsmod.from_namespace(args, ap)          # (a --ground-strip-* flag without --ground-strip grid: the same)
     virtual = vpmod.from_args(args, ap)             # (a --virtual-points-* flag without --virtual-points DIR: the same)
+    owner = pomod.from_namespace(args, ap)          # (--point-owner-min-keep or --point-labels without --point-owner: the same)
     filters = lifting.Stage2Filters.from_args(False, args.lane_max_dist, args.vehicle_lane_max_dist)
     t0 = time.time()
     rank, world, local_rank = cdist.init_from_env()
@@ -176,7 +184,7 @@ def main(argv=None):
     classes = lifting.ClassTable.waymo(pri)
     eng = lifting.LiftEngine(f"cuda:{local_rank}", classes=classes, filters=filters, cluster=clmod.from_namespace(args),
                              nms=nmsmod.from_args(args), yaw=bevfit.from_namespace(args), place=place,
-                             vertical=vertical, ground=ground, strip=strip, virtual=virtual)
+                             vertical=vertical, ground=ground, strip=strip, virtual=virtual, owner=owner)
     lo, hi = cdist.shard_range(len(scenes), rank, world)
     mine, meta, heights = [], {}, []
     for si in range(lo, hi):
@@ -187,7 +195,8 @@ def main(argv=None):
             if lanes is None:
                 raise FileNotFoundError(f"{scenes[si]}: no lane polylines (frame 0)")
             mine.extend(lift_scene(eng, frames, lanes, classes, args.masks, scene_index=si, heights=heights,
-                                   virtual_dir=None if virtual is None else os.path.join(args.virtual_points, scenes[si])))
+                                   virtual_dir=None if virtual is None else os.path.join(args.virtual_points, scenes[si]),
+                                   labels_dir=None if args.point_labels is None else os.path.join(args.point_labels, scenes[si])))
     rec = torch.cat(mine, 0) if mine else torch.zeros(0, 10, dtype=torch.float64, device=eng.dev)
     # the single exchange of the job: fixed-size box records -> rank 0 (also the path of a one-rank run)
     gathered = cdist.gather_records(rec, dst=0)

@@ -1468,6 +1468,86 @@ int cm3d_virtual_points(const uint32_t *packed, const int32_t *bbox, int32_t W, 
                         int32_t *vp_count, int32_t *vp_status, double *vp_xyz, int32_t *vp_pix, int32_t *vp_src, float *vp_depth,
                         float *vp_d2, cm3d_stream_t stream);
 
+/* ---- opt-in: one owner per contested point, exclusive in-mask lists (csrc/pointowner.hip) ----------------------
+ * Added within ABI v5: new symbols only, so CM3D_ABI_VERSION stays.  Every stage behind the compaction assumes that an in-mask list
+ * holds the points of its own object, and nothing makes that true where masks overlap: the 2D NMS is per class, a pedestrian's mask
+ * lies inside the mask of the bus behind them, adjacent cameras see one object twice.  Here every point that several masks of a frame
+ * list gets one owner, and every list keeps the positions it owns, between the compaction and the ground strip: everything behind
+ * reads the exclusive lists.  ow_owner is also the table of a painted cloud (one instance per LiDAR point).  The reference has
+ * nothing of the kind.  The defaults rule = 0 (score), MIN_KEEP = 5 are UNTUNED, both, and what the stage does to label quality has
+ * not been measured (it cannot be on synthetic scenes).  Host statement to the bit: cm3d_amd.pointowner.point_owner_host.
+ * F = n_frames, M = n_masks, P = max_pts_per_frame.
+ *
+ *  Lists.      The masks of frame f are [mask_off[f], mask_off[f+1]) (mask_off ascends from 0 to M; every value is clamped into [0, M]
+ *              before it is used, and a mask that no frame holds contests nothing: it owns all its positions).  The raw list of mask m
+ *              is positions lo_m .. hi_m of hit_idx / hit_xyz, the offsets clamped into [0, idx_cap] exactly as cm3d_depth_cluster
+ *              clamps them (hit_off ascends; lists that share positions are not an input); n_m = hi_m - lo_m.  s_m = score[m]
+ *              (double).  A NaN score is lower than every number, and two NaNs are equal.
+ *  Beats.      For two different masks a, b of one frame:
+ *                rule 0 (score):    a beats b iff s_a > s_b; or equal and n_a < n_b; or both equal and a < b
+ *                rule 1 (smallest): a beats b iff n_a < n_b; or equal and s_a > s_b; or both equal and a < b
+ *              Both are strict total orders within a frame.
+ *  Owner.      Position i of mask m (frame f) holds point p = hit_idx[i].  If 0 <= p < P its claimants are the masks of frame f whose
+ *              list holds p, and the owner is the claimant that beats all the others.  If p is outside [0, P) the owner is m.  Masks
+ *              of different frames never contest.  ow_owner int32[idx_cap] = the owner's batch mask index at every position of every
+ *              list; positions beyond the clamped end of the last list are not written.
+ *  Result.     kept_m = the number of positions of m whose owner is m:
+ *                ow_status 2: empty list, empty result, ow_lost 0
+ *                ow_status 1: kept_m < MIN_KEEP: the list is kept whole, ow_lost 0 (ow_owner still names the owners)
+ *                ow_status 0: the positions the list owns, in its own order, ow_lost = n_m - kept_m (which may be 0)
+ *              A non-empty list never becomes empty, so the set of masks with a box cannot change.
+ *  ow_off, ow_tile_off int32[M+1], ow_idx int32[idx_cap], ow_xyz float[idx_cap][4], ow_status int32[M]: the formats of
+ *              cm3d_depth_cluster's cl_off, cl_tile_off, cl_idx, cl_xyz, cl_status;  ow_lost int32[M].
+ *  workspace   cm3d_point_owner_workspace_bytes(F, P, M, idx_cap) = 16 M + 4 F P + idx_cap bytes, 4-byte aligned (the kept counts,
+ *              the ranks, the frames and the masks by rank; the owner table int32[F][P]; one keep byte per position).  Nothing
+ *              depends on what it held before the call.
+ *
+ *  cm3d_point_owner_check: CM3D_OK iff rule is 0 or 1 and MIN_KEEP >= 1; anything else is CM3D_ERR_ARG.  cm3d_point_owner applies it
+ *  before any launch; CM3D_ERR_ARG before any launch as well: a negative count, idx_cap <= 0, a NULL hit_idx (the stage cannot do
+ *  without it), with M > 0 a NULL array, hit_xyz or ow_xyz not 16-byte aligned; a workspace too small is CM3D_ERR_WORKSPACE.  M == 0:
+ *  CM3D_OK, nothing launched, nothing written.
+ *  Six launches: k_owner_rank, one thread per mask (its frame by a search of mask_off; its rank = the number of the frame's masks it
+ *  beats, and the inverse table); k_owner_claim twice, one workgroup per mask: first 0 into the table entry of every listed point --
+ *  only entries that are read are cleared, not the 4 F P bytes of the table --, then an integer maximum of rank + 1 on it (a maximum
+ *  does not depend on the order of arrival); k_owner_resolve, one workgroup per mask (entry -> owner, ow_owner, keep bytes, the count,
+ *  the MIN_KEEP rule); then the scan and the stable compaction cm3d_depth_cluster uses (csrc/list_compact.h).  No position >= idx_cap
+ *  and no table entry outside [0, F P) is read or written whatever hit_off and hit_idx hold.  Integer atomics only, no float atomic,
+ *  no allocation, no read-back: every run gives the same bytes, and the call can be captured in a graph. */
+int cm3d_point_owner_check(int32_t rule, int32_t min_keep);
+int64_t cm3d_point_owner_workspace_bytes(int32_t n_frames, int32_t max_pts_per_frame, int32_t n_masks, int32_t idx_cap);
+int cm3d_point_owner(const float *hit_xyz, const int32_t *hit_idx, const int32_t *hit_off, const int32_t *mask_off, int32_t n_frames,
+                     int32_t n_masks, int32_t idx_cap, int32_t max_pts_per_frame, const double *score, int32_t rule, int32_t min_keep,
+                     int32_t *ow_owner, int32_t *ow_off, int32_t *ow_tile_off, int32_t *ow_idx, float *ow_xyz, int32_t *ow_status,
+                     int32_t *ow_lost, void *workspace, int64_t workspace_bytes, cm3d_stream_t stream);
+
+/* What the owned pass needs beyond cm3d_lift_pass_desc.  `size` is sizeof(cm3d_point_owner_desc) (another value: CM3D_ERR_ARG); the
+ * other fields as in cm3d_point_owner. */
+typedef struct cm3d_point_owner_desc {
+    int64_t size;
+    int32_t *ow_owner; int32_t *ow_off; int32_t *ow_tile_off; int32_t *ow_idx; float *ow_xyz; int32_t *ow_status; int32_t *ow_lost;
+    void *ws; int64_t ws_bytes;
+    void *ev[2];                 /* optional hipEvent_t, recorded in front of and behind cm3d_point_owner */
+    int32_t rule, min_keep;
+} cm3d_point_owner_desc;
+
+/* The composed pass with the point ownership (host code, csrc/pass_owner.cpp; behind the ownership and the strip it enters
+ * csrc/pass_options.cpp on the lists that are left.  cm3d_lift_pass_opt, _placed and _stripped do not know the stage).  Enqueues on
+ * `stream`, stopping at and returning the first error; no descriptor of the caller's is written.  opt, place and strip may be NULL; a
+ * NULL owner is CM3D_ERR_ARG: it does not fall back to another pass.
+ *
+ *   every descriptor is checked first, CM3D_ERR_ARG and NO call at all: desc (with hit_idx), opt and its members as in
+ *   cm3d_lift_pass_opt; place as in cm3d_lift_pass_placed; strip as in cm3d_lift_pass_stripped; owner's size, its arrays, its workspace
+ *   pointer and cm3d_point_owner_check of its parameters; yaw's hit_xyz, hit_off, medoid_pos each NULL or what is derived below
+ *   cm3d_lift_pass_head(desc)
+ *   record owner->ev[0]; cm3d_point_owner (desc's lists, mask_off, score -> the ow_* arrays); record owner->ev[1]
+ *   strip   ?  record strip->ev[0]; cm3d_ground_grid; cm3d_ground_strip (the ow_* lists -> the gs_* arrays); record strip->ev[1]
+ *   cluster ?  cm3d_depth_cluster (the gs_* lists, else the ow_* lists -> the cl_* arrays), between its events
+ *   cm3d_lift_pass_tail(desc')            desc' = desc with the cl_* arrays, else the gs_* arrays, else the ow_* arrays; tile_work = NULL
+ *   filter, yaw, place, nms               as in cm3d_lift_pass_stripped; the yaw fit reads the lists the medoid saw
+ *   medoid_pos is then a position in the lists the medoid saw: cl_*, else gs_*, else ow_*. */
+int cm3d_lift_pass_owned(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, const cm3d_box_place_desc *place,
+                         const cm3d_ground_strip_desc *strip, const cm3d_point_owner_desc *owner, cm3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
