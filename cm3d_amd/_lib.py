@@ -150,6 +150,7 @@ SIGNATURES = {
     "cm3d_point_owner_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "cm3d_point_owner": (_i32, [_p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _i32, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _p]),
     "cm3d_lift_pass_owned": (_i32, [_p, _p, _p, _p, _p, _p]),
+    "cm3d_lift_pass_composed": (_i32, [_p, _p, _p, _p, _p, _p]),
 }
 
 POLY_INDEX_ARRAYS = ("tab_y", "tab_slab", "slab_off", "ent_edge", "ent_ring", "edge", "ring_info")     # cm3d_points_in_polygons, in order

@@ -1,21 +1,10 @@
 // Host side of the opt-in stages of a pass (cm3d_lift_pass_opt, include/cm3d_hip.h): the depth clustering between the halves of the
 // plain pass, and behind it the stage-2 filter, the yaw fit and the rotated-box NMS.  The only statement of a composed pass's order
-// (csrc/pass_strip.cpp enters it behind the seam, on the stripped lists, through cm3d_pass_seam_run below).  No
+// (the composer of the stages in front of the clustering enters it behind the seam, on the lists those leave, through cm3d_pass_seam_run
+// below; record() and bound() come from csrc/pass_seam.h).  No
 // kernel lives here, and csrc/pipeline.cpp knows nothing of this file: the plain pass and cm3d_pipe_submit stay what they are.
-#include <hip/hip_runtime_api.h>
-
 #include "../../include/cm3d_hip.h"
 #include "pass_seam.h"
-
-static int record(void *ev, cm3d_stream_t st)
-{
-    return !ev || hipEventRecord((hipEvent_t)ev, (hipStream_t)st) == hipSuccess ? CM3D_OK : CM3D_ERR_LAUNCH;
-}
-
-static int32_t bound(const cm3d_lift_pass_desc *d)          // no frame has more than 32 * planes masks
-{
-    return d->planes > 0 && d->planes < CM3D_MAX_MASKS_PER_FRAME / 32 ? 32 * d->planes : CM3D_MAX_MASKS_PER_FRAME;
-}
 
 // the box launch of the plain pass once more, on other positions or other lane tables: `box` and `flags` are written whole, so nothing
 // of an earlier launch remains
@@ -65,7 +54,7 @@ extern "C" int cm3d_yaw_fit_boxes(const cm3d_lift_pass_desc *d, const cm3d_yaw_f
 
 // A composed pass behind the seam, on the lists of `l`: `d` itself (nothing has been enqueued yet: the head runs here), or a copy of `d`
 // with other lists in hit_off, tile_off, hit_idx, hit_xyz and no tile_work (the head has run and something stands between it and the
-// clustering: csrc/pass_strip.cpp).  Every descriptor has been checked.
+// clustering).  Every descriptor has been checked.
 static int behind(const cm3d_lift_pass_desc *d, const cm3d_lift_pass_desc *l, const cm3d_depth_cluster_desc *c, const cm3d_stage2_filter_desc *f,
                   const cm3d_yaw_fit_desc *y, const cm3d_rotated_nms_desc *n, cm3d_stream_t st)
 {
@@ -127,7 +116,7 @@ extern "C" int cm3d_lift_pass_opt(const cm3d_lift_pass_desc *d, const cm3d_lift_
     return behind(d, d, o->cluster, o->filter, o->yaw, o->nms, st);
 }
 
-// The seam for csrc/pass_strip.cpp (declared in csrc/pass_seam.h, no part of include/cm3d_hip.h): the check of a composed pass's
+// The seam for the composer (declared in csrc/pass_seam.h, no part of include/cm3d_hip.h): the check of a composed pass's
 // descriptors for the lists of `l`, and the pass behind the seam on them (opt may be NULL: the tail alone).
 extern "C" int cm3d_pass_seam_check(const cm3d_lift_pass_desc *d, const cm3d_lift_pass_desc *l, const cm3d_lift_pass_options *o)
 {

@@ -55,6 +55,8 @@ THRESHS_BY_LABEL = {  # :850-861 (squared metres)
 PUSHED_CLASSES = ["car", "truck", "bus", "construction_vehicle", "trailer", "barrier"]  # :763
 MIN_DIST = 2.3            # :348
 N_SWEEPS = 3              # :437
+# the opt-in stages of a pass that have an event pair, in the order LiftEngine.run appends their events (`b.timed`)
+TIMED_ORDER = ("filter", "owner", "strip", "cluster", "yaw", "place")
 
 
 def get_detection_name(name):
@@ -469,7 +471,7 @@ class LiftEngine:
         obb: also fit KITTI's oriented box of every mask on the device (stage_obb, cm3d_obb: src/kitti/2d_to_3d.py:855-876, :1524);
         download() then returns `obb_yaw` and `obb_status`.  Off: no OBB buffer, no OBB launch.
         The four opt-in stages below are off when None (or inactive): then nothing changes, neither a buffer nor a launch.  With any of
-        them on, `run` still makes one call, cm3d_lift_pass_opt; include/cm3d_hip.h states where each stage stands in the pass.
+        them on, `run` still makes one call, cm3d_lift_pass_composed; include/cm3d_hip.h states where each stage stands in the pass.
         filters: the stage-2 filters (drivable.Stage2Filters; the reference ships them commented out, :755-785).  download(full=True)
         adds `on_road` and `medoid_pos_kept`; `drivable` needs batches with polygon tables (HostBatch.polygons).
         cluster: the depth clustering of the in-mask lists (cluster.DepthCluster; the reference's clusters_hdbscan is dead code), with
@@ -483,7 +485,7 @@ class LiftEngine:
         `box` holds the yaw that was used.
         place: the placement from the fitted rectangle (boxplace.BoxPlace; needs `yaw`): columns 0 and 1 of the boxes whose yaw was
         fitted come from the rectangle's sensor-side corner and faces instead of the view-ray push, and the circle NMS is decided again
-        on the new centres (cm3d_box_place, enqueued by cm3d_lift_pass_placed in front of the rotated NMS).  download() adds `place_src`
+        on the new centres (cm3d_box_place, enqueued by cm3d_lift_pass_composed in front of the rotated NMS).  download() adds `place_src`
         and `place_pushed`.  None: no buffer, no launch.
         velocity: the box velocity stage (velocity.Velocity; nuScenes batches, whose boxes are in the global frame): a call of its own
         behind the pass (cm3d_box_velocity) associates the kept boxes of consecutive frames.  It needs batches with `frame_next` and
@@ -512,7 +514,7 @@ class LiftEngine:
         strip: the ground strip (groundstrip.GroundStrip; nuScenes and Waymo batches, with any other option or none): directly behind the
         compaction a grid of ground heights is taken from every frame's own sweep rows (cm3d_ground_grid; the raw rows, or the cloud where
         the engine has materialised it -- it never makes the engine materialise it) and every in-mask list loses its ground points
-        (cm3d_ground_strip), both enqueued by cm3d_lift_pass_stripped.  The clustering, the medoid, the yaw fit and the vertical stage then
+        (cm3d_ground_strip), both enqueued by cm3d_lift_pass_composed.  The clustering, the medoid, the yaw fit and the vertical stage then
         read the stripped lists: `medoid_pos` is a position in the lists the medoid saw -- the clustered ones (`cl_off`) when the engine
         clusters, else the stripped ones (`gs_off`) --, while `hit_off` / `hit_idx` / `hit_xyz` stay the raw lists.  download() adds
         `gs_off`, `gs_status`, `gs_dropped` (full=True: `gs_idx`, `gs_xyz`, `grid_z`, `grid_n`).  None: no buffer, no launch.  Its seven
@@ -526,7 +528,7 @@ class LiftEngine:
         full=True, `hit_uvd`.  None: no buffer, no call.  Its parameters are untuned.
         owner: the point ownership (pointowner.PointOwner; nuScenes and Waymo batches, with any other option or none): directly behind the
         compaction, in front of the ground strip, every point that several masks of a frame list gets one owner and every list keeps
-        the positions it owns (cm3d_point_owner, enqueued by cm3d_lift_pass_owned).  The strip, the clustering, the medoid, the yaw fit,
+        the positions it owns (cm3d_point_owner, enqueued by cm3d_lift_pass_composed).  The strip, the clustering, the medoid, the yaw fit,
         the vertical stage and the virtual points then read the exclusive lists: `medoid_pos` is a position in the lists the medoid
         saw -- `cl_off`, else `gs_off`, else `ow_off` --, while `hit_off` / `hit_idx` / `hit_xyz` stay the raw lists.  download() adds
         `ow_off`, `ow_status`, `ow_lost` (full=True: `ow_owner`, `ow_idx`, `ow_xyz`).  None: no buffer, no launch.  Its two parameters
@@ -791,18 +793,16 @@ class LiftEngine:
         for name, desc in stages.items():
             setattr(b, name + "_desc", desc)
             setattr(b.opts, name, ctypes.addressof(desc))
-        b.timed = {name: desc for name, desc in stages.items() if name != "nms"}
-        if self.strip is not None:             # (no member of the options: cm3d_lift_pass_stripped takes it beside them; its events stand in front of the clustering's)
-            b.strip_desc = self._strip_descriptor(b)
-            b.timed = {**{k: v for k, v in b.timed.items() if k == "filter"}, "strip": b.strip_desc,
-                       **{k: v for k, v in b.timed.items() if k != "filter"}}
-        if self.owner is not None:             # (no member of the options either: cm3d_lift_pass_owned takes it; its events stand in front of the strip's)
-            b.owner_desc = self._owner_descriptor(b)
-            front = [k for k in b.timed if k == "filter"]
-            b.timed = {**{k: b.timed[k] for k in front}, "owner": b.owner_desc, **{k: v for k, v in b.timed.items() if k not in front}}
-        if self.place is not None:             # (no member of the options: cm3d_lift_pass_placed takes it beside them; its events come last)
-            b.place_desc = b.timed["place"] = self._place_descriptor(b)
+        # the stages the options have no member for: cm3d_lift_pass_composed takes their descriptors beside the options
+        beside = {"owner": self.owner and self._owner_descriptor(b), "strip": self.strip and self._strip_descriptor(b),
+                  "place": self.place and self._place_descriptor(b)}
+        beside = {name: desc for name, desc in beside.items() if desc is not None}
+        for name, desc in beside.items():
+            setattr(b, name + "_desc", desc)
+        have = {**stages, **beside}
+        b.timed = {name: have[name] for name in TIMED_ORDER if name in have}
         b.opts_ref = ctypes.byref(b.opts) if stages else None
+        b.place_ref, b.strip_ref, b.owner_ref = (ctypes.byref(beside[name]) if name in beside else None for name in ("place", "strip", "owner"))
         b.plain_pass = not stages and self.velocity is None and self.vertical is None and self.ground is None and self.strip is None and self.virtual is None and self.owner is None      # what cm3d_pipe_submit can enqueue by itself (LiftPipeline.rerun)
         self.b = b
         return b
@@ -1143,17 +1143,22 @@ class LiftEngine:
                                     _ptr(b.frame_lane), b.n_tables, b.n_lane, _ptr(b.grid), _ptr(b.lane_idx),
                                     _ptr(b.lane_dist), _ptr(b.ws), b.ws_bytes, st), "cm3d_lane_nn")
 
+    @staticmethod
+    def _mask_bound(b):
+        """`planes` words of mask bits per point: no frame of the batch has more than 32 * planes masks -- the bound cm3d_lift_pass hands
+        to the box launch, the rotated NMS and the placement."""
+        return min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME)
+
     def stage_boxes(self, st, medoid_pos=None):
         """The box launch on the resident results.  medoid_pos: the positions that decide which masks have a box (None: the medoid
         stage's; an engine with filters hands `b.medoid_pos_kept` for the launch behind the filter)."""
         b = self.b
-        # (`planes` words of mask bits per point: no frame of the batch has more than 32 * planes masks -- the bound cm3d_lift_pass hands over)
         check(self.lib.cm3d_box_nms_bounded(_ptr(b.centroid_g), _ptr(b.medoid_pos if medoid_pos is None else medoid_pos), _ptr(b.mask_off),
                                             b.F, b.M, _ptr(b.class_id),
                                             _ptr(b.score), _ptr(b.lane), _ptr(b.lane_off), _ptr(b.frame_lane), _ptr(b.lane_idx),
                                             _ptr(b.lane_dist), _ptr(self.prior_wlh), _ptr(self.is_vehicle), _ptr(self.nms_group),
                                             _ptr(self.nms_thr), len(self.classes.names), _ptr(b.ego_xyz), _ptr(b.pose_inv),
-                                            min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), _ptr(b.box), _ptr(b.flags), st),
+                                            self._mask_bound(b), _ptr(b.box), _ptr(b.flags), st),
               "cm3d_box_nms_bounded")
 
     def stage_obb(self, st):
@@ -1215,7 +1220,7 @@ class LiftEngine:
         b, n = self.b, self.b.nms_desc
         check(self.lib.cm3d_box_rotated_nms(_ptr(b.box), _ptr(b.flags), _ptr(b.mask_off), b.F, b.M, _ptr(b.class_id), _ptr(self.prior_wlh),
                                             _ptr(self.nms_group), len(self.classes.names), n.thr, n.n_thr, n.measure, n.class_agnostic,
-                                            int(b.pose_inv is not None), min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), st),
+                                            int(b.pose_inv is not None), self._mask_bound(b), st),
               "cm3d_box_rotated_nms")
 
     def stage_place(self, st):
@@ -1223,7 +1228,7 @@ class LiftEngine:
         b, p = self.b, self.b.place_desc
         check(self.lib.cm3d_box_place(_ptr(b.box), _ptr(b.flags), _ptr(b.mask_off), b.F, b.M, _ptr(b.fit_rect), _ptr(b.yaw_src),
                                       _ptr(self.prior_wlh), _ptr(self.nms_group), _ptr(self.nms_thr), len(self.classes.names), _ptr(b.ego_xyz),
-                                      int(b.pose_inv is not None), p.thin, min(32 * b.planes, _lib.MAX_MASKS_PER_FRAME), p.place_src,
+                                      int(b.pose_inv is not None), p.thin, self._mask_bound(b), p.place_src,
                                       p.place_pushed, st), "cm3d_box_place")
 
     def stage_velocity(self, st):
@@ -1294,19 +1299,34 @@ class LiftEngine:
 
     STAGES = ("sweeps", "masks", "project", "compact", "medoid", "lanes", "boxes")
 
+    def _timed(self, stage, st, stage_events):
+        """A stage's call behind the pass, between a new pair of events appended to stage_events when the pass is timed."""
+        if stage_events is None:
+            return stage(st)
+        pair = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        stage_events.extend(pair)
+        pair[0].record(torch.cuda.current_stream(self.dev))
+        stage(st)
+        pair[1].record(torch.cuda.current_stream(self.dev))
+
     def run(self, masks="dense", project_events=None, stage_events=None):
         """One pass of the hot path over the resident batch (asynchronous).  project_events: optional pair of
         torch.cuda.Event recorded around the projection launch on the launch stream (bench.py's roofline timing).
-        stage_events: optional list; gets five timing events appended -- before the point/mask stages, behind the compaction,
-        the medoid, the lane search and the boxes -- the entry points' timer buckets (reference :368-378) come from them.
-        Each opt-in stage the engine has appends two more behind those, in this order: around the filter launch (the "drivable"
-        bucket), around the point ownership's launches (the "owner" bucket; behind the second of the five, in front of the strip's), around the ground strip's launches (the "strip" bucket; behind the second of the five, in front of the clustering's), around the clustering's launches (the "cluster" bucket; they lie between the second and the third of the five), around
-        the yaw fit's two launches (the "yawfit" bucket; behind the fifth event), around the placement's launch (the "place" bucket;
-        behind the yaw fit's boxes), around the vertical stage's call (the "vertical" bucket; behind the pass), around the ground stage's
-        call (the "ground" bucket; behind the vertical stage's), around the virtual points' call (the "virtual points" bucket; last of
-        all, behind the velocity, track and size stages' calls, which have no events).  One library call enqueues
-        the pass, opt-in stages included (cm3d_lift_pass_opt, cm3d_lift_pass_placed with a placement, cm3d_lift_pass_stripped with a ground strip, or cm3d_lift_pass_owned with the point ownership; include/cm3d_hip.h states the
-        order); no allocation, no synchronisation."""
+        stage_events: optional list; gets timing events appended, from which the entry points' timer buckets (reference :368-378)
+        come, in this order:
+          - five: before the point/mask stages, behind the compaction, the medoid, the lane search and the boxes;
+          - then a pair around each opt-in stage the engine has, in the order of TIMED_ORDER:
+              filter   the filter launch (the "drivable" bucket);
+              owner    the point ownership's launches (the "owner" bucket; behind the second of the five, in front of the strip's);
+              strip    the ground strip's launches (the "strip" bucket; behind the second of the five, in front of the clustering's);
+              cluster  the clustering's launches (the "cluster" bucket; between the second and the third of the five);
+              yaw      the yaw fit's two launches (the "yawfit" bucket; behind the fifth event);
+              place    the placement's launch (the "place" bucket; behind the yaw fit's boxes);
+          - then a pair around each of these calls behind the pass: the vertical stage's (the "vertical" bucket), the ground stage's
+            (the "ground" bucket; behind the vertical stage's), the virtual points' (the "virtual points" bucket; last of all, behind
+            the velocity, track and size stages' calls, which have no events).
+        One library call enqueues the pass, opt-in stages included (cm3d_lift_pass_composed; include/cm3d_hip.h states the order); no
+        allocation, no synchronisation."""
         dense = self.resident_masks(masks)               # raises before anything is enqueued
         if not self._lane["built"]:
             self.start_lane_grid()
@@ -1317,35 +1337,13 @@ class LiftEngine:
             stage_events.extend(marks + [ev for pair in omarks.values() for ev in pair])
         st = torch.cuda.current_stream(self.dev).cuda_stream
         desc = self.refresh_pass_descriptor(dense, project_events, marks, omarks)
-        if self.owner is not None:                       # the same pass, the ownership in front of the strip (and the placement as below)
-            check(self.lib.cm3d_lift_pass_owned(desc, self.b.opts_ref, ctypes.byref(self.b.place_desc) if self.place is not None else None,
-                                                ctypes.byref(self.b.strip_desc) if self.strip is not None else None,
-                                                ctypes.byref(self.b.owner_desc), st), "cm3d_lift_pass_owned")
-        elif self.strip is not None:                     # the same pass, the strip in front of the clustering (and the placement as below)
-            check(self.lib.cm3d_lift_pass_stripped(desc, self.b.opts_ref, ctypes.byref(self.b.place_desc) if self.place is not None else None,
-                                                   ctypes.byref(self.b.strip_desc), st), "cm3d_lift_pass_stripped")
-        elif self.place is None:
-            check(self.lib.cm3d_lift_pass_opt(desc, self.b.opts_ref, st), "cm3d_lift_pass_opt")
-        else:                                            # the same pass, the placement in front of its rotated NMS
-            check(self.lib.cm3d_lift_pass_placed(desc, self.b.opts_ref, ctypes.byref(self.b.place_desc), st), "cm3d_lift_pass_placed")
+        b = self.b
+        check(self.lib.cm3d_lift_pass_composed(desc, b.opts_ref, b.place_ref, b.strip_ref, b.owner_ref, st), "cm3d_lift_pass_composed")
+
         if self.vertical is not None:                    # directly behind the pass: column 2 only, so the stages below see what they saw
-            pair = None
-            if stage_events is not None:
-                pair = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-                stage_events.extend(pair)
-                pair[0].record(torch.cuda.current_stream(self.dev))
-            self.stage_vertical(st)
-            if pair is not None:
-                pair[1].record(torch.cuda.current_stream(self.dev))
+            self._timed(self.stage_vertical, st, stage_events)
         if self.ground is not None:                      # behind the vertical stage's call: column 2 only, like it
-            pair = None
-            if stage_events is not None:
-                pair = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-                stage_events.extend(pair)
-                pair[0].record(torch.cuda.current_stream(self.dev))
-            self.stage_ground(st)
-            if pair is not None:
-                pair[1].record(torch.cuda.current_stream(self.dev))
+            self._timed(self.stage_ground, st, stage_events)
         if self.velocity is not None:                    # behind the pass, on its final kept set: one more library call
             self.stage_velocity(st)
         if self.tracks is not None:                      # behind the velocity stage, on its matches: one more
@@ -1353,14 +1351,7 @@ class LiftEngine:
         if self.size is not None:                        # behind the track stage, on its tracks: one more
             self.stage_size(st)
         if self.virtual is not None:                     # behind everything that writes `flags`; it writes no box, flag or record
-            pair = None
-            if stage_events is not None:
-                pair = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-                stage_events.extend(pair)
-                pair[0].record(torch.cuda.current_stream(self.dev))
-            self.stage_virtual(st)
-            if pair is not None:
-                pair[1].record(torch.cuda.current_stream(self.dev))
+            self._timed(self.stage_virtual, st, stage_events)
 
     def capture_graph(self, masks="rle"):
         """Captures one pass over the resident batch into a HIP graph and returns it (`g.replay()` re-runs the pass

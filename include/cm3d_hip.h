@@ -924,7 +924,8 @@ typedef struct cm3d_lift_pass_options {    /* NULL member: that stage is off */
 
 /* Every pass with an opt-in stage: enqueues on `stream`, stopping at and returning the first error (a failed event call:
  * CM3D_ERR_LAUNCH); NULL events are skipped; no descriptor of the caller's is written.  This is the only statement of a composed
- * pass's order -- cm3d_amd.lifting.LiftEngine.run and the three single-option passes end here:
+ * pass's order for the stages the options name -- cm3d_lift_pass_composed (at the end of this header; it adds the stages the options
+ * have no member for) and the three single-option passes end here:
  *
  *   every present descriptor is checked first: `size` of opt, desc and each member; cluster's cl_off, cl_tile_off, cl_xyz, cl_status
  *   (and cl_idx when desc has hit_idx); filter's medoid_pos_kept, on_road; yaw's tables and outputs as in cm3d_yaw_fit_boxes, and its
@@ -1086,20 +1087,12 @@ typedef struct cm3d_box_place_desc {       /* what the placed pass needs beyond 
     double thin;
 } cm3d_box_place_desc;
 
-/* The composed pass with the placement (host code, csrc/pass_place.cpp; cm3d_lift_pass_options has no member for it and
- * csrc/pass_options.cpp does not know it).  Enqueues on `stream`, stopping at and returning the first error; no descriptor of the
- * caller's is written:
- *
- *   checked first, CM3D_ERR_ARG and NO call at all: desc, opt or place NULL or of a wrong `size`; opt->yaw NULL, of a wrong size or
- *   without fit_rect or yaw_src; place_src or place_pushed NULL; a bad thin; opt->nms given but of a wrong size or without thr
- *   cm3d_lift_pass_opt(desc, opt')        opt' = a copy of opt with nms = NULL: cluster, filter and yaw as stated there (it checks
- *                                         their descriptors before its first call)
- *   record place->ev[0]
- *   cm3d_box_place                        box, flags, mask_off, prior_wlh, nms_group, nms_thr, ego_xyz ... of desc; fit_rect, yaw_src of
- *                                         opt->yaw; waymo = pose_inv != NULL; bound as the box launch's
- *   record place->ev[1]
- *   opt->nms ?  cm3d_box_rotated_nms      as in cm3d_lift_pass_opt: it judges the placed boxes and overwrites the circle NMS's verdict
- *   behind the pass, calls of the caller's own as before: cm3d_box_velocity (its centres are the placed ones), cm3d_box_tracks */
+/* The composed pass with the placement: cm3d_lift_pass_composed(desc, opt, place, NULL, NULL, stream) (below; host code,
+ * csrc/pass_compose.cpp), which states the order and the checks; cm3d_lift_pass_options has no member for the placement and
+ * csrc/pass_options.cpp does not know it.  Its own requirement, checked first: a NULL opt or a NULL place is CM3D_ERR_ARG and NO call
+ * at all.  So every refusal of the composer's applies: desc, opt or place of a wrong `size`; opt->yaw NULL, of a wrong size or without
+ * fit_rect or yaw_src; place_src or place_pushed NULL; a bad thin; opt->nms given but of a wrong size or without thr.
+ * Behind the pass, calls of the caller's own as before: cm3d_box_velocity (its centres are the placed ones), cm3d_box_tracks. */
 int cm3d_lift_pass_placed(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, const cm3d_box_place_desc *place,
                           cm3d_stream_t stream);
 
@@ -1367,28 +1360,10 @@ typedef struct cm3d_ground_strip_desc {
     int32_t min_points, min_keep;
 } cm3d_ground_strip_desc;
 
-/* The composed pass with the ground strip (host code, csrc/pass_strip.cpp; behind the strip it enters csrc/pass_options.cpp, which
- * states the order of every composed pass, on the stripped lists.  No member of cm3d_lift_pass_options: the strip stands in front of
- * every stage the options name, and pass_options.cpp does not know it).  Enqueues on `stream`, stopping at
- * and returning the first error; no descriptor of the caller's is written.  opt may be NULL (no other stage), place may be NULL;
- * a NULL strip is CM3D_ERR_ARG: it does not fall back to the plain pass.
- *
- *   every descriptor is checked first, CM3D_ERR_ARG and NO call at all: desc, opt and its members as in cm3d_lift_pass_opt; place as
- *   in cm3d_lift_pass_placed (it needs opt->yaw); strip's size, its arrays (gs_idx when desc has hit_idx), its workspace pointer and
- *   cm3d_ground_strip_check of its parameters; yaw's hit_xyz, hit_off, medoid_pos each NULL or what is derived below
- *   cm3d_lift_pass_head(desc)
- *   record strip->ev[0]; cm3d_ground_grid (desc's sweep rows: the cloud where desc has points, else the raw rows; origin -> grid_z, grid_n);
- *   cm3d_ground_strip (desc's lists -> the gs_* arrays); record strip->ev[1]
- *   cluster ?  record cluster->ev[0]; cm3d_depth_cluster (the gs_* lists -> the cl_* arrays); record cluster->ev[1]
- *   cm3d_lift_pass_tail(desc')            desc' = desc with hit_off, tile_off, hit_idx, hit_xyz = the cl_* arrays, or the gs_* arrays
- *                                         without a cluster; tile_work = NULL
- *   filter  ?  as in cm3d_lift_pass_opt
- *   yaw     ?  cm3d_yaw_fit_boxes' sequence          lists = cluster ? cl_xyz, cl_off : gs_xyz, gs_off
- *   place   ?  record place->ev[0]; cm3d_box_place; record place->ev[1]      as in cm3d_lift_pass_placed
- *   nms     ?  cm3d_box_rotated_nms                  as in cm3d_lift_pass_opt
- *   medoid_pos is then a position in the lists the medoid saw (the cl_* lists, or the gs_* lists).  Behind the pass the caller's own
- *   calls as before; cm3d_box_vertical reads the lists the yaw fit reads.  cm3d_box_ground stays what it is: it streams the sweep and
- *   does not read the grid. */
+/* The composed pass with the ground strip: cm3d_lift_pass_composed(desc, opt, place, strip, NULL, stream) (below; host code,
+ * csrc/pass_compose.cpp), which states the order and the checks.  No member of cm3d_lift_pass_options: the strip stands in front of
+ * every stage the options name, and csrc/pass_options.cpp does not know it.  opt may be NULL (no other stage), place may be NULL.  Its
+ * own requirement, checked first: a NULL strip is CM3D_ERR_ARG and NO call at all: it does not fall back to the plain pass. */
 int cm3d_lift_pass_stripped(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, const cm3d_box_place_desc *place,
                             const cm3d_ground_strip_desc *strip, cm3d_stream_t stream);
 
@@ -1530,21 +1505,48 @@ typedef struct cm3d_point_owner_desc {
     int32_t rule, min_keep;
 } cm3d_point_owner_desc;
 
-/* The composed pass with the point ownership (host code, csrc/pass_owner.cpp; behind the ownership and the strip it enters
- * csrc/pass_options.cpp on the lists that are left.  cm3d_lift_pass_opt, _placed and _stripped do not know the stage).  Enqueues on
- * `stream`, stopping at and returning the first error; no descriptor of the caller's is written.  opt, place and strip may be NULL; a
- * NULL owner is CM3D_ERR_ARG: it does not fall back to another pass.
+/* ---- One pass with any opt-in stage, those without a member in cm3d_lift_pass_options included ----
+ * Added within ABI v5: a new symbol only, so CM3D_ABI_VERSION stays.  Host code (csrc/pass_compose.cpp; behind the ownership and the
+ * strip it enters csrc/pass_options.cpp, which does not know these stages, on the lists that are left).  This is the one statement of
+ * the order of a pass with a placement, a ground strip or a point ownership: cm3d_lift_pass_placed, _stripped and _owned and
+ * cm3d_amd.lifting.LiftEngine.run end here.  Enqueues on `stream`, stopping at and returning the first error (a failed event call:
+ * CM3D_ERR_LAUNCH); NULL events are skipped; no descriptor of the caller's is written.  opt, place, strip and owner may each be NULL.
  *
- *   every descriptor is checked first, CM3D_ERR_ARG and NO call at all: desc (with hit_idx), opt and its members as in
- *   cm3d_lift_pass_opt; place as in cm3d_lift_pass_placed; strip as in cm3d_lift_pass_stripped; owner's size, its arrays, its workspace
- *   pointer and cm3d_point_owner_check of its parameters; yaw's hit_xyz, hit_off, medoid_pos each NULL or what is derived below
- *   cm3d_lift_pass_head(desc)
- *   record owner->ev[0]; cm3d_point_owner (desc's lists, mask_off, score -> the ow_* arrays); record owner->ev[1]
- *   strip   ?  record strip->ev[0]; cm3d_ground_grid; cm3d_ground_strip (the ow_* lists -> the gs_* arrays); record strip->ev[1]
- *   cluster ?  cm3d_depth_cluster (the gs_* lists, else the ow_* lists -> the cl_* arrays), between its events
- *   cm3d_lift_pass_tail(desc')            desc' = desc with the cl_* arrays, else the gs_* arrays, else the ow_* arrays; tile_work = NULL
- *   filter, yaw, place, nms               as in cm3d_lift_pass_stripped; the yaw fit reads the lists the medoid saw
- *   medoid_pos is then a position in the lists the medoid saw: cl_*, else gs_*, else ow_*. */
+ *   every descriptor is checked first, CM3D_ERR_ARG and NO call at all, whichever is bad:
+ *     desc     NULL or of a wrong `size`
+ *     owner    desc without hit_idx; owner's `size`, a NULL ow_* array, a NULL workspace pointer, cm3d_point_owner_check of its parameters
+ *     strip    its `size`, a NULL array (gs_idx only when desc has hit_idx), a NULL workspace pointer, cm3d_ground_strip_check of its
+ *              parameters
+ *     opt      its `size` and its members as in cm3d_lift_pass_opt, for the lists the pass goes on with: yaw's hit_xyz, hit_off,
+ *              medoid_pos each NULL or what is derived below; cluster's cl_idx when those lists have a hit_idx
+ *     place    its `size`; place_src or place_pushed NULL; thin not in [0, DBL_MAX]; opt NULL, opt->yaw NULL or without fit_rect or
+ *              yaw_src (a placement needs the yaw fit)
+ *   owner or strip ?  cm3d_lift_pass_head(desc)
+ *   owner   ?  record owner->ev[0]; cm3d_point_owner (desc's lists, mask_off, score -> the ow_* arrays); record owner->ev[1]
+ *   strip   ?  record strip->ev[0]; cm3d_ground_grid (desc's sweep rows: the cloud where desc has points, else the raw rows; origin ->
+ *              grid_z, grid_n); cm3d_ground_strip (the ow_* lists, else desc's lists -> the gs_* arrays); record strip->ev[1]
+ *   the lists the pass goes on with: the gs_* arrays, else the ow_* arrays, else desc's
+ *   owner or strip ?  cluster ?  record cluster->ev[0]; cm3d_depth_cluster (the lists -> the cl_* arrays); record cluster->ev[1]
+ *                     cm3d_lift_pass_tail(desc')     desc' = desc with hit_off, tile_off, hit_idx, hit_xyz = the cl_* arrays, else the
+ *                                                    lists; tile_work = NULL
+ *                  :  cluster and the plain pass as in cm3d_lift_pass_opt (the head runs there, in front of the clustering)
+ *   filter  ?  as in cm3d_lift_pass_opt
+ *   yaw     ?  cm3d_yaw_fit_boxes' sequence          lists = cluster ? cl_xyz, cl_off : the lists the pass goes on with
+ *   place   ?  record place->ev[0]
+ *              cm3d_box_place                        box, flags, mask_off, prior_wlh, nms_group, nms_thr, ego_xyz ... of desc; fit_rect,
+ *                                                    yaw_src of opt->yaw; waymo = pose_inv != NULL; bound as the box launch's
+ *              record place->ev[1]
+ *   nms     ?  cm3d_box_rotated_nms                  as in cm3d_lift_pass_opt; with a placement it judges the placed boxes and overwrites
+ *                                                    the circle NMS's verdict (the stages in front run on a copy of opt with nms = NULL)
+ *   place, strip and owner all NULL: exactly cm3d_lift_pass_opt(desc, opt) for a desc of the right size
+ *   medoid_pos is then a position in the lists the medoid saw: cl_*, else gs_*, else ow_*, else desc's.  Behind the pass the caller's own
+ *   calls as before; cm3d_box_vertical reads the lists the yaw fit reads.  cm3d_box_ground stays what it is: it streams the sweep and
+ *   does not read the grid. */
+int cm3d_lift_pass_composed(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, const cm3d_box_place_desc *place,
+                            const cm3d_ground_strip_desc *strip, const cm3d_point_owner_desc *owner, cm3d_stream_t stream);
+
+/* The composed pass with the point ownership: cm3d_lift_pass_composed with the same arguments (above).  opt, place and strip may be
+ * NULL.  Its own requirement, checked first: a NULL owner is CM3D_ERR_ARG and NO call at all: it does not fall back to another pass. */
 int cm3d_lift_pass_owned(const cm3d_lift_pass_desc *desc, const cm3d_lift_pass_options *opt, const cm3d_box_place_desc *place,
                          const cm3d_ground_strip_desc *strip, const cm3d_point_owner_desc *owner, cm3d_stream_t stream);
 

@@ -1,6 +1,6 @@
-// Stand-alone trace of cm3d_lift_pass_placed (cm3d_amd/csrc/pass_place.cpp) over the real cm3d_lift_pass_opt (csrc/pass_options.cpp) and
+// Stand-alone trace of cm3d_lift_pass_placed (cm3d_amd/csrc/pass_compose.cpp) over the real seam of csrc/pass_options.cpp and
 // stubs of the entry points the two call: the stubs, the arrays and the case runner of tests/pass_options_sim.cpp, taken in whole, plus
-// a stub of cm3d_box_place.  tests/test_box_place_host.py builds it with the address and undefined-behaviour sanitizers and compares
+// a stub of cm3d_box_place, and of what the composer calls for a strip or an ownership (never reached here).  tests/test_box_place_host.py builds it with the address and undefined-behaviour sanitizers and compares
 // the output with the sequence include/cm3d_hip.h states.  Per case, as there: the calls of a clean pass, `rc`, then `fail k rc calls`.
 #include <cmath>
 
@@ -20,6 +20,28 @@ extern "C" int cm3d_box_place(double *box, int32_t *flags, const int32_t *mask_o
     CALLED(CM3D_ERR_WORKSPACE, CM3D_OK, "cm3d_box_place io=%s,%s off=%s rest=%s n=%d,%d,%d waymo=%d thin=%g bound=%d out=%s,%s", who(box), who(flags),
            who(mask_off), rest ? "set" : "other", n_frames, n_masks, n_classes, waymo, thin, max_masks_per_frame,
            place_src == g_place_src ? "set" : "other", place_pushed == g_pushed ? "set" : "other");
+}
+
+// what csrc/pass_compose.cpp needs to link beyond that: the ground strip's and the point ownership's entry points.  No case here has a
+// strip or an ownership, so none is called; one that were would print its line under the case
+extern "C" {
+int cm3d_ground_strip_check(double, double, double, double, int32_t, double, int32_t) { CALLED(CM3D_ERR_ARG, CM3D_OK, "cm3d_ground_strip_check"); }
+int cm3d_ground_grid(const float *, const int32_t *, const float *, int32_t, const float *, const int32_t *, const int32_t *, int32_t, float, int32_t,
+                     const double *, int32_t, double, double, double, double, int32_t, double *, int32_t *, cm3d_stream_t)
+{
+    CALLED(CM3D_ERR_WORKSPACE, CM3D_OK, "cm3d_ground_grid");
+}
+int cm3d_ground_strip(const float *, const int32_t *, const int32_t *, const int32_t *, int32_t, int32_t, const double *, const double *, int32_t, double,
+                      double, int32_t, int32_t *, int32_t *, int32_t *, float *, int32_t *, int32_t *, void *, int64_t, cm3d_stream_t)
+{
+    CALLED(CM3D_ERR_WORKSPACE, CM3D_OK, "cm3d_ground_strip");
+}
+int cm3d_point_owner_check(int32_t, int32_t) { CALLED(CM3D_ERR_ARG, CM3D_OK, "cm3d_point_owner_check"); }
+int cm3d_point_owner(const float *, const int32_t *, const int32_t *, const int32_t *, int32_t, int32_t, int32_t, int32_t, const double *, int32_t,
+                     int32_t, int32_t *, int32_t *, int32_t *, int32_t *, float *, int32_t *, int32_t *, void *, int64_t, cm3d_stream_t)
+{
+    CALLED(CM3D_ERR_WORKSPACE, CM3D_OK, "cm3d_point_owner");
+}
 }
 
 struct PlaceCase { Case k; cm3d_box_place_desc p; };

@@ -1,8 +1,10 @@
-// Stand-alone trace of cm3d_lift_pass_stripped (cm3d_amd/csrc/pass_strip.cpp over the seam of csrc/pass_options.cpp) over stubs of the entry points it calls and of
-// hipEventRecord, in the manner of tests/pass_options_sim.cpp (whose stubs do not know the gs_* arrays, so this program has its own:
-// each says whose arrays it was handed).  tests/test_ground_strip_host.py builds it with the address and undefined-behaviour sanitizers
-// and compares the output with the sequence include/cm3d_hip.h states.  Per case: the calls of a clean pass, `rc`, then for every call
-// k of that pass `fail k rc calls`: the pass again with call k answering an error.
+// Stand-alone trace of cm3d_lift_pass_stripped, cm3d_lift_pass_owned and cm3d_lift_pass_composed (cm3d_amd/csrc/pass_compose.cpp over the
+// seam of csrc/pass_options.cpp) over stubs of the entry points they call and of hipEventRecord, in the manner of
+// tests/pass_options_sim.cpp (whose stubs do not know the gs_* and ow_* arrays, so this program has its own: each says whose arrays it
+// was handed).  tests/test_ground_strip_host.py builds it with the address and undefined-behaviour sanitizers and compares the output
+// with the sequence include/cm3d_hip.h states; tests/test_owned_pass_host.py does so for the owned.* cases, and holds the composer's
+// trace against that of the entry point with the same arguments (the equiv.* cases).  Per case: the calls of a clean pass, `rc`, then
+// for every call k of that pass `fail k rc calls`: the pass again with call k answering an error.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -28,12 +30,13 @@ static bool fails() { return g_calls++ == g_fail_at; }
 static int32_t g_hit_off[4], g_tile_off[4], g_hit_idx[4], g_tile_work[4], g_cl_off[4], g_cl_tile_off[4], g_cl_idx[4], g_cl_status[4], g_gs_off[4],
     g_gs_tile_off[4], g_gs_idx[4], g_gs_status[4], g_gs_dropped[4], g_grid_n[4], g_medoid_pos[4], g_kept[4], g_lane_off[4], g_frame_lane[4],
     g_lane_idx[4], g_mask_frame[4], g_class[4], g_veh[4], g_fit_k[4], g_fit_status[4], g_yaw_idx[4], g_yaw_src[4], g_tab_off[2], g_tab_frame[4],
-    g_mask_off[4], g_flags[4], g_group[4], g_place_src[4], g_sweep_row_off[4], g_frame_sweep_off[4], g_pt_off[4];
+    g_mask_off[4], g_flags[4], g_group[4], g_place_src[4], g_sweep_row_off[4], g_frame_sweep_off[4], g_pt_off[4], g_ow_owner[4], g_ow_off[4],
+    g_ow_tile_off[4], g_ow_idx[4], g_ow_status[4], g_ow_lost[4];
 static float g_hit_xyz[4], g_cl_xyz[4], g_gs_xyz[4], g_lane[4], g_yaw_tab[4], g_centroid[4], g_pose_rt[12], g_pose_inv[16], g_raw[4], g_xf[24],
-    g_points[4];
+    g_points[4], g_ow_xyz[4];
 static double g_cs[4], g_rect[8], g_lane_dist[4], g_score[4], g_prior[4], g_thr[4], g_rot_thr[4], g_ego[4], g_box[4], g_origin[4], g_grid_z[4],
     g_pushed[8];
-static uint8_t g_ws[16], g_gs_ws[16], g_on_road[4];
+static uint8_t g_ws[16], g_gs_ws[16], g_ow_ws[16], g_on_road[4];
 
 struct Name { const void *p; const char *n; };
 static const char *who(const void *p)
@@ -44,7 +47,9 @@ static const char *who(const void *p)
                           {g_grid_n, "grid_n"}, {g_medoid_pos, "medoid_pos"}, {g_kept, "kept"}, {g_hit_xyz, "hit_xyz"}, {g_cl_xyz, "cl_xyz"},
                           {g_lane, "lane"}, {g_yaw_tab, "yaw_tab"}, {g_box, "box"}, {g_flags, "flags"}, {g_origin, "origin"}, {g_ego, "ego"},
                           {g_raw, "raw"}, {g_points, "points"}, {g_pt_off, "pt_off"}, {g_ws, "cl_ws"}, {g_gs_ws, "gs_ws"}, {g_rect, "fit_rect"},
-                          {g_yaw_src, "yaw_src"}, {g_place_src, "place_src"}, {g_pushed, "place_pushed"}, {g_cl_status, "cl_status"}};
+                          {g_yaw_src, "yaw_src"}, {g_place_src, "place_src"}, {g_pushed, "place_pushed"}, {g_cl_status, "cl_status"}, {g_ow_owner, "ow_owner"},
+                          {g_ow_off, "ow_off"}, {g_ow_tile_off, "ow_tile_off"}, {g_ow_idx, "ow_idx"}, {g_ow_xyz, "ow_xyz"}, {g_ow_status, "ow_status"},
+                          {g_ow_lost, "ow_lost"}, {g_ow_ws, "ow_ws"}, {g_mask_off, "mask_off"}, {g_score, "score"}};
     if (!p) return "null";
     for (const Name &e : names)
         if (e.p == p) return e.n;
@@ -88,6 +93,17 @@ int cm3d_ground_strip(const float *hit_xyz, const int32_t *hit_idx, const int32_
            who(hit_xyz), who(hit_idx), who(hit_off), mask_frame == g_mask_frame ? "set" : "other", n_masks, idx_cap, n_frames, who(origin),
            who(grid_z), cell, margin, min_keep, who(gs_off), who(gs_tile_off), who(gs_idx), who(gs_xyz), who(gs_status), who(gs_dropped), who(ws),
            (long long)ws_bytes);
+}
+// the rule of include/cm3d_hip.h, written out once more
+int cm3d_point_owner_check(int32_t rule, int32_t min_keep) { return (rule == 0 || rule == 1) && min_keep >= 1 ? CM3D_OK : CM3D_ERR_ARG; }
+int cm3d_point_owner(const float *hit_xyz, const int32_t *hit_idx, const int32_t *hit_off, const int32_t *mask_off, int32_t n_frames, int32_t n_masks,
+                     int32_t idx_cap, int32_t max_pts_per_frame, const double *score, int32_t rule, int32_t min_keep, int32_t *ow_owner,
+                     int32_t *ow_off, int32_t *ow_tile_off, int32_t *ow_idx, float *ow_xyz, int32_t *ow_status, int32_t *ow_lost, void *ws,
+                     int64_t ws_bytes, cm3d_stream_t)
+{
+    CALLED(CM3D_ERR_WORKSPACE, CM3D_OK, "cm3d_point_owner in=%s,%s,%s off=%s score=%s n=%d,%d,%d,%d par=%d,%d out=%s,%s,%s,%s,%s,%s,%s ws=%s,%lld",
+           who(hit_xyz), who(hit_idx), who(hit_off), who(mask_off), who(score), n_frames, n_masks, idx_cap, max_pts_per_frame, rule, min_keep,
+           who(ow_owner), who(ow_off), who(ow_tile_off), who(ow_idx), who(ow_xyz), who(ow_status), who(ow_lost), who(ws), (long long)ws_bytes);
 }
 int cm3d_depth_cluster(const float *hit_xyz, const int32_t *hit_idx, const int32_t *hit_off, const int32_t *, int32_t, int32_t, const double *origin,
                        int32_t, double, int32_t, int32_t, int32_t *cl_off, int32_t *cl_tile_off, int32_t *cl_idx, float *cl_xyz, int32_t *cl_status,
@@ -143,16 +159,28 @@ struct Case {
     cm3d_lift_pass_options o;
     cm3d_box_place_desc b;
     cm3d_ground_strip_desc s;
+    cm3d_point_owner_desc w;
 };
 
-// cm3d_lift_pass_stripped with the members `which` names (c, f, y, n: the options' members; p: the placement; o: the options themselves
-// -- without it opt is NULL; s: the strip) pointing at the case's descriptors
+// the entry point under trace: cm3d_lift_pass_stripped ('s'), cm3d_lift_pass_owned ('w'), cm3d_lift_pass_placed ('p'),
+// cm3d_lift_pass_opt ('o') or cm3d_lift_pass_composed ('x')
+static char g_entry = 's';
+
+// the entry point with the members `which` names (c, f, y, n: the options' members; p: the placement; o: the options themselves
+// -- without it opt is NULL; s: the strip; w: the ownership) pointing at the case's descriptors
 static int call(Case &k, const char *which)
 {
     k.o.cluster = std::strchr(which, 'c') ? &k.c : nullptr, k.o.filter = std::strchr(which, 'f') ? &k.f : nullptr;
     k.o.yaw = std::strchr(which, 'y') ? &k.y : nullptr, k.o.nms = std::strchr(which, 'n') ? &k.n : nullptr;
-    return cm3d_lift_pass_stripped(&k.p, std::strchr(which, 'o') ? &k.o : nullptr, std::strchr(which, 'p') ? &k.b : nullptr,
-                                   std::strchr(which, 's') ? &k.s : nullptr, nullptr);
+    const cm3d_lift_pass_options *o = std::strchr(which, 'o') ? &k.o : nullptr;
+    const cm3d_box_place_desc *b = std::strchr(which, 'p') ? &k.b : nullptr;
+    const cm3d_ground_strip_desc *s = std::strchr(which, 's') ? &k.s : nullptr;
+    const cm3d_point_owner_desc *w = std::strchr(which, 'w') ? &k.w : nullptr;
+    if (g_entry == 'x') return cm3d_lift_pass_composed(&k.p, o, b, s, w, nullptr);
+    if (g_entry == 'w') return cm3d_lift_pass_owned(&k.p, o, b, s, w, nullptr);
+    if (g_entry == 'p') return cm3d_lift_pass_placed(&k.p, o, b, nullptr);
+    if (g_entry == 'o') return cm3d_lift_pass_opt(&k.p, o, nullptr);
+    return cm3d_lift_pass_stripped(&k.p, o, b, s, nullptr);
 }
 
 static void run(const char *name, Case k, const char *which)
@@ -185,7 +213,7 @@ int main()
     p.class_id = g_class, p.score = g_score, p.prior_wlh = g_prior, p.is_vehicle = g_veh, p.nms_group = g_group, p.nms_thr = g_thr;
     p.ego_xyz = g_ego, p.box = g_box, p.flags = g_flags, p.mask_off = g_mask_off;
     p.raw = g_raw, p.raw_stride = 5, p.sweep_xf = g_xf, p.sweep_row_off = g_sweep_row_off, p.frame_sweep_off = g_frame_sweep_off, p.pt_off = g_pt_off;
-    p.n_sweeps = 6, p.pt_cap = 5000, p.halfw = 1.5f;
+    p.n_sweeps = 6, p.pt_cap = 5000, p.halfw = 1.5f, p.max_pts_per_frame = 3000;
     p.n_masks = 7, p.n_frames = 3, p.idx_cap = 4096, p.n_tables = 2, p.n_lane_points = 900, p.n_classes = 10, p.planes = 3;
     q.c.size = (int64_t)sizeof q.c;
     q.c.origin = g_origin, q.c.cl_off = g_cl_off, q.c.cl_tile_off = g_cl_tile_off, q.c.cl_idx = g_cl_idx, q.c.cl_xyz = g_cl_xyz;
@@ -210,6 +238,10 @@ int main()
     s.gs_xyz = g_gs_xyz, s.gs_status = g_gs_status, s.gs_dropped = g_gs_dropped, s.ws = g_gs_ws, s.ws_bytes = 16;
     s.ev[0] = (void *)0x30, s.ev[1] = (void *)0x31;
     s.cell = 2.0, s.down = 4.0, s.up = 3.0, s.quantile = 0.1, s.margin = 0.3, s.min_points = 8, s.min_keep = 5;
+    q.w.size = (int64_t)sizeof q.w;
+    q.w.ow_owner = g_ow_owner, q.w.ow_off = g_ow_off, q.w.ow_tile_off = g_ow_tile_off, q.w.ow_idx = g_ow_idx, q.w.ow_xyz = g_ow_xyz;
+    q.w.ow_status = g_ow_status, q.w.ow_lost = g_ow_lost, q.w.ws = g_ow_ws, q.w.ws_bytes = 16, q.w.rule = 1, q.w.min_keep = 5;
+    q.w.ev[0] = (void *)0x20, q.w.ev[1] = (void *)0x21;
     Case w = q;
     w.p.pose_rt = g_pose_rt, w.p.pose_inv = g_pose_inv, w.p.planes = 40;
 
@@ -305,6 +337,85 @@ int main()
     {
         Case y = q;
         std::printf("case bad.null_pass\nrc %d\n", cm3d_lift_pass_stripped(nullptr, nullptr, nullptr, &y.s, nullptr));
+    }
+
+    // ---- cm3d_lift_pass_owned: every presence combination of strip, cluster, filter, yaw, placement (with yaw only) and nms
+    g_entry = 'w';
+    for (int m = 0; m < 64; ++m) {
+        if ((m & 16) && !(m & 8)) continue;
+        char which[9] = "ow------", name[40];
+        if (m & 1) which[2] = 's';
+        if (m & 2) which[3] = 'c';
+        if (m & 4) which[4] = 'f';
+        if (m & 8) which[5] = 'y';
+        if (m & 16) which[6] = 'p';
+        if (m & 32) which[7] = 'n';
+        std::snprintf(name, sizeof name, "owned.combo.%s", which + 2);
+        run(name, q, which);
+    }
+    run("owned.combo_waymo.scfypn", w, "owscfypn");
+    run("owned.ok.null_opt", q, "w");
+    e = q, e.p.points = g_points;
+    run("owned.ok.cloud", e, "ows");
+    e = q, e.w.ev[0] = e.w.ev[1] = e.s.ev[0] = e.s.ev[1] = nullptr;
+    run("owned.ok.no_events", e, "owsc");
+    e = q, e.y.hit_xyz = g_ow_xyz, e.y.hit_off = g_ow_off;
+    run("owned.rule.ow_lists", e, "owy");
+    e = q, e.y.hit_xyz = g_gs_xyz, e.y.hit_off = g_gs_off;
+    run("owned.rule.gs_lists", e, "owsy");
+
+    // ---- every refusal makes no call
+    run("owned.bad.null_owner", q, "oscfypn");
+    e = q, e.w.size -= 8;
+    run("owned.bad.owner_size", e, "owscfypn");
+    const char *ows[] = {"ow_owner", "ow_off", "ow_tile_off", "ow_idx", "ow_xyz", "ow_status", "ow_lost", "ws"};
+    for (int i = 0; i < 8; ++i) {
+        char name[40];
+        e = q;
+        if (i == 0) e.w.ow_owner = nullptr;
+        if (i == 1) e.w.ow_off = nullptr;
+        if (i == 2) e.w.ow_tile_off = nullptr;
+        if (i == 3) e.w.ow_idx = nullptr;
+        if (i == 4) e.w.ow_xyz = nullptr;
+        if (i == 5) e.w.ow_status = nullptr;
+        if (i == 6) e.w.ow_lost = nullptr;
+        if (i == 7) e.w.ws = nullptr;
+        std::snprintf(name, sizeof name, "owned.bad.owner_no_%s", ows[i]);
+        run(name, e, "owscfypn");
+    }
+    e = q, e.w.rule = 2;
+    run("owned.bad.rule_2", e, "ow");
+    e = q, e.w.min_keep = 0;
+    run("owned.bad.min_keep_0", e, "owc");
+    e = q, e.p.hit_idx = nullptr;
+    run("owned.bad.pass_no_hit_idx", e, "ow");
+    e = q, e.s.gs_idx = nullptr;
+    run("owned.bad.strip_no_gs_idx", e, "ows");
+    e = q, e.s.cell = 0.0;
+    run("owned.bad.strip_param", e, "ows");
+    run("owned.bad.place_without_yaw", q, "owscfpn");
+    e = q, e.y.hit_xyz = g_hit_xyz, e.y.hit_off = g_hit_off;
+    run("owned.bad.raw_lists_behind_owner", e, "owy");
+    e = q, e.y.hit_xyz = g_ow_xyz, e.y.hit_off = g_ow_off;
+    run("owned.bad.ow_lists_behind_strip", e, "owsy");
+
+    // ---- cm3d_lift_pass_composed beside the entry point that takes the same arguments: every presence combination, and a NULL opt
+    for (int m = 0; m < 128 + 4; ++m) {                  // (the last four: opt == NULL, with and without an ownership and a strip)
+        if ((m & 32) && !(m & 16)) continue;
+        char which[9] = "o-------", name[40];
+        if (m & 1) which[1] = 'w';
+        if (m & 2) which[2] = 's';
+        if (m & 4) which[3] = 'c';
+        if (m & 8) which[4] = 'f';
+        if (m & 16) which[5] = 'y';
+        if (m & 32) which[6] = 'p';
+        if (m & 64) which[7] = 'n';
+        if (m & 128) which[0] = '-';
+        const char old_entry = std::strchr(which, 'w') ? 'w' : std::strchr(which, 's') ? 's' : std::strchr(which, 'p') ? 'p' : 'o';
+        std::snprintf(name, sizeof name, "equiv.old.%s", which);
+        g_entry = old_entry, run(name, q, which);
+        std::snprintf(name, sizeof name, "equiv.new.%s", which);
+        g_entry = 'x', run(name, q, which);
     }
     std::printf("pass_strip_sim done\n");
     return 0;

@@ -270,7 +270,7 @@ def _run_sim():
         rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
         csrc = os.path.join(ROOT, "cm3d_amd", "csrc")
         r = subprocess.run(SANITIZED + ["-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include"), os.path.join(ROOT, "tests", "pass_place_sim.cpp"),
-                                        os.path.join(csrc, "pass_place.cpp"), os.path.join(csrc, "pass_options.cpp"), "-o", exe],
+                                        os.path.join(csrc, "pass_compose.cpp"), os.path.join(csrc, "pass_options.cpp"), "-o", exe],
                            capture_output=True, text=True)
         assert r.returncode == 0, r.stderr
         r = subprocess.run([exe], capture_output=True, text=True)            # its own executable: the sanitizers' runtimes are linked in
@@ -344,7 +344,9 @@ def test_pass_options_cpp_does_not_know_the_placement():
     for rel in ("pass_options.cpp", "pipeline.cpp"):
         src = open(os.path.join(csrc, rel)).read()
         assert "box_place" not in src and "pass_placed" not in src and "pass_place" not in src, rel
-    assert open(os.path.join(csrc, "pass_place.cpp")).read().count("cm3d_lift_pass_opt(") == 1
+        assert "ground_strip" not in src and "point_owner" not in src and "pass_compose" not in src, rel
+    src = open(os.path.join(csrc, "pass_compose.cpp")).read()
+    assert src.count("cm3d_pass_seam_run(") == 1 and "cm3d_box_nms_bounded(" not in src
 
 
 # ------------------------------------------------------------------------------------------------ the C ABI

@@ -296,7 +296,7 @@ def _run_sim():
         exe = os.path.join(tmp, "pass_strip_sim")
         rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
         r = subprocess.run(SANITIZED + ["-D__HIP_PLATFORM_AMD__", "-isystem", os.path.join(rocm, "include"), os.path.join(ROOT, "tests", "pass_strip_sim.cpp"),
-                                        os.path.join(ROOT, "cm3d_amd", "csrc", "pass_strip.cpp"), os.path.join(ROOT, "cm3d_amd", "csrc", "pass_options.cpp"),
+                                        os.path.join(ROOT, "cm3d_amd", "csrc", "pass_compose.cpp"), os.path.join(ROOT, "cm3d_amd", "csrc", "pass_options.cpp"),
                                         "-o", exe], capture_output=True, text=True)
         assert r.returncode == 0, r.stderr
         r = subprocess.run([exe], capture_output=True, text=True)            # its own executable: the sanitizers' runtimes are linked in
