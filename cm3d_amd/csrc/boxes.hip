@@ -5,6 +5,8 @@
 // latency-bound (NMS); no HBM roofline applies.
 #include "common.h"
 #include "circle_nms.h"
+#include "lane_flat.h"
+#include <type_traits>
 
 // ---- nearest lane point (a10) ------------------------------------------------------------------
 // Reference: scipy cdist (float64) between every centroid and every lane point, np.argmin (first
@@ -18,7 +20,6 @@
 #define LG_MAX_CELLS 32768          // cells per table: the whole cell index lives in LDS (128 KiB) during the build
 #define LG_CELL0 4.0f               // preferred cell edge [m]
 #define LG_MAX_RINGS 64             // rings (256 m at the preferred cell size) a search may cover before the wave scans its whole table
-#define LG_BIG_CELL 12         // points in a cell above which the whole wave scans it together
 #define LG_BUILD_THREADS 1024
 
 struct LaneGrid { float x0, y0, h, inv_h; int gw, gh, cell_base; float margin; };
@@ -118,7 +119,6 @@ __global__ __launch_bounds__(LG_BUILD_THREADS) void k_lane_grid_build(const floa
     }
 }
 
-#define LG_PF 4                                       // points of a row segment requested per round trip (k_lane_nn_grid)
 // candidate (d2, j) against the running best under the reference's semantics:
 // minimise sqrt(d2) (float64), ties -> smaller original index.
 static __device__ __forceinline__ void lg_consider(double d2, int j, double &d2cut, double &sbest, int &jbest)
@@ -129,11 +129,56 @@ static __device__ __forceinline__ void lg_consider(double d2, int j, double &d2c
     }
 }
 
-// One wave per centroid.  Ring r has 8r cells (one for r = 0); lane u takes cell u of the ring,
-// scans that cell's points and the wave merges (sqrt(d2), index) lexicographically.
+// The state of one step's flat list (lane_flat.h): this lane's inclusive prefix sum and base, the total, and for the first ring batch the
+// five segments' sums and bases as wave-uniform values.
+struct LgFlat { int incl, base, T, i0, i1, i2, i3, b0, b1, b2, b3, b4; };
+
+// NR rounds of 64 flat positions from p0 on: the NR point loads of a lane go out together (clamped positions, masked afterwards), then the
+// live ones are considered.  FIRST: five segments, the position's segment from compares against uniform values; otherwise a binary search
+// over the lanes' prefix sums (ds_bpermute: the LDS crossbar, no LDS memory).  Collective.
+template <int NR, bool FIRST>
+static __device__ __forceinline__ void lg_flat_rounds(const LanePt *__restrict__ sorted, const LgFlat &f, int p0, int lane, double cx, double cy,
+                                                      double &d2cut, double &sbest, int &jbest)
+{
+    // (a record is read as ONE 16-byte word: read field by field, the index -- which only an improving candidate needs -- was loaded
+    // inside lg_consider's branch, a dependent round trip per improvement)
+    static_assert(sizeof(LanePt) == sizeof(int4), "one 16-byte load per record");
+    int4 pt[NR];
+#pragma unroll
+    for (int v = 0; v < NR; ++v) {
+        const int p = min(p0 + v * 64 + lane, f.T - 1);
+        int base;
+        if (FIRST) base = lf_pick5(p, f.i0, f.i1, f.i2, f.i3, f.b0, f.b1, f.b2, f.b3, f.b4);
+        else {
+            const int s = lf_segment(p, [&](int l) { return __builtin_amdgcn_ds_bpermute(l << 2, f.incl); });
+            base = __builtin_amdgcn_ds_bpermute(s << 2, f.base);
+        }
+        pt[v] = reinterpret_cast<const int4 *>(sorted)[p + base];
+    }
+#pragma unroll
+    for (int v = 0; v < NR; ++v) asm volatile("" : "+v"(pt[v].z));          // (the index arrives with the coordinates: see above)
+#pragma unroll
+    for (int v = 0; v < NR; ++v) {
+        if (p0 + v * 64 + lane < f.T) {
+            const double dx = cx - (double)__int_as_float(pt[v].x), dy = cy - (double)__int_as_float(pt[v].y);
+            lg_consider(dx * dx + dy * dy, pt[v].z, d2cut, sbest, jbest);
+        }
+    }
+}
+
+// One wave per centroid.  The rings around the centroid's cell are searched in batches; a batch is a short list of row segments, one per
+// lane, and the wave scans the segments' points as one flat list (lane_flat.h), merging (sqrt(d2), index) lexicographically at the end.
+//
+// WHO SCANS WHICH POINT DOES NOT CHANGE ANY RESULT (the flat scan deals a step's points to the lanes by position, the version before it
+// gave every segment to one lane and a long one to the whole wave):
+//  * lg_consider keeps, per lane, the lexicographic minimum of (sqrt(d2), original index) over the points that lane sees; its pruning
+//    only drops a point whose root is above the lane's own best, which cannot be that minimum.  The wave's argmin of the lanes' minima is
+//    therefore the minimum over the union of what the lanes saw, however the points were dealt;
+//  * wb, the wave minimum that drives the stop test, is the minimum of the same roots over the same visited set, so the batches visited,
+//    the fallback taken or not, and with them every output are the same.
 __global__ __launch_bounds__(256) void k_lane_nn_grid(const float *__restrict__ centroid, const int32_t *__restrict__ medoid_pos,
                                                       const int32_t *__restrict__ mask_frame, int n_masks,
-                                                      const int32_t *__restrict__ lane_off, const int32_t *__restrict__ frame_lane,
+                                                      const int32_t *__restrict__ lane_off, const int32_t *__restrict__ frame_lane, int n_tables,
                                                       const LaneGrid *__restrict__ grids, const int32_t *__restrict__ cell_start,
                                                       const LanePt *__restrict__ sorted, int max_rings,
                                                       int32_t *__restrict__ lane_idx, double *__restrict__ lane_dist)
@@ -141,18 +186,29 @@ __global__ __launch_bounds__(256) void k_lane_nn_grid(const float *__restrict__ 
     const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = cm3d_lane();
     if (k >= n_masks) return;
+    // One lane table in the batch (n_tables is wave-uniform): every frame maps to table 0, so the grid record and the table's bounds are
+    // requested in the first round with the mask's own words, and the frame_lane[mask_frame[k]] trip and the grids[tb] trip behind it
+    // are not made.  Several tables: the loads and their order as before.
+    LaneGrid g;
+    int lo0, lo1;
+    if (n_tables == 1) { g = grids[0]; lo0 = lane_off[0]; lo1 = lane_off[1]; }
     // (everything that only needs the mask's number is requested before the first branch: behind `if (medoid_pos[k] < 0) return` the other
-    // loads started a round trip later each)
-    const int mp = medoid_pos[k], mf = mask_frame[k];
-    const float cxf = centroid[3 * k], cyf = centroid[3 * k + 1];
+    // loads started a round trip later each -- and that is where the compiler moves a load whose value only the live path reads, so the
+    // empty statement below takes the values in front of the branch)
+    const int mp = medoid_pos[k];
+    int mf = n_tables == 1 ? 0 : mask_frame[k];
+    float cxf = centroid[3 * k], cyf = centroid[3 * k + 1];
+    asm volatile("" : "+v"(cxf), "+v"(cyf), "+v"(mf));
     if (mp < 0) { if (lane == 0) { lane_idx[k] = -1; lane_dist[k] = INFINITY; } return; }
-    const int tb = frame_lane[mf];
-    const LaneGrid g = grids[tb];
+    if (n_tables != 1) {
+        const int tb = frame_lane[mf];
+        g = grids[tb]; lo0 = lane_off[tb]; lo1 = lane_off[tb + 1];
+    }
     const double cx = (double)cxf, cy = (double)cyf;
     double d2cut = INFINITY, sbest = INFINITY;
     int jbest = 0x7FFFFFFF;
     bool resolved = true;
-    if (lane_off[tb + 1] > lane_off[tb] && cx == cx && cy == cy) {
+    if (lo1 > lo0 && cx == cx && cy == cy) {
         resolved = false;
         // (virtual) cell of the centroid; may lie outside the grid
         const double fi = floor((cx - (double)g.x0) * (double)g.inv_h), fj = floor((cy - (double)g.y0) * (double)g.inv_h);
@@ -160,35 +216,29 @@ __global__ __launch_bounds__(256) void k_lane_nn_grid(const float *__restrict__ 
         const int out_i = qi < 0 ? -qi : (qi >= g.gw ? qi - g.gw + 1 : 0);
         const int out_j = qj < 0 ? -qj : (qj >= g.gh ? qj - g.gh + 1 : 0);
         const int32_t *cs = cell_start + g.cell_base;
-        // Every lane brings the point range [a, b) of one cell (empty if it has none).  Short ranges are scanned by
-        // their lane; a long one (a cell where many lanes and connectors meet -- one lane would keep the whole wave
-        // waiting) is handed to the whole wave, 64 points per step.  Collective: call with all lanes.
-        auto visit = [&](int a, int b) {
-            const bool big = b - a > LG_BIG_CELL;
-            if (!big) {
-                // (LG_PF points per round trip, unconditional loads of a clamped index: one load per iteration made a segment of ten points
-                // ten dependent round trips -- 18 us for the launch alone, 45 with the other batches' kernels on the memory system)
-                for (int q = a; q < b; q += LG_PF) {
-                    LanePt p[LG_PF];
-#pragma unroll
-                    for (int v = 0; v < LG_PF; ++v) p[v] = sorted[min(q + v, b - 1)];
-#pragma unroll
-                    for (int v = 0; v < LG_PF; ++v) {
-                        if (q + v < b) {
-                            const double dx = cx - (double)p[v].x, dy = cy - (double)p[v].y;
-                            lg_consider(dx * dx + dy * dy, p[v].idx, d2cut, sbest, jbest);
-                        }
-                    }
-                }
+        // Every lane brings the point range [a, b) of one segment (empty if it has none).  The ranges laid end to end are one list of T
+        // points; the wave scans it 64 positions per round, the loads of up to LF_ROUNDS rounds in flight together, and loops only when
+        // T > 64 * LF_ROUNDS.  The number of live rounds is wave-uniform.  Collective: call with all lanes.
+        auto visit = [&](int a, int b, auto first) {
+            constexpr bool FIRST = decltype(first)::value;
+            const int len = b - a;
+            LgFlat f;
+            f.incl = cm3d_wave_incl_scan(len);
+            f.base = a - (f.incl - len);
+            f.T = __builtin_amdgcn_readlane(f.incl, 63);
+            if (FIRST) {
+                f.i0 = __builtin_amdgcn_readlane(f.incl, 0); f.i1 = __builtin_amdgcn_readlane(f.incl, 1);
+                f.i2 = __builtin_amdgcn_readlane(f.incl, 2); f.i3 = __builtin_amdgcn_readlane(f.incl, 3);
+                f.b0 = __builtin_amdgcn_readlane(f.base, 0); f.b1 = __builtin_amdgcn_readlane(f.base, 1);
+                f.b2 = __builtin_amdgcn_readlane(f.base, 2); f.b3 = __builtin_amdgcn_readlane(f.base, 3);
+                f.b4 = __builtin_amdgcn_readlane(f.base, 4);
             }
-            for (uint64_t bm = __ballot(big); bm; bm &= bm - 1) {
-                const int src = (int)__builtin_ctzll(bm);
-                const int ra = __builtin_amdgcn_readlane(a, src), rb = __builtin_amdgcn_readlane(b, src);
-                for (int q = ra + lane; q < rb; q += 64) {
-                    const LanePt p = sorted[q];
-                    const double dx = cx - (double)p.x, dy = cy - (double)p.y;
-                    lg_consider(dx * dx + dy * dy, p.idx, d2cut, sbest, jbest);
-                }
+            for (int p0 = 0; p0 < f.T; p0 += 64 * LF_ROUNDS) {
+                const int rem = f.T - p0;
+                if (rem <= 64) lg_flat_rounds<1, FIRST>(sorted, f, p0, lane, cx, cy, d2cut, sbest, jbest);
+                else if (rem <= 128) lg_flat_rounds<2, FIRST>(sorted, f, p0, lane, cx, cy, d2cut, sbest, jbest);
+                else if (rem <= 192) lg_flat_rounds<3, FIRST>(sorted, f, p0, lane, cx, cy, d2cut, sbest, jbest);
+                else lg_flat_rounds<LF_ROUNDS, FIRST>(sorted, f, p0, lane, cx, cy, d2cut, sbest, jbest);
             }
         };
         // Rings are searched in batches that grow with the distance: [0..2] (the 5 x 5 cells around the centroid --
@@ -221,7 +271,7 @@ __global__ __launch_bounds__(256) void k_lane_nn_grid(const float *__restrict__ 
                 const int rowc = min(max(row, 0), g.gh - 1), c0c = min(c0, g.gw - 1), c1c = max(c1, 0);
                 int a = cs[rowc * g.gw + c0c], b = cs[rowc * g.gw + c1c + 1];
                 if (!seg_ok) { a = 0; b = 0; }
-                visit(a, b);
+                if (r_lo == 0) visit(a, b, std::true_type()); else visit(a, b, std::false_type());
             }
             r_done = r_hi;
             // wave-wide best distance so far
@@ -321,7 +371,7 @@ extern "C" int cm3d_lane_nn(const float *centroid, const int32_t *medoid_pos, co
     if (workspace_bytes < cm3d_lane_nn_workspace_bytes(n_masks)) return CM3D_ERR_WORKSPACE;
     const LgLayout l = lg_layout(const_cast<void *>(grid), n_tables, n_lane_points);
     hipLaunchKernelGGL(k_lane_nn_grid, dim3((n_masks + 3) / 4), dim3(256), 0, (hipStream_t)stream, centroid, medoid_pos, mask_frame,
-                       n_masks, lane_off, frame_lane, l.grids, l.cell_start, l.sorted, LG_MAX_RINGS, lane_idx, lane_dist);
+                       n_masks, lane_off, frame_lane, n_tables, l.grids, l.cell_start, l.sorted, LG_MAX_RINGS, lane_idx, lane_dist);
     CM3D_CHECK_LAUNCH();
     return CM3D_OK;
 }

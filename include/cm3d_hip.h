@@ -340,7 +340,8 @@ int cm3d_selftest_sqrt(uint32_t first_bits, uint32_t last_bits, uint64_t *n_bad,
  * distance on (x,y) between float32-rounded centroids and lane points, first minimum.
  *  lane      float[L_total][3]  x,y,yaw (float32-rounded, as torch.Tensor(...) does at :278)
  *  lane_off  int32[T+1]         lane tables back to back
- *  frame_lane int32[F]          table of each frame
+ *  frame_lane int32[F]          table of each frame, in [0, T) (T = 1: every frame is on table 0; the search reads neither
+ *                               frame_lane nor mask_frame then)
  *  lane_idx  int32[n_masks] OUT index into the frame's table (-1 for masks without centroid)
  *  lane_dist double[n_masks] OUT
  *  Exactly the brute-force result (first minimum of the float64 distance); internally the lane points are
